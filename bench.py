@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- train-step Gaussians*views/sec of the edge-Gaussian hot path on N MI355X.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 200 --warmup 20
 
@@ -15,9 +15,11 @@ Workload (BASELINE.json): default = configs[1], "ABC-NEF 00004926, 100k Gaussian
 50 views @512x512, 1xMI355X" -- synthetic Gaussians of that shape (edgegaussians_amd/synth.py) seen from
 the scan's 50 REAL camera poses (tests/golden/cameras_00004926.npz, intrinsics rescaled 800 -> 512),
 loss strategy alternating like configs/ABC_DexiNed.json:85-92 after epoch 50 (bg_edge_ratio on
-every 5th step, whole otherwise).  The same run also measures config 1 (30 k Gaussians, north_star's
-stated target) and a trained-like variant (`other_workloads`), and `roofline.traffic` with two
-rocprofv3 --pmc passes over this script.
+every 5th step, whole otherwise).  A plain run does only what the headline needs: set up, warm up, time
+--steps steps, print the line (and with --dump-outputs DIR write what the timed steps computed as DIR/*.npy).
+With --full the same run also measures config 1 (30 k Gaussians, north_star's stated target) and a
+trained-like variant (`other_workloads`), `roofline.traffic` with two rocprofv3 --pmc passes over this
+script, per-kernel timings, repeat windows and the CPU baselines.
 """
 import argparse
 import json
@@ -352,9 +354,38 @@ def cpu_baseline(sc, budget_s=15.0, which="c"):
                       f"oracle/ref_torch.py on {torch.get_num_threads()} torch threads"}
 
 
-def measure(name, args, device, rank, world, backend, spread=False, steps=None, warmup=None, stages=True, vps=1):
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tr, loss_sum):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the trainer's parameters in the
+    reference's row order and layout (EdgeTrainer.state_dict), the accumulated absgrads that densification reads, and the
+    loss sum the window's read-back returned -- as <name>.npy (float32; the loss float64).  Above DUMP_MAX_BYTES in all,
+    the same seeded sample of rows of every per-Gaussian array (rows.npy holds their indices).  Every rank calls it (a
+    read-back may be collective); out_dir None: nothing is written."""
+    import numpy as np
+    arrs = {k.split(".")[-1]: v for k, v in tr.state_dict().items()}
+    arrs["absgrads"] = tr._in_reference_order(tr.absgrads)
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrs.items()}
+    if out_dir is None:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    n = tr.N
+    row_bytes = sum(a.nbytes for a in arrs.values()) // n
+    if row_bytes * n > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, (DUMP_MAX_BYTES - (1 << 16)) // (row_bytes + 8), replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    arrs["loss_sum"] = np.array([loss_sum], dtype=np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
+
+
+def measure(name, args, device, rank, world, backend, spread=False, steps=None, warmup=None, stages=True, vps=1,
+            dump_to=None):
     """One workload: pre-warm, W untimed + K timed steps between barriers, then (rank 0) a second window of the
-    same steps with HIP events between the kernels.  Returns the result dict (value, ms_per_step, roofline ...)."""
+    same steps with HIP events between the kernels.  Returns the result dict (value, ms_per_step, roofline ...).
+    dump_to(trainer, loss_sum) is called right behind the timed window's read-back."""
     import torch.distributed as dist
     from edgegaussians_amd import dist as egdist
     steps = args.steps if steps is None else steps
@@ -431,6 +462,9 @@ def measure(name, args, device, rank, world, backend, spread=False, steps=None, 
     # seen running its first 0.1-0.3 s of work 10-80 % slow (clocks / power state), which a fixed 25 ms pre-warm did
     # not always absorb: default-bench outliers of 87 us against 78.  With several ranks the count is fixed (every
     # rank must issue the same collectives).
+    # With --dump-outputs the count is fixed at the upper bound instead: the state the timed window starts from then
+    # depends on the arguments alone, so that two runs (two builds) can be compared output for output.
+    fixed_prewarm = world > 1 or args.profile_only or dump_to is not None
     pre_steps, chunk_t, best, calm = 0, [], float("inf"), 0
     while pre_steps < (400 if args.profile_only else (2000 if world > 1 else 10000)):  # (--profile-only: a known count)
         torch.cuda.synchronize()
@@ -439,7 +473,7 @@ def measure(name, args, device, rank, world, backend, spread=False, steps=None, 
         torch.cuda.synchronize()
         chunk_t.append(time.perf_counter() - t_c)
         pre_steps += 200
-        if world > 1 or args.profile_only:
+        if fixed_prewarm:
             continue
         best = min(best, chunk_t[-1])
         calm = calm + 1 if chunk_t[-1] <= 1.03 * best else 0
@@ -470,9 +504,11 @@ def measure(name, args, device, rank, world, backend, spread=False, steps=None, 
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss_sum = tr.pop_loss()  # raises IsectOverflow if ANY step since the last read-back dropped intersections
+    if dump_to is not None:
+        dump_to(tr, loss_sum)  # (before anything else steps the trainer)
     # two more windows of the same K steps (informational: `value` is the contract's window above)
     windows = [1e3 * dt / steps]
-    for rep in range(0 if args.profile_only else 2):
+    for rep in range(2 if args.full and not args.profile_only else 0):
         barrier()
         t1 = time.perf_counter()
         run(steps, warmup + (1 + rep) * steps)
@@ -487,11 +523,13 @@ def measure(name, args, device, rank, world, backend, spread=False, steps=None, 
     if tr.overflow_events or tr.rewalk_misses or tr.overflowed() or not math.isfinite(loss_sum):
         # (a replayed window would have been timed twice)
         raise SystemExit(f"invalid run: overflow events={tr.overflow_events} re-walk misses={tr.rewalk_misses} loss={loss_sum}")
-    m_last = tr.last_m()
     # M of EVERY view (count-only passes, one host sync each; the parameters are practically stationary: LR_SCALE): the
     # line's M -- and the algorithmic bytes of the roofline -- are MEANS over the views a measurement covered, not the M
-    # of whatever view came last (frac moved by 10 % from run to run with it)
-    m_by_view = [tr.count_intersections(v) for v in range(n_views)]
+    # of whatever view came last (frac moved by 10 % from run to run with it).  A plain run leaves
+    # them out; --profile-only keeps them (the kernel traces taken over it have always held these passes).
+    count_m = args.full or args.profile_only
+    m_last = tr.last_m() if count_m else None
+    m_by_view = [tr.count_intersections(v) for v in range(n_views)] if count_m else None
 
     def step_views(s):
         if dp is None:
@@ -502,15 +540,18 @@ def measure(name, args, device, rank, world, backend, spread=False, steps=None, 
         vs = [v for s in range(step0, step0 + k) for v in step_views(s)]
         return sum(m_by_view[v] for v in vs) / max(len(vs), 1)
 
-    m_timed, m_all = mean_m(warmup, steps), sum(m_by_view) / n_views
+    m_timed, m_all = (mean_m(warmup, steps), sum(m_by_view) / n_views) if count_m else (None, None)
+    m_fields = {} if not count_m else {
+        "tile_intersections_M": m_timed, "tile_intersections_M_is": "mean over the views of the timed window (this rank's)",
+        "tile_intersections_M_all_views": m_all, "tile_intersections_M_last_view": m_last,
+        "tile_intersections_M_min_max": [min(m_by_view), max(m_by_view)]}
     res = {
         "value": n * steps * world * vps / dt, "ms_per_step": 1e3 * dt / steps, "steps": steps, "warmup": warmup,
         "config": {"workload": f"{name}: {n} Gaussians (5:1 anisotropic, scale 0.004, opacity "
                                f"{'U(0.05,0.9)' if spread else '0.08'}), {n_views} views @{w}x{h}, {poses}, "
                                f"loss whole/bg_edge_ratio 4:1",
                    "n_gaussians": n, "views": n_views, "width": w, "height": h, "lr_scale": LR_SCALE, "poses": poses,
-                   "tile_intersections_M": m_timed, "tile_intersections_M_is": "mean over the views of the timed window (this rank's)",
-                   "tile_intersections_M_all_views": m_all, "tile_intersections_M_last_view": m_last, "tile_intersections_M_min_max": [min(m_by_view), max(m_by_view)],
+                   **m_fields,
                    "largest_tile_population": int(tr.max_tile_seen),
                    "views_per_step": world * vps,
                    "gaussian_row_order": "morton" if tr.spatial_order else "as given",
@@ -536,7 +577,10 @@ def measure(name, args, device, rank, world, backend, spread=False, steps=None, 
         "ms_per_step_windows": windows,  # the contract's window first, then two repeats of the same K steps
         "ms_per_step_min": min(windows), "ms_per_step_median": sorted(windows)[len(windows) // 2],
     }
-    if dp is not None:
+    if not (args.full or args.profile_only):  # (a plain run times one window: the repeats are --full's)
+        for k in ("ms_per_step_windows", "ms_per_step_min", "ms_per_step_median"):
+            del res[k]
+    if dp is not None and args.full:
         # exposed all-reduce time on the compute stream (events around the collective), over a short extra window:
         # every rank runs it (the collective is collective), every rank's figure is gathered onto rank 0
         comm_n, comm_max = 0, None
@@ -603,7 +647,7 @@ def measure(name, args, device, rank, world, backend, spread=False, steps=None, 
             nprof = _egl.load().eg_dp_host_profile(prof)
             res["native_dp_host_us_per_step"] = {"steps": int(nprof), "grad_step_kernels": prof[0], "ncclAllReduce": prof[1],
                                                  "adam_and_next_projection": prof[2]}
-    if stages and not args.profile_only and vps == 1:
+    if stages and args.full and not args.profile_only and vps == 1:
         # ---- per-kernel launch durations: HIP events recorded natively between the kernels of eg_train_step on
         # the launch stream, over a second window of the same steps (one sync).  With N ranks every rank runs the
         # window (the all-reduce is collective), rank 0 records.
@@ -659,7 +703,7 @@ def measure(name, args, device, rank, world, backend, spread=False, steps=None, 
             ab_t = algorithmic_bytes(n, m_timed, w * h)["step_total"]  # (the contract window's own views)
             res["step_roofline"] = {"algorithmic_bytes_per_step": ab_t, "achieved_GBps": ab_t / (dt / steps) / 1e9,
                                     "frac": ab_t / (dt / steps) / 1e9 / HBM_PEAK_GBS}
-    if dp is not None and not args.profile_only:
+    if dp is not None and args.full and not args.profile_only:
         # LAST (the replicas diverge from here on): the same enqueue path with the gradient collective left out on every
         # rank -- t_no_collective / t is the share of the step that is NOT the wire (RCCL latency + its stream stalls), so
         # that a scaling curve says what it lost to the collective and what to everything else
@@ -908,6 +952,14 @@ def main():
                     help="wrap the stages of every step in roctx ranges (eg_roctx_enable; for rocprofv3 --marker-trace)")
     ap.add_argument("--no-extra", action="store_true",
                     help="only the headline workload (skip the config1 and trained-like lines under other_workloads)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the repeat windows, per-view M, per-kernel HIP-event timing, "
+                         "the rocprofv3 traffic / kernel-trace / SQ passes, the sibling workloads, the CPU baselines and the "
+                         "data-parallel extras (a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed (parameters, absgrads, loss sum) as "
+                         "DIR/<name>.npy; the pre-warm then runs a fixed number of steps, so that the same arguments give "
+                         "the same inputs to every step")
     ap.add_argument("--extra-set", default="all", choices=["all", "target"],
                     help="which siblings ride on the line: 'all', or 'target' = only north_star's named configuration as a full "
                          "citizen (config 1 with its own roofline, traffic and CPU baseline) and the scan at its native 800x800 "
@@ -958,7 +1010,11 @@ def main():
         print(json.dumps({"metric": "train-step Gaussians*views/sec", "n_gpus": 1, "higher_is_better": True, "scaling": "weak",
                           "vs_baseline": None, "dtype": "f32", "data": "synthetic", **r}), flush=True)
         return
-    head = measure(args.config, args, device, rank, world, backend, spread=args.spread_opacity, vps=args.views_per_step)
+    dump_to = None
+    if args.dump_outputs is not None:
+        dump_to = lambda tr, loss_sum: dump_outputs(args.dump_outputs if rank == 0 else None, tr, loss_sum)  # noqa: E731
+    head = measure(args.config, args, device, rank, world, backend, spread=args.spread_opacity, vps=args.views_per_step,
+                   dump_to=dump_to)
     sc = head.pop("_scene")
     out = {
         "metric": "train-step Gaussians*views/sec",
@@ -967,7 +1023,7 @@ def main():
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
     }
     out.update({k: v for k, v in head.items() if k not in ("value", "ms_per_step", "steps", "warmup")})
-    single = world == 1 and not args.profile_only and not args.force_dp and args.views_per_step == 1
+    single = world == 1 and args.full and not args.profile_only and not args.force_dp and args.views_per_step == 1
     if single and rank == 0 and not args.no_traffic:
         stages, src = measure_traffic(args.config, args.spread_opacity)
         out["roofline"]["traffic"] = stages.get(out["roofline"]["kernel"]) if stages else None
@@ -1055,7 +1111,7 @@ def main():
                     out["kernel_trace_avg_us_config1"] = kt1
             if sc_config1 is not None and not args.no_cpu_baseline:
                 out["cpu_baseline_config1"] = cpu_baseline(sc_config1, min(args.cpu_budget, 8.0), args.cpu_oracle)
-    if world > 1 and not args.replicas and args.views_per_step == 1 and not args.no_extra:
+    if world > 1 and args.full and not args.replicas and args.views_per_step == 1 and not args.no_extra:
         # the overlapped mode of the data-parallel step (dist.py: two half batches per rank and step, the first half's
         # all-reduce hidden behind the second half's rasterisation): a sibling on the same line, every rank runs it
         r2 = measure(args.config, args, device, rank, world, backend, spread=args.spread_opacity, vps=2,
@@ -1069,8 +1125,9 @@ def main():
         dist.destroy_process_group()
     if args.steps < 200:
         out["warning"] = (f"--steps {args.steps}: a timed window of {args.steps * head['ms_per_step']:.1f} ms; windows below "
-                          "200 steps read up to ~7 % slow / noisy on a freshly started box (ms_per_step_windows holds two "
-                          "repeats; profiles/ holds 1000-step runs)")
+                          "200 steps read up to ~7 % slow / noisy on a freshly started box ("
+                          + ("ms_per_step_windows holds two repeats; " if args.full else "")
+                          + "profiles/ holds 1000-step runs)")
     if rank == 0:  # last thing on stdout: the one JSON line
         sys.stdout.flush()
         import ctypes

@@ -267,6 +267,113 @@ def boundary_trace(views):
     json.dump(TRACE, open(os.path.join(OUT, "boundary_trace.json"), "w"), indent=1, sort_keys=True)
 
 
+def ply_reader_fields():
+    """The vertex properties `io_utils.read_gaussian_params_from_ply` indexes, in order, recorded by handing it a stub
+    PLY whose vertex element logs every key it is asked for."""
+    from edgegaussians.utils import io_utils
+    asked = []
+
+    class _Vertex:
+        def __getitem__(self, key):
+            asked.append(key)
+            return np.zeros(1, dtype=np.float32)
+
+    saved = io_utils.PlyData
+    io_utils.PlyData = types.SimpleNamespace(read=lambda path: {"vertex": _Vertex()})
+    try:
+        io_utils.read_gaussian_params_from_ply("unused.ply")
+    finally:
+        io_utils.PlyData = saved
+    json.dump({"read_gaussian_params_from_ply": asked}, open(os.path.join(OUT, "ply_reader_fields.json"), "w"), indent=1)
+
+
+PROTOCOL_STEPS = [(0, "whole"), (1, "weighted"), (0, "bg_edge_ratio")]
+
+
+def reference_protocol():
+    """The reference's model class driven through the operator surface, `gsplat.rasterization` bound to the CPU oracle
+    of this repository: forward -> compute_projection_loss -> backward -> update_absgrads -> 4x Adam for three steps, then
+    the densify event that consumes the absgrads (edge_gs.py:197-324, 544-613; train_gaussians.py:81-106).  Recorded:
+    the inputs of every step (initial parameters, the cameras and masks the model built, the optimiser settings, the
+    background draw of the bg_edge_ratio step) and what came out (losses, parameters, absgrads, the densify decision)."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    from edgegaussians_amd import synth
+    from oracle import ref_torch as O
+    calls, draws = [], []
+
+    def rasterization(**kw):
+        calls.append((kw["viewmats"].detach().clone(), kw["Ks"].detach().clone()))
+        return O.rasterization(**kw)
+
+    randperm = torch.randperm
+
+    def recording_randperm(*a, **k):
+        r = randperm(*a, **k)
+        draws.append(r.clone())
+        return r
+
+    torch.Tensor.cuda = lambda self, *a, **k: self  # edge_gs.py:247 hard-codes .cuda()
+    saved = edge_gs.rasterization
+    edge_gs.rasterization = rasterization
+    W = H = 96
+    sc = synth.make_scene(400, 2, W, H, seed=3, scale=0.02)
+    cams = [OpenCVCamera(height=H, width=W, K=sc.Ks[v].numpy(), R=sc.viewmats[v, :3, :3].numpy(),
+                         t=sc.viewmats[v, :3, 3].numpy()) for v in range(2)]
+    torch.manual_seed(0)
+    model = edge_gs.EdgeGaussianSplatting(device="cpu")
+    model.poplutate_params(seed_points=sc.means.clone(), viewcams=cams, config=CFG["model"])
+    model.compute_image_masks([sc.gt[0], sc.gt[1]])
+    model.compute_weight_masks()
+    opts, _ = train_utils.get_optimizers_schedulers(model, CFG["training"]["optim"])
+    names = ["means", "scales", "quats", "opacities"]
+    out = {f"init_{k}": model.gauss_params[k].detach().numpy().copy() for k in names}
+    out["gt"] = sc.gt.numpy()
+    out["edge_masks"] = np.stack([model.edge_masks[i].numpy() for i in range(2)])
+    out["adam_lr"] = np.array([opts[k].param_groups[0]["lr"] for k in names], dtype=np.float64)
+    out["adam_betas"] = np.array([opts[k].param_groups[0]["betas"] for k in names], dtype=np.float64)
+    out["adam_eps"] = np.array([opts[k].param_groups[0]["eps"] for k in names], dtype=np.float64)
+    out["steps_view"] = np.array([s[0] for s in PROTOCOL_STEPS])
+    out["steps_strategy"] = np.array([s[1] for s in PROTOCOL_STEPS])
+    model.train()
+    losses = []
+    torch.randperm = recording_randperm
+    try:
+        for idx, strategy in PROTOCOL_STEPS:
+            o = model(idx)
+            loss = model.compute_projection_loss(o["rgb"][:, :, 0], sc.gt[idx], image_index=idx, strategy=strategy,
+                                                 bg_edge_pixel_ratio=1.0)
+            loss.backward()
+            model.update_absgrads()
+            for opt in opts.values():
+                opt.step()
+                opt.zero_grad()
+            losses.append(float(loss))
+    finally:
+        torch.randperm = randperm
+        edge_gs.rasterization = saved
+    assert len(draws) == 1 and len(calls) == len(PROTOCOL_STEPS)
+    out["bg_draw_step2"] = draws[0][:int(model.edge_masks[0].sum())].numpy()
+    out["viewmats"] = np.stack([c[0].numpy() for c in calls])
+    out["Ks"] = np.stack([c[1].numpy() for c in calls])
+    out["losses"] = np.array(losses, dtype=np.float64)
+    for k in names:
+        out[f"final_{k}"] = model.gauss_params[k].detach().numpy().copy()
+    out["absgrads"] = model.absgrads.numpy().copy()
+    out["absgrads_normalize_factor"] = np.array(model.absgrads_normalize_factor)
+    out["model_step"] = np.array(model.step)
+    out["radii_dtype"] = np.array(str(model.radii.dtype))
+    out["xys_shape"] = np.array(model.xys.shape)
+    masks = []
+    dup = model.dup_gaussians
+    model.dup_gaussians = lambda optimizers, mask: masks.append(torch.as_tensor(mask).clone()) or dup(optimizers, mask)
+    out["n_before_densify"] = np.array(model.means.shape[0])
+    model.duplicate_high_pos_gradients(opts)
+    out["dup_mask"] = masks[0].numpy()
+    out["n_after_densify"] = np.array(model.means.shape[0])
+    out["absgrads_len_after_densify"] = np.array(model.absgrads.shape[0])
+    np.savez_compressed(os.path.join(OUT, "reference_protocol.npz"), **out)
+
+
 def filter_projection(views, keep):
     """edge_extraction/filtering.py:80-123 run as-is on seeded points and the four fixture views."""
     from edgegaussians.edge_extraction import filtering
@@ -428,6 +535,10 @@ if __name__ == "__main__":
     if "--only-calendar" in sys.argv:
         replica_calendar()
         raise SystemExit(0)
+    if "--only-protocol" in sys.argv:
+        ply_reader_fields()
+        reference_protocol()
+        raise SystemExit(0)
     views, keep = cameras_and_edges()
     if "--only-train" in sys.argv:
         train_fixture(views)
@@ -449,5 +560,7 @@ if __name__ == "__main__":
     densify_cull(m, cams)
     boundary_trace(views)
     replica_calendar()
+    ply_reader_fields()
+    reference_protocol()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -1691,7 +1691,7 @@ def test_bench_line_contract(env):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "config1", "--steps", "20",
-                        "--warmup", "5", "--cpu-budget", "1", "--no-traffic", "--no-extra"], capture_output=True, text=True,
+                        "--warmup", "5", "--cpu-budget", "1", "--no-traffic", "--no-extra", "--full"], capture_output=True, text=True,
                        timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.strip()][-1]
@@ -1733,6 +1733,39 @@ def test_bench_line_contract(env):
     assert abs(rf["achieved"] - rf["algorithmic_bytes_per_launch"] / (rf["avg_launch_us"] * 1e-6) / 1e9) <= 1e-6 * rf["achieved"]
 
 
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(env, tmp_path):
+    """A plain `bench.py` run times exactly --steps steps of the headline path and measures nothing else (that is --full's);
+    `--dump-outputs DIR` writes what the timed steps computed, and the same arguments give the same outputs."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for tag in ("a", "b"):
+        dumps.append(str(tmp_path / tag))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", "config1", "--steps", "30",
+                            "--warmup", "5", "--dump-outputs", dumps[-1]], capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1]))
+    d = lines[0]
+    assert d["metric"] == "train-step Gaussians*views/sec" and d["unit"] == "Gaussians*views/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["steps"] == 30 and d["warmup"] == 5 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["n_gaussians"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "other_workloads", "stages_us", "ms_per_step_windows", "kernel_trace_avg_us"):
+        assert k not in d, k
+    assert "tile_intersections_M" not in d["config"]
+    n = d["config"]["n_gaussians"]
+    shapes = {"means": (n, 3), "scales": (n, 3), "quats": (n, 4), "opacities": (n, 1), "absgrads": (n,), "loss_sum": (1,)}
+    assert sorted(os.listdir(dumps[0])) == sorted(f"{k}.npy" for k in shapes)
+    assert sum(os.path.getsize(os.path.join(dumps[0], f)) for f in os.listdir(dumps[0])) <= 64 << 20
+    for k, shape in shapes.items():
+        a, b = (np.load(os.path.join(p, f"{k}.npy")) for p in dumps)
+        assert a.shape == shape and a.dtype == (np.float64 if k == "loss_sum" else np.float32), k
+        assert np.isfinite(a).all(), k
+        assert np.allclose(a, b, rtol=1e-5, atol=1e-7), f"{k}: two runs with the same arguments differ"
+    assert float(np.load(os.path.join(dumps[0], "absgrads.npy")).max()) > 0
+
+
 def test_bench_line_carries_the_target_configuration(env, golden_dir):
     """Round 6 (VERDICT r05 missing 3 / 4): north_star's named configuration -- config 1, ~30 k Gaussians on the scan's 50 views
     @512 x 512 -- rides on the line as a full citizen (value, its own roofline, its own CPU baseline on the same N), and the scan
@@ -1742,7 +1775,7 @@ def test_bench_line_carries_the_target_configuration(env, golden_dir):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "200", "--warmup", "10", "--cpu-budget", "2",
-                        "--no-traffic", "--extra-set", "target"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--no-traffic", "--extra-set", "target", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
     assert d["config"]["n_gaussians"] == 100_000  # the headline stays config 2
@@ -1805,7 +1838,7 @@ def test_bench_launches_its_own_ranks(env):
     envv = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     envv["EG_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "config1", "--steps", "20",
-                        "--warmup", "5", "--no-traffic", "--no-cpu-baseline"], capture_output=True, text=True,
+                        "--warmup", "5", "--no-traffic", "--no-cpu-baseline", "--full"], capture_output=True, text=True,
                        timeout=900, cwd=root, env=envv)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

@@ -10,7 +10,7 @@ for c in abc800 config1 config2; do
   python $R/tools/rocpd_summary.py /tmp/ks_$c/r_results.db $O/kernel_stats_${c}.txt > /dev/null
   echo "== $c"; head -8 $O/kernel_stats_${c}.txt | cut -c1-130
   cd $R
-  timeout 300 python bench.py --config $c --steps 1000 --warmup 100 --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --config $c --steps 1000 --warmup 100 --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -8,7 +8,7 @@ for n in 20000 30000 40000 50000 65000 80000; do
     export EG_BENCH_GAUSSIANS=$n
     if [ $leg = two ]; then export EG_TWO_KERNEL_BACKWARD=1; else unset EG_TWO_KERNEL_BACKWARD; fi
     for c in config1 config2; do
-      timeout 300 python bench.py --config $c --steps 1000 --warmup 100 --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | python -c "
+      timeout 300 python bench.py --full --config $c --steps 1000 --warmup 100 --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

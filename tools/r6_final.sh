@@ -8,15 +8,15 @@ python -m edgegaussians_amd.build 2>&1 | grep -v "^built" | tail -2
 rm -f $R/gpurun_out/parity_report.jsonl
 timeout 1800 python -m pytest tests -m gpu -q --tb=short 2>&1 | grep -v "$F" | tail -15 > $O/pytest_gpu.log
 cp $R/gpurun_out/parity_report.jsonl $O/parity_report.jsonl 2>/dev/null
-( time timeout 1200 python bench.py ) 2>$O/bench_default.err | tail -1 > $O/bench_default.json
-( time timeout 600 python bench.py --steps 20 --warmup 5 ) 2>$O/bench_driver_window.err | tail -1 > $O/bench_driver_window.json
-timeout 600 python bench.py --config config1 --no-extra 2>/dev/null | tail -1 > $O/bench_config1.json
-timeout 600 python bench.py --config abc800 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_abc800.json
-timeout 600 python bench.py --config config2 --init-opacity --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_config2_init_opacity.json
+( time timeout 1200 python bench.py --full ) 2>$O/bench_default.err | tail -1 > $O/bench_default.json
+( time timeout 600 python bench.py --full --steps 20 --warmup 5 ) 2>$O/bench_driver_window.err | tail -1 > $O/bench_driver_window.json
+timeout 600 python bench.py --full --config config1 --no-extra 2>/dev/null | tail -1 > $O/bench_config1.json
+timeout 600 python bench.py --full --config abc800 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_abc800.json
+timeout 600 python bench.py --full --config config2 --init-opacity --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_config2_init_opacity.json
 for c in config3 config4; do
-  timeout 900 python bench.py --config $c --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_${c}.json
+  timeout 900 python bench.py --full --config $c --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_${c}.json
 done
-timeout 300 python bench.py --force-dp --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | tail -1 > $O/bench_config2_force_dp.json
+timeout 300 python bench.py --full --force-dp --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | tail -1 > $O/bench_config2_force_dp.json
 timeout 300 python tools/train_abc_fixture.py 2>/dev/null | tail -5 > $O/train_abc_fixture.txt
 timeout 300 python tools/late_epoch_bench.py 2>/dev/null | grep -v "$F" > $O/late_epoch_bench.txt
 cd /tmp && export TMPDIR=/tmp

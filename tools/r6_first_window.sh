@@ -12,10 +12,10 @@ for c in config2 config1 config2; do
   cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/fw
   timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/fw -o r -- python $R/bench.py --config $c --steps 100 --warmup 10 --profile-only > /dev/null 2>&1
   cd $R
-  python bench.py --config $c --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | line "behind rocprofv3 $c"
+  python bench.py --full --config $c --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | line "behind rocprofv3 $c"
 done
 for i in 1 2; do
   python -m pytest tests/test_gpu_parity.py -q -x -k "fused_backward_kernel or binning" > /dev/null 2>&1
-  python bench.py --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | line "behind pytest config2"
+  python bench.py --full --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | line "behind pytest config2"
 done
 } 2>&1 | tee $O/summary.txt

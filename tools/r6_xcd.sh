@@ -11,7 +11,7 @@ for c in ${CONFIGS:-config3 config4 abc800}; do
   for leg in 1 0; do
     export EG_XCD_LARGE=$leg
     echo "== $c EG_XCD_LARGE=$leg"
-    timeout 900 python bench.py --config $c --steps 300 --warmup 30 --no-cpu-baseline --no-extra 2>/dev/null | python -c "
+    timeout 900 python bench.py --full --config $c --steps 300 --warmup 30 --no-cpu-baseline --no-extra 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

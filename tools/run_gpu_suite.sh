@@ -11,12 +11,12 @@ F='^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl'
 rm -f $R/gpurun_out/parity_report.jsonl
 timeout 1500 python -m pytest tests -m gpu -q --tb=short 2>&1 | grep -v "$F" | tail -15 > $O/pytest_gpu.log
 cp $R/gpurun_out/parity_report.jsonl $O/parity_report.jsonl 2>/dev/null
-( time timeout 900 python bench.py ) 2>$O/bench_default.err | tail -1 > $O/bench_default.json
-timeout 600 python bench.py --config config1 --no-extra 2>/dev/null | tail -1 > $O/bench_config1.json
-timeout 600 python bench.py --config config2 --init-opacity --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_config2_init_opacity.json
+( time timeout 900 python bench.py --full ) 2>$O/bench_default.err | tail -1 > $O/bench_default.json
+timeout 600 python bench.py --full --config config1 --no-extra 2>/dev/null | tail -1 > $O/bench_config1.json
+timeout 600 python bench.py --full --config config2 --init-opacity --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_config2_init_opacity.json
 for c in config3 config4; do
-  timeout 900 python bench.py --config $c --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_${c}.json
-  timeout 600 python bench.py --config $c --init-opacity --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | tail -1 > $O/bench_${c}_init_opacity.json
+  timeout 900 python bench.py --full --config $c --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $O/bench_${c}.json
+  timeout 600 python bench.py --full --config $c --init-opacity --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | tail -1 > $O/bench_${c}_init_opacity.json
 done
 tools/microbench/issue_rates > $O/issue_rates.txt 2>&1
 EG_FWD_PROF=1 python tools/fwd_prof.py config2 --spread 2>/dev/null | grep -v "^RCCL\|^HIP\|amdgpu.ids" > $O/fwd_wave_phases_config2.txt
@@ -25,7 +25,7 @@ EG_FWD_PROF=1 python tools/fwd_prof.py config4 --spread 2>/dev/null | grep -v "^
 for S in 1 2 4 8; do timeout 300 python bench.py --config config1 --scenes-per-gpu $S 2>/dev/null | tail -1 > $O/bench_config1_scenes$S.json; done
 timeout 300 python bench.py --config config1 --scenes-per-gpu 8 --scenes-driver threads 2>/dev/null | tail -1 > $O/bench_config1_scenes8_threads.json
 timeout 300 python bench.py --config config2 --scenes-per-gpu 4 2>/dev/null | tail -1 > $O/bench_config2_scenes4.json
-timeout 300 python bench.py --force-dp --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | tail -1 > $O/bench_config2_force_dp.json
+timeout 300 python bench.py --full --force-dp --no-cpu-baseline --no-traffic --no-extra 2>/dev/null | tail -1 > $O/bench_config2_force_dp.json
 timeout 300 python tools/bench_regularizers.py 2>/dev/null | tail -1 > $O/regularizers_timing.json
 timeout 300 python tools/operator_profile.py config2 2>/dev/null | grep -v "^RCCL\|^HIP\|amdgpu.ids" > $O/operator_profile_config2.txt
 ( echo "--- with edgegaussians_amd.optim.Adam ---"; timeout 300 python tools/operator_profile.py config2 native 2>/dev/null | grep -v "^RCCL\|^HIP\|amdgpu.ids" ) >> $O/operator_profile_config2.txt
