@@ -31,6 +31,8 @@ from typing import List, Optional, Protocol, Sequence, Union
 import torch
 import torch.distributed as dist
 
+from .journal import DataParallel, chunks
+
 
 class GradWorker(Protocol):
     """What the driver needs from a per-rank worker (EdgeTrainer implements it on the GPU)."""
@@ -229,8 +231,7 @@ class DataParallelStep:
         else:
             view, wmap = list(view), list(wmap)
         if self._journals:
-            w = self.worker
-            w._journal_push(("d", view, (wmap, next_view), w.epoch, w.loss_scale))
+            self.worker.prologue(DataParallel([view], [wmap], [next_view]))
         self._step_raw(view, wmap, next_view)
 
     # ------------------------------------------------------------------ K optimizer steps by one native call
@@ -239,7 +240,7 @@ class DataParallelStep:
         group's size (init_native_comm)."""
         from . import _lib
         w = self.worker
-        return (hasattr(w, "_dp_steps_raw") and getattr(w, "seg_cap", 0) > 0
+        return (hasattr(w, "dp_steps") and getattr(w, "seg_cap", 0) > 0
                 and _lib.load().eg_dp_world() == (dist.get_world_size(self.group) if dist.is_initialized() else 1))
 
     def steps(self, views: Sequence[int], wmaps: Sequence[torch.Tensor], next_view: Optional[int] = None) -> None:
@@ -253,12 +254,10 @@ class DataParallelStep:
             for v, w_, n_ in zip(views, wmaps, nxt):
                 self.step(v, w_, next_view=n_)
             return
-        w = self.worker
-        if self._journals:
-            w._reserve_tags(len(views))
-            for v, w_, n_ in zip(views, wmaps, nxt):
-                w._journal_push(("d", v, (w_, n_), w.epoch, w.loss_scale), reserve=False)
-        w._dp_steps_raw(views, list(wmaps), next_view, journalled=self._journals and w.replay_on_overflow)
+        w = self.worker  # (an EdgeTrainer: it journals)
+        for vs, ws, ns in chunks(views, list(wmaps), nxt):
+            w.prologue(DataParallel(vs, ws, ns))
+            w.dp_steps(vs, ws, ns[-1], journalled=w.replay_on_overflow)
 
     def _step_raw(self, view, wmap, next_view=None) -> None:
         """One (grad_step, all-reduce, apply_adam) triple -- also what a collective replay runs."""

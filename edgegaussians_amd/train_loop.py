@@ -273,8 +273,7 @@ def train(tr: EdgeTrainer, model_cfg: Dict, training_cfg: Dict, view_order: Call
         # neighbour table is rebuilt by every direction-regulariser step.)
         wayward = get("if_cull_wayward", False) and epoch in get("cull_wayward_at_epoch", [])
         if changed or wayward:
-            if tr._journal:
-                tr.flush()
+            tr.flush()
             tr.reset_absgrads()          # train_gaussians.py:218-219
         if changed:
             if tr.spatial_order:

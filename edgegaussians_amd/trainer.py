@@ -22,6 +22,7 @@ Differences from the reference that are deliberate (documented in DESIGN.md):
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import ctypes as C
@@ -34,6 +35,7 @@ from torch import Tensor
 
 from . import _lib
 from ._lib import AdamHyper, StepArgs, call, ptr, stream
+from .journal import WINDOW_TAGS, Batched, EpochMark, Regulariser, StepJournal, Steps, chunks
 
 TILE = 16
 
@@ -89,15 +91,16 @@ class EdgeTrainer:
         # steps instead of silently training on dropped intersections.  Costs one state copy (136 B per
         # Gaussian) per run of steps between read-backs.
         self.replay_on_overflow = bool(replay_on_overflow)
-        self._journal: List = []
+        self._journal = StepJournal(self)  # (also the tag counter of the chained forward: one fresh tag per enqueued step)
         self._snap: Optional[Dict] = None
+        # the stream of the last enqueue on this trainer's state (raw handle, torch.cuda.Stream): read-backs run on it, an
+        # enqueue from another stream first makes that stream wait for it
+        self._stream_h, self._stream = None, None
         self.overflow_events = 0
         self.rewalk_misses = 0  # replays caused by a transmittance stop while the re-walk launch was being skipped
         self.rewalk_hint = -1  # re-walk list length seen at the last read-back (launch-shape hint; -1 = unknown)
         self._projected: Optional[int] = None  # view already projected + binned by apply_adam(next_view=...)
         self._dp = None  # the DataParallelStep driving this trainer (dist.py), if any: read-backs and replays are collective
-        self._ws_tag = 0       # tags of the chained forward (eg_step_args.ws_tag): one fresh value per enqueued step
-        self._replaying = False  # inside _recover_from_overflow's replay of the journal
         self.chained_forward = bool(int(os.environ.get("EG_CHAINED", "1")))
         # round 6 (eg_step_args.two_kernel_backward): inside a native run of steps on a tile grid of <= 2048 tiles the backward of
         # a scene of <= 32768 Gaussians is ONE kernel (csrc/backward_fused.hip); != 0 (development: EG_TWO_KERNEL_BACKWARD=1)
@@ -139,6 +142,7 @@ class EdgeTrainer:
         self._hyper = AdamHyper()
         self._alloc_state()
         self._alloc_pixels()
+        self._bind_stream()
         # spatial_order: keep the Gaussian rows in 3-D Morton order (re-sorted after every densify / cull
         # event).  Neighbouring rows then project to neighbouring pixels in every view, so a binning
         # workgroup touches a handful of tile counters instead of hundreds and the gathers of the
@@ -170,7 +174,6 @@ class EdgeTrainer:
         self.g2d = torch.empty(N, 8, device=d)  # written (not accumulated) by the footprint backward
         self.tile_mask = torch.zeros(N, dtype=torch.int32, device=d)  # exact tile hits per Gaussian (bit mask)
         self.grads = torch.zeros(N, 12, device=d)  # [means3|quats4|scales3|opac1|absgrad-inc1] for all-reduce
-        self._grads_b = None
         self._args_cache: Dict = {}
         self._batches: Dict = {}  # C -> [C, ...] work buffers of train_step_batched (allocated on first use)
         self._grads_b = None      # second gradient buffer (data-parallel half-step overlap)
@@ -330,6 +333,7 @@ class EdgeTrainer:
     def ensure_capacity(self, slack: float = 1.3, views: Optional[List[int]] = None) -> int:
         """Sizes the isect buffers from a count-only sweep (called at start and after every
         densify / cull event, i.e. whenever N changes -- 22 times in a 400-epoch ABC run)."""
+        self._bind_stream()
         self._drop_projection()
         views = list(range(self.V)) if views is None else views
         m_max, tile_max, span_max = 0, 0, 0
@@ -387,7 +391,7 @@ class EdgeTrainer:
         a.wmap = wmap.data_ptr()
         a.loss_scale = self.loss_scale
         a.rewalk_hint = self._rewalk_arg(fused_adam)
-        a.ws_tag = self._next_tag(n_tags) if self.chained_forward else 0
+        a.ws_tag = self._journal.take(n_tags) if self.chained_forward else 0
         a.two_kernel_backward = 1 if (self.two_kernel_backward or getattr(self, "_side_by_side", False)) else 0
         if fused_adam:
             a.absgrads = ptr(self.absgrads)
@@ -411,27 +415,6 @@ class EdgeTrainer:
             return _lib.REWALK_SPECULATE
         return self.rewalk_hint
 
-    def _reserve_tags(self, n: int) -> None:
-        """Make sure n fresh, consecutive tags are left in 1 .. EG_MAX_WS_TAG (16 bits: the forward's hand-over granules
-        carry them).  When the range is used up (every 65 534 steps) the journal is flushed -- the sticky words of the
-        control block are about to go: look at them first -- the workspaces are zeroed and the tags start over, so that
-        a granule written 2^16 steps ago can never be mistaken for this call's.  Called BEFORE the steps are journalled
-        and before their arguments are built.  (A replay reserves the tags of its whole journal before it starts,
-        _recover_from_overflow: inside one this function never wraps.)"""
-        assert 0 < n <= _lib.MAX_WS_TAG, n
-        # (a replay draws up to two fresh tags per journalled entry and reserves them all up front: the journal is read
-        # back -- flushed -- before it grows past half the tag range, whatever the forward's mode)
-        if self._journal and not self._replaying and 2 * (len(self._journal) + n) > _lib.MAX_WS_TAG:
-            self.flush()
-        if self.chained_forward and self._ws_tag + n > _lib.MAX_WS_TAG:
-            assert not self._replaying, "a replay reserves its tags up front"
-            if self._journal:
-                self.flush()
-            else:  # nothing to replay, but the stall bit of control word 3 must not be zeroed unread
-                if self._ctl_bits()[1]:
-                    raise RuntimeError(self._STALL_MSG)
-            self._zero_workspaces()
-
     def _zero_workspaces(self) -> None:
         for ws in [self.workspace] + [b["workspace"] for b in self._batches.values()]:
             if ws is not None:
@@ -440,15 +423,6 @@ class EdgeTrainer:
         for rec in [getattr(self, "item_rec", None)] + [b.get("item_rec") for b in self._batches.values()]:
             if rec is not None:
                 rec.zero_()
-        self._ws_tag = 0
-
-    def _next_tag(self, n: int) -> int:
-        """First of n fresh, consecutive tags (see _reserve_tags, which the public entry points call before they
-        journal; here it only catches a caller that did not)."""
-        self._reserve_tags(n)
-        t = self._ws_tag + 1
-        self._ws_tag += n
-        return t
 
     def _drop_projection(self) -> None:
         """Forget the view pre-projected by apply_adam(next_view=...).  Its binning has counted the tile cursors
@@ -490,33 +464,50 @@ class EdgeTrainer:
         for i in range(4):
             h.group_steps[i] = self.group_steps[i]
 
+    # ------------------------------------------------------------------ the enqueue prologue
+    def prologue(self, entry=None) -> None:
+        """What every enqueue on this trainer's state does first: order it after the trainer's earlier work (on a change of
+        stream the current one waits for the last), size the isect buffers, and -- for a journalled `entry` (journal.py) --
+        reserve its call tags and journal it.  A run of steps is at most journal.WINDOW_TAGS long (journal.chunks)."""
+        self._bind_stream()
+        if self.capacity == 0:
+            self.ensure_capacity()
+        if entry is not None:
+            self._journal.reserve(entry.tags)
+            if self.replay_on_overflow:
+                self._journal.push(entry)
+
+    def _bind_stream(self) -> None:
+        h = stream()
+        if h != self._stream_h:
+            cur = torch.cuda.current_stream(self.dev)
+            if self._stream is not None:
+                cur.wait_stream(self._stream)
+            self._stream_h, self._stream = h, cur
+
+    def _on_stream(self):
+        """Context of the trainer's stream: read-backs and replays follow its last enqueue whatever stream is current."""
+        return contextlib.nullcontext() if self._stream_h == stream() else torch.cuda.stream(self._stream)
+
+    def _settle(self) -> None:
+        """In front of an operation that reads or replaces the state outside the journal: follow the trainer's stream and
+        verify (or repair) the steps since the last read-back."""
+        self._bind_stream()
+        self.flush()
+
     def train_step(self, view: int, wmap: Tensor) -> None:
         """One reference iteration (train_gaussians.py:81-106) for `view`, fully asynchronous.
         `wmap` [H,W]: the per-pixel loss weights of the strategy chosen for this step."""
-        if self.capacity == 0:
-            self.ensure_capacity()
-        self._reserve_tags(1)
-        if self.replay_on_overflow:
-            if not self._journal:
-                self._snapshot()
-            self._journal.append(("1", view, wmap, self.epoch, self.loss_scale))
+        self.prologue(Steps([view], [wmap]))
         self._step_raw(view, wmap)
 
     def train_steps(self, views: List[int], wmaps: List[Tensor]) -> None:
         """len(views) consecutive reference iterations (one optimizer step per view, exactly `train_step` in a loop)
         enqueued by ONE native call: no Python between the steps.  The learning rates / loss scale of the current
-        epoch apply to all of them."""
-        K = len(views)
-        if K == 0:
-            return
-        if self.capacity == 0:
-            self.ensure_capacity()
-        self._reserve_tags(K)
-        if self.replay_on_overflow:
-            if not self._journal:
-                self._snapshot()
-            self._journal.extend(("1", v, w, self.epoch, self.loss_scale) for v, w in zip(views, wmaps))
-        self._steps_raw(views, wmaps)
+        epoch apply to all of them.  (A run longer than a window goes out as several, read back in between.)"""
+        for vs, ws in chunks(views, wmaps):
+            self.prologue(Steps(vs, ws))
+            self._steps_raw(vs, ws)
 
     def _steps_raw(self, views, wmaps) -> None:
         a, va, wa = self._steps_begin(views, wmaps)
@@ -610,7 +601,7 @@ class EdgeTrainer:
             wp[i] = w.data_ptr()
         a.loss_scale = self.loss_scale
         a.max_tile_hint = getattr(self, "max_tile_seen", 0)
-        a.ws_tag = self._next_tag(1) if self.chained_forward else 0
+        a.ws_tag = self._journal.take(1) if self.chained_forward else 0
         journalled = fused_adam if journalled is None else journalled
         a.rewalk_hint = (_lib.REWALK_SPECULATE if (journalled and self.replay_on_overflow and b["rewalk_hint"] == 0
                                                    and self.rewalk_hint in (0, -1)) else b["rewalk_hint"])
@@ -630,22 +621,15 @@ class EdgeTrainer:
         """C = len(views) <= 8 views in ONE launch sequence (gridDim.y = view) and ONE optimizer step on the SUM of
         their gradients -- the semantics of C-way data parallelism (dist.py) on a single GPU.  A throughput mode:
         the reference steps after every view (train_gaussians.py:104-106)."""
-        if self.capacity == 0:
-            self.ensure_capacity()
         views, wmaps = list(views), list(wmaps)
-        self._reserve_tags(1)
-        if self.replay_on_overflow:
-            if not self._journal:
-                self._snapshot()
-            self._journal.append(("b", views, wmaps, self.epoch, self.loss_scale))
+        self.prologue(Batched(views, wmaps))
         self._batched_raw(views, wmaps, True)
 
     def grad_step_batched(self, views: List[int], wmaps: List[Tensor], slot: int = 0, journalled: bool = False) -> Tensor:
         """Forward + loss + backward of C views, gradients SUMMED into ``self.grads`` (layout of grad_step), or
         into a second buffer of the same layout (slot = 1: the data-parallel driver reduces one half step while
         the other is computed)."""
-        if self.capacity == 0:
-            self.ensure_capacity()
+        self.prologue()
         return self._batched_raw(list(views), list(wmaps), False, slot, journalled)
 
     # ------------------------------------------------------------------ overflow: journal, snapshot, replay
@@ -709,106 +693,57 @@ class EdgeTrainer:
             raise IsectOverflow("tile-intersection buffers overflowed and the steps since the last read-back "
                                 "cannot be replayed (journal off or data-parallel leg): results are invalid; "
                                 "buffers were grown, restart from the last checkpoint")
-        journal = list(self._journal)
-        epoch_now, ls_now = self.epoch, self.loss_scale
-        assert 2 * len(journal) <= _lib.MAX_WS_TAG, "journal longer than the tag range"
-        self._replaying = True
-        try:
-            for attempt in range(9):
-                if attempt > 0:
-                    missed, stall, over = flags()
-                    if not (missed or stall or over):
-                        self.epoch, self.loss_scale = epoch_now, ls_now
-                        return
-                    if attempt == 8:
-                        break
-                if stall and not over:  # (a stall next to an overflow is the overflow's: truncated item tables)
-                    raise RuntimeError(self._STALL_MSG)
-                if missed:
-                    self.rewalk_hint = -1  # stops exist: launch the re-walk from now on (the next read-back sizes it)
-                    for b in self._batches.values():
-                        b["rewalk_hint"] = -1
-                    self.rewalk_misses += 1
-                if missed or stall:
-                    for w in self._ctl_words():
-                        w.view(-1, 2)[:, 1].zero_()
-                    o = 4 * (self.T + self.max_items + 3)
-                    self.workspace[o:o + 4].zero_()
-                    for b in self._batches.values():
-                        b["workspace"][:, o:o + 4].zero_()
-                if over:
-                    self.overflow_events += 1
-                    self._grow_isect(2.0)  # (drops the batched work buffers as well: re-allocated, flags clear)
-                # the replayed steps draw fresh tags: reserve the whole journal's now (two per entry at most), so that the
-                # range cannot wrap -- flush, zero the workspaces -- in the middle of the replay
-                if self.chained_forward and self._ws_tag + 2 * len(journal) > _lib.MAX_WS_TAG:
-                    self._zero_workspaces()
-                self.total.zero_()
-                self.tile_counts.zero_()  # (a step that ran out of items leaves the cursors of the unserved tiles behind)
+        for attempt in range(9):
+            if attempt > 0:
+                missed, stall, over = flags()
+                if not (missed or stall or over):
+                    return
+                if attempt == 8:
+                    break
+            if stall and not over:  # (a stall next to an overflow is the overflow's: truncated item tables)
+                raise RuntimeError(self._STALL_MSG)
+            if missed:
+                self.rewalk_hint = -1  # stops exist: launch the re-walk from now on (the next read-back sizes it)
                 for b in self._batches.values():
-                    b["total"].zero_()
-                    b["tile_counts"].zero_()
-                self._restore()  # (the running loss sum included)
-                for kind, view, wmap, epoch, ls in journal:
-                    self.epoch, self.loss_scale = epoch, ls
-                    if kind == "1":
-                        self._step_raw(view, wmap)
-                    elif kind == "r":
-                        self._regulariser_raw(view, self.loss_acc[0], *wmap)
-                    elif kind == "e":
-                        self._mark_raw(view)
-                    elif kind == "d":  # a data-parallel step: every rank replays it, the collective included
-                        self._dp._step_raw(view, wmap[0], wmap[1])
-                    else:
-                        self._batched_raw(view, wmap, True)
-        finally:
-            self._replaying = False
+                    b["rewalk_hint"] = -1
+                self.rewalk_misses += 1
+            if missed or stall:
+                for w in self._ctl_words():
+                    w.view(-1, 2)[:, 1].zero_()
+                o = 4 * (self.T + self.max_items + 3)
+                self.workspace[o:o + 4].zero_()
+                for b in self._batches.values():
+                    b["workspace"][:, o:o + 4].zero_()
+            if over:
+                self.overflow_events += 1
+                self._grow_isect(2.0)  # (drops the batched work buffers as well: re-allocated, flags clear)
+            self.total.zero_()
+            self.tile_counts.zero_()  # (a step that ran out of items leaves the cursors of the unserved tiles behind)
+            for b in self._batches.values():
+                b["total"].zero_()
+                b["tile_counts"].zero_()
+            self._journal.replay()  # (restores the snapshot, then runs the journalled steps again)
         raise IsectOverflow("tile-intersection buffers still overflow after 8 doublings")
 
-    def _journal_push(self, entry, reserve: bool = True) -> None:
-        """(kind, a, b, epoch, loss_scale): snapshot the state in front of the first journalled step of a window."""
-        if reserve:
-            self._reserve_tags(2)  # (a data-parallel step with two half batches takes two)
-        if self.replay_on_overflow:
-            if not self._journal:
-                self._snapshot()
-            self._journal.append(entry)
-
     def journal_bytes(self) -> int:
-        """Bytes of the distinct weight maps the journal keeps alive (the per-step `bg_edge_ratio` draws are fresh
-        tensors: at 1600 x 1200 a window of 8 epochs holds ~0.7 GB of them); `train()` reads back early when this
-        grows past 512 MB."""
-        seen, total = set(), 0
-        def tensors(x):
-            if isinstance(x, Tensor):
-                yield x
-            elif isinstance(x, (list, tuple)):
-                for y in x:
-                    yield from tensors(y)
+        """Bytes of the weight maps the journal keeps alive (StepJournal.bytes); `train()` reads back early past 512 MB."""
+        return self._journal.bytes()
 
-        for entry in self._journal:
-            for t in tensors(entry[2]):
-                if t.data_ptr() not in seen:
-                    seen.add(t.data_ptr())
-                    total += t.numel() * t.element_size()
-        return total
-
-    def _scene_stream(self):
-        """Context of the stream this trainer's steps were last enqueued on by `train_steps_multi` (a no-op context for a
-        trainer that only ever ran on the current stream): read-backs and replays must follow the scene's own work."""
-        import contextlib
-        st = getattr(self, "_bound_stream", None)
-        return torch.cuda.stream(st) if st is not None else contextlib.nullcontext()
+    @property
+    def _ws_tag(self) -> int:
+        """The call tag of the last enqueued forward (the journal's counter)."""
+        return self._journal.tag
 
     def flush(self) -> None:
-        """Drain the stream, verify that no step since the last read-back overflowed (repairing it if one
-        did) and forget the journal.  Every operation that changes the state outside train_step calls it.
-        (A trainer driven by `train_steps_multi` does this on the scene's stream.)"""
-        with self._scene_stream():
-            r = self._read_words()
-            if r["overflow"] or r["missed"]:
-                self._recover_from_overflow()
-            self._journal.clear()
+        """Drain the trainer's stream, verify that no step since the last read-back overflowed (repairing it if one
+        did) and forget the journal.  Every operation that changes the state outside the journal calls it.  Nothing to
+        verify -- no read-back -- when the journal is empty."""
+        if self._journal:
+            with self._on_stream():
+                r = self._read_words()
+                if r["overflow"] or r["missed"]:
+                    self._recover_from_overflow()
+                self._journal.clear()
 
     # ------------------------------------------------------------------ epoch marks (no host sync)
     def _mark_raw(self, k: int) -> None:
@@ -822,51 +757,10 @@ class EdgeTrainer:
         k = self._n_marks
         if 1 + k >= self._loss_buf.numel():
             raise RuntimeError("mark_epoch: 64 epochs are parked; call pop_losses()")
+        self.prologue(EpochMark(k))
         self._mark_raw(k)
-        if self.replay_on_overflow and self._journal:
-            self._journal.append(("e", k, None, self.epoch, self.loss_scale))
         self._n_marks = k + 1
         return k
-
-    def train_step_staged(self, view: int, wmap: Tensor, mark=None) -> None:
-        """The same step as ``train_step`` but sequenced from Python, one C-ABI call per stage, with
-        ``mark(stage_name)`` called after each enqueue -- bench.py brackets the stages with HIP
-        events through it.  Results are identical to ``train_step`` (same kernels, same order)."""
-        if self.capacity == 0:
-            self.ensure_capacity()
-        mark = mark or (lambda name: None)
-        self._advance_all()
-        self._set_hyper()
-        fl = (_lib.FLAG_LOG_SCALES | _lib.FLAG_LOGIT_OPACITIES | _lib.FLAG_ANTIALIASED |
-              _lib.FLAG_TIGHT_TILES)
-        st = stream()
-        vm, K = ptr(self.viewmats[view]), ptr(self.Ks[view])
-        N, W, H = self.N, self.width, self.height
-        mark("start")
-        call("eg_project_fwd", ptr(self.means), ptr(self.quats), ptr(self.log_scales), ptr(self.logit_opacities),
-             vm, K, N, W, H, 0.01, 1e10, 0.3, 0.0, fl, ptr(self.splat), None, None, None, None, None, None,
-             ptr(self.tile_counts), None, st)
-        mark("project_fwd")
-        call("eg_tile_offsets", ptr(self.tile_counts), self.T, self.capacity, ptr(self.offsets),
-             ptr(self.item_offsets), ptr(self.total), st)
-        mark("tile_offsets")
-        call("eg_tile_emit", None, None, None, ptr(self.splat), fl, N, W, H, ptr(self.offsets), ptr(self.tile_counts),
-             self.capacity, ptr(self.keys), None, st)
-        mark("tile_emit")
-        call("eg_sort_pairs", ptr(self.keys), ptr(self.offsets), self.T, self.capacity, ptr(self.flatten_ids),
-             None, getattr(self, "max_tile_seen", 0), st)
-        mark("tile_sort")
-        call("eg_composite_fwd", ptr(self.splat), None, 1, ptr(self.offsets), ptr(self.flatten_ids), W, H,
-             ptr(self.render), ptr(self.alphas), ptr(self.last_ids), ptr(self.gt[view]), ptr(wmap),
-             self.loss_scale, ptr(self.vpix), ptr(self.loss_acc), ptr(self.item_offsets), ptr(self.total),
-             self.max_items, ptr(self.workspace), ptr(self.gtstop), self.rewalk_hint, st)
-        mark("composite_fwd")
-        call("eg_backward_fused", ptr(self.means), ptr(self.quats), ptr(self.log_scales),
-             ptr(self.logit_opacities), vm, K, N, W, H, 0.3, fl, ptr(self.splat), ptr(self.gtstop), ptr(self.g2d),
-             None, None, None, None, ptr(self.absgrads), ptr(self.adam_m), ptr(self.adam_v), C.byref(self._hyper), st)
-        mark("backward_fused")
-        self.absgrads_normalize_factor += 1
-        self.step += 1
 
     @staticmethod
     def timing_begin(n_steps: int) -> None:
@@ -894,8 +788,7 @@ class EdgeTrainer:
         blocks) for the data-parallel driver, which all-reduces them and then calls ``apply_adam``.
         journalled: the caller keeps a journal of its steps (DataParallelStep does), so the forward may speculate that no
         pixel reaches the transmittance stop, like train_step."""
-        if self.capacity == 0:
-            self.ensure_capacity()
+        self.prologue()
         a = self._args(view, wmap, False)
         if journalled:
             a.rewalk_hint = self._rewalk_arg(True)
@@ -910,12 +803,11 @@ class EdgeTrainer:
         self.step += 1
         return self.grads
 
-    def _dp_steps_raw(self, views: List[int], wmaps: List[Tensor], next_view: Optional[int], journalled: bool) -> None:
+    def dp_steps(self, views: List[int], wmaps: List[Tensor], next_view: Optional[int], journalled: bool) -> None:
         """K data-parallel steps of this rank by one native call (eg_train_steps_dp: grad -> RCCL all-reduce on the launch
-        stream -> Adam + projection of the next view); the host-side bookkeeping of K x (grad_step, apply_adam)."""
+        stream -> Adam + projection of the next view); the host-side bookkeeping of K x (grad_step, apply_adam).  Called by
+        DataParallelStep.steps after `prologue(journal.DataParallel(...))`."""
         K = len(views)
-        if self.capacity == 0:
-            self.ensure_capacity()
         for w in wmaps:
             assert w.is_cuda and w.is_contiguous() and w.shape == (self.height, self.width)
         self._advance_all()   # step 0's counts; the native loop advances them by k
@@ -947,6 +839,7 @@ class EdgeTrainer:
         """The four Adam steps on the (all-reduced) gradient buffer.  next_view: the view this rank rasterises next
         -- Adam and that view's projection + binning then run as ONE launch (eg_adam_emit) and the following
         `grad_step(next_view)` skips its projection."""
+        self._bind_stream()
         self._advance_all()
         self._set_hyper()
         c = self._args_cache.get("adam_ptrs")
@@ -1006,12 +899,10 @@ class EdgeTrainer:
         A float: the caller's host value (one sync for the journal check).  Returns the loss value as a float
         when want_value (one sync), else the device scalar."""
         device_lambda = avg_loss_sum is None
-        if device_lambda and self.replay_on_overflow:
-            if not self._journal:
-                self._snapshot()
-            self._journal.append(("r", kind, (scale_factor, dir_loss_num_nn, enforce_method), self.epoch, self.loss_scale))
-        elif self._journal:
-            self.flush()
+        if device_lambda:
+            self.prologue(Regulariser(kind, scale_factor, dir_loss_num_nn, enforce_method))
+        else:
+            self._settle()
         loss = self._regulariser_raw(kind, self.loss_acc[0] if device_lambda else avg_loss_sum, scale_factor,
                                      dir_loss_num_nn, enforce_method)
         return float(loss) if want_value else loss
@@ -1093,53 +984,50 @@ class EdgeTrainer:
                 "seen": seen, "batch_seen": batch_seen, "missed": missed != 0}
 
     def _sync_state(self) -> Dict:
-        with self._scene_stream():  # (train_steps_multi: on the scene's stream)
-            return self._sync_state_here()
-
-    def _sync_state_here(self) -> Dict:
-        """The read-back between runs of steps: checks the sticky flags (replaying the journalled steps when one is
-        raised), forgets the journal, zeroes the loss sums and refreshes launch-shape hints and buffer sizes."""
-        r = self._read_words()
-        if r["overflow"] or r["missed"]:  # sticky flags: SOME step since the last read-back must be repeated
-            self._recover_from_overflow()  # raises IsectOverflow when the steps cannot be replayed
+        """The read-back between runs of steps (on the trainer's stream): checks the sticky flags (replaying the journalled
+        steps when one is raised), forgets the journal, zeroes the loss sums and refreshes launch-shape hints and buffer sizes."""
+        with self._on_stream():
             r = self._read_words()
-        self._journal.clear()
-        self.loss_acc.zero_()
-        self._n_marks = 0
-        # the stream is drained anyway: refresh the launch-shape hints -- the longest exact-stop re-walk list since
-        # the last read-back (control word 2 of the compositing workspace) ...
-        o = 4 * (self.T + self.max_items + 2)
-        if r["seen"]:
-            self.workspace[o:o + 4].zero_()
-        # (hysteresis: a window without a stop does not send the forward back to its speculative mode at once -- a scene
-        # whose pixels stop now and then would pay a replayed window at every relapse; four calm windows do)
-        self._calm_windows = 0 if r["seen"] else getattr(self, "_calm_windows", 4) + 1
-        seen = r["seen"] if (r["seen"] or self._calm_windows >= 4 or self.rewalk_hint <= 0) else self.rewalk_hint
-        if seen != self.rewalk_hint:
-            self.rewalk_hint = seen
-            self._args_cache = {}
-        for b, seen in zip(self._batches.values(), r["batch_seen"]):
-            if seen or self._calm_windows >= 4 or b["rewalk_hint"] <= 0:
-                b["rewalk_hint"] = seen
-            if seen:
-                b["workspace"][:, o:o + 4].zero_()
-        # ... and the tile-sort launch hint from the last step's scan
-        m_last, tile_max = r["m_last"], r["tile_max"]
-        if tile_max > getattr(self, "max_tile_seen", 0):
-            self.max_tile_seen = tile_max
-            self._args_cache = {}
-        # ... and grow ahead of the drift (opacities climbing, Gaussians converging on the edges)
-        seg = self.seg_cap
-        if seg and tile_max * 1.15 > seg:  # a tile is about to outgrow its segment
-            seg = (int(tile_max * 1.5) // 128 + 2) * 128
-            if self.T * seg > (1 << 28):
-                seg = 0
-        cap = self.capacity
-        if m_last * 1.15 > cap:
-            cap = int(m_last * 1.5) + 4096
-        if seg != self.seg_cap or cap != self.capacity:
-            self._alloc_isect(cap, seg)
-        return r
+            if r["overflow"] or r["missed"]:  # sticky flags: SOME step since the last read-back must be repeated
+                self._recover_from_overflow()  # raises IsectOverflow when the steps cannot be replayed
+                r = self._read_words()
+            self._journal.clear()
+            self.loss_acc.zero_()
+            self._n_marks = 0
+            # the stream is drained anyway: refresh the launch-shape hints -- the longest exact-stop re-walk list since
+            # the last read-back (control word 2 of the compositing workspace) ...
+            o = 4 * (self.T + self.max_items + 2)
+            if r["seen"]:
+                self.workspace[o:o + 4].zero_()
+            # (hysteresis: a window without a stop does not send the forward back to its speculative mode at once -- a scene
+            # whose pixels stop now and then would pay a replayed window at every relapse; four calm windows do)
+            self._calm_windows = 0 if r["seen"] else getattr(self, "_calm_windows", 4) + 1
+            seen = r["seen"] if (r["seen"] or self._calm_windows >= 4 or self.rewalk_hint <= 0) else self.rewalk_hint
+            if seen != self.rewalk_hint:
+                self.rewalk_hint = seen
+                self._args_cache = {}
+            for b, seen in zip(self._batches.values(), r["batch_seen"]):
+                if seen or self._calm_windows >= 4 or b["rewalk_hint"] <= 0:
+                    b["rewalk_hint"] = seen
+                if seen:
+                    b["workspace"][:, o:o + 4].zero_()
+            # ... and the tile-sort launch hint from the last step's scan
+            m_last, tile_max = r["m_last"], r["tile_max"]
+            if tile_max > getattr(self, "max_tile_seen", 0):
+                self.max_tile_seen = tile_max
+                self._args_cache = {}
+            # ... and grow ahead of the drift (opacities climbing, Gaussians converging on the edges)
+            seg = self.seg_cap
+            if seg and tile_max * 1.15 > seg:  # a tile is about to outgrow its segment
+                seg = (int(tile_max * 1.5) // 128 + 2) * 128
+                if self.T * seg > (1 << 28):
+                    seg = 0
+            cap = self.capacity
+            if m_last * 1.15 > cap:
+                cap = int(m_last * 1.5) + 4096
+            if seg != self.seg_cap or cap != self.capacity:
+                self._alloc_isect(cap, seg)
+            return r
 
     def pop_loss(self) -> float:
         """Sum of the projection losses since the last read-back (the reference's avg_loss numerator,
@@ -1216,8 +1104,7 @@ class EdgeTrainer:
         N = self.N
         if N == 0:
             return
-        if self._journal:
-            self.flush()
+        self._settle()
         perm = self._morton_perm()
         m_old, v_old = self._moment_views(self.adam_m), self._moment_views(self.adam_v)
         names = list(self._params().keys())
@@ -1245,8 +1132,7 @@ class EdgeTrainer:
         """cull_gaussians (edge_gs.py:412-429) + remove_from_all_optim (:384-409): rows of the 4
         params, 8 moment tensors and absgrads where ~cull_mask, then the reference's opacity clamp
         (a probability-space constant applied in LOGIT space -- kept, it is what the reference does)."""
-        if self._journal:
-            self.flush()
+        self._settle()
         keep = (~cull_mask.to(self.dev).bool()).to(torch.uint8).contiguous()
         pos, n_keep = self._scan(keep)
         N = self.N
@@ -1279,16 +1165,14 @@ class EdgeTrainer:
 
     def cull_opacity(self, value: float = 0.05, reset_opacity_value: float = 0.08) -> int:
         """cull_gaussians_opacity, 'absolute' (edge_gs.py:477-488; every shipped config)."""
-        if self._journal:
-            self.flush()  # the mask must come from the verified state (steps may still be rolled back and replayed)
+        self._settle()  # the mask must come from the verified state (steps may still be rolled back and replayed)
         return self.cull(torch.sigmoid(self.logit_opacities) < value, reset_opacity_value)
 
     def duplicate(self, dup_mask: Tensor, dup_factor: int = 3, noise_scale: float = 0.05,
                   noise: Optional[Tensor] = None) -> int:
         """dup_gaussians (edge_gs.py:460-474) + dup_in_all_optim (:431-457): append dup_factor-1
         copies of the masked rows; means get N(0, noise_scale^2) noise, moments of new rows are 0."""
-        if self._journal:
-            self.flush()
+        self._settle()
         sel = dup_mask.to(self.dev).bool().to(torch.uint8).contiguous()
         pos, n_sel = self._scan(sel)
         copies = dup_factor - 1
@@ -1339,8 +1223,7 @@ class EdgeTrainer:
         config).  'percentile_top' (:559-568): the threshold is the int(1/value)-quantile boundary of the
         RAW mean absgrads ('lower' interpolation) -- and is then compared with the NORMALISED values, as the
         reference does."""
-        if self._journal:
-            self.flush()  # absgrads of steps that may still be replayed must not decide the mask
+        self._settle()  # absgrads of steps that may still be replayed must not decide the mask
         g = self.absgrads / self.absgrads_normalize_factor
         gn = (g - g.min()) / (g.max() - g.min())
         if threshold_type == "absolute":
@@ -1362,8 +1245,7 @@ class EdgeTrainer:
                             reset_opacity_value: float = 0.08) -> int:
         """cull_gaussians_not_projecting (edge_gs.py:578-601) as one N x V device kernel.
         edge_masks_u8: [V,H,W] uint8 (gt >= 0.5)."""
-        if self._journal:
-            self.flush()
+        self._settle()
         P = torch.bmm(self.Ks, self.viewmats[:, :3, :4]).contiguous()  # K @ viewmat[:3,:4]
         hits = torch.zeros(self.N, dtype=torch.int32, device=self.dev)
         call("eg_project_hits", ptr(self.means), self.N, ptr(P), self.V, ptr(edge_masks_u8.contiguous()),
@@ -1381,8 +1263,7 @@ class EdgeTrainer:
         """Weights only, like the reference's `--ckpt_path` (edge_gs.py:625-633, train_gaussians.py builds
         fresh optimizers after loading): Adam moments, absgrads AND every step counter (Adam bias
         correction, model.step alternation phase, absgrad normaliser) restart."""
-        if self._journal:
-            self.flush()
+        self._settle()
         f = dict(device=self.dev, dtype=torch.float32)
         self.means = state["gauss_params.means"].detach().to(**f).contiguous().clone()
         self.log_scales = state["gauss_params.scales"].detach().to(**f).contiguous().clone()
@@ -1398,8 +1279,7 @@ class EdgeTrainer:
     def state_dict(self) -> Dict[str, Tensor]:
         """Same keys / shapes -- and, whatever the internal row order, the same row order -- as the
         reference's checkpoint (edge_gs.py:625-633)."""
-        if self._journal:
-            self.flush()  # (speculated / overflowed steps are repaired before anything is exported)
+        self._settle()  # (speculated / overflowed steps are repaired before anything is exported)
         r = self._in_reference_order
         return {"gauss_params.means": r(self.means).clone(), "gauss_params.scales": r(self.log_scales).clone(),
                 "gauss_params.quats": r(self.quats).clone(),
@@ -1410,19 +1290,23 @@ def train_steps_multi(trainers: List["EdgeTrainer"], views: List[List[int]], wma
                       n_threads: int = 0) -> None:
     """K consecutive reference iterations of EACH of S independent scenes, enqueued by ONE native call
     (`eg_train_steps_multi`): scene s = `trainers[s].train_steps(views[s], wmaps[s])` on `streams[s]` (torch.cuda.Stream
-    objects, all different, none of them the stream a trainer's tensors are still being written on).  The scenes share
-    nothing -- every trainer ends exactly where its solo run ends (tests/test_gpu_parity.py) -- but one GPU runs their
-    launch sequences side by side: BASELINE configs[4] ("115-scan sweep, one scene per GPU") with S scenes per device.
-    n_threads: host threads inside the native call (0: one per scene, at most 8).  The weight maps must have been produced on
-    the scene's stream (or before a synchronisation).  The trainer remembers `streams[s]`: its later read-backs (`flush`,
-    `pop_loss`, `pop_losses`) and an overflow replay of these steps run on that stream whatever stream is current; any OTHER
-    call on the trainer (densify, single steps) must be made under `torch.cuda.stream(streams[s])` or after a synchronisation.  After a failure of the native call the trainers' states are undefined
-    (some scenes have enqueued more steps than others): restore them from checkpoints."""
+    objects, all different).  The scenes share nothing -- every trainer ends exactly where its solo run ends
+    (tests/test_gpu_parity.py) -- but one GPU runs their launch sequences side by side: BASELINE configs[4] ("115-scan
+    sweep, one scene per GPU") with S scenes per device.  n_threads: host threads inside the native call (0: one per scene,
+    at most 8).  The weight maps must have been produced on the scene's stream (or before a synchronisation).  Each trainer
+    orders its own work: its steps here follow its earlier work on any stream, and its later read-backs and enqueues
+    follow these steps.  After a failure of the native call the trainers' states are undefined (some scenes have
+    enqueued more steps than others): restore them from checkpoints."""
     S = len(trainers)
     assert S >= 1 and len(views) == S and len(wmaps) == S and len(streams) == S
     K = len(views[0])
     assert all(len(v) == K for v in views) and all(len(w) == K for w in wmaps), "the same number of steps for every scene"
     assert len({int(st.cuda_stream) for st in streams}) == S and len({id(t) for t in trainers}) == S
+    if K > WINDOW_TAGS:  # (a run longer than a window: one native call per window, read back in between)
+        for i in range(0, K, WINDOW_TAGS):
+            train_steps_multi(trainers, [v[i:i + WINDOW_TAGS] for v in views], [w[i:i + WINDOW_TAGS] for w in wmaps],
+                              streams, n_threads)
+        return
     if K == 0:
         return
     for tr, vs, ws in zip(trainers, views, wmaps):  # (checked BEFORE any trainer's host state moves)
@@ -1435,16 +1319,9 @@ def train_steps_multi(trainers: List["EdgeTrainer"], views: List[List[int]], wma
     for tr in trainers:
         tr._side_by_side = S >= 2
     for tr, vs, ws, sx in zip(trainers, views, wmaps, streams):
-        with torch.cuda.stream(sx):  # (whatever host-side preparation enqueues -- a tag wrap's zeroing, a snapshot -- goes to the scene's stream)
-            if tr.capacity == 0:
-                tr.ensure_capacity()
-            tr._reserve_tags(K)
-            if tr.replay_on_overflow:
-                if not tr._journal:
-                    tr._snapshot()
-                tr._journal.extend(("1", v, w, tr.epoch, tr.loss_scale) for v, w in zip(vs, ws))
+        with torch.cuda.stream(sx):  # (the trainer's work moves to the scene's stream)
+            tr.prologue(Steps(vs, ws))
             blocks.append(tr._steps_begin(vs, ws))
-        tr._bound_stream = sx  # (flush / pop_loss / a replay of these steps run on the scene's stream from now on)
     args = (C.POINTER(_lib.StepArgs) * S)(*[C.pointer(b[0]) for b in blocks])
     va = (C.POINTER(C.c_int32) * S)(*[C.cast(b[1], C.POINTER(C.c_int32)) for b in blocks])
     wa = (C.POINTER(C.c_void_p) * S)(*[C.cast(b[2], C.POINTER(C.c_void_p)) for b in blocks])

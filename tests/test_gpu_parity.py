@@ -2063,6 +2063,74 @@ def test_native_multi_scene_run_equals_the_solo_runs(env, n_threads):
     torch.cuda.synchronize()
 
 
+def test_a_trainer_orders_its_work_across_streams(env):
+    """A trainer driven by train_steps_multi on a side stream and then by train_steps on the current stream orders its own
+    work: the read-back follows the current stream's steps, sees their overflow and replays them -- the same parameters as
+    the same steps run on one stream with buffers that never overflow."""
+    _lib, synth, O = env
+    from edgegaussians_amd import EdgeTrainer, LRSchedule, train_steps_multi
+    sc = _overflow_scene(synth)
+    sched = LRSchedule(scales_start=0, quats_start=0, opacities_start=0)
+    mk = lambda: EdgeTrainer(sc.means, sc.log_scales, sc.quats, sc.logit_opacities, sc.viewmats, sc.Ks, sc.gt,  # noqa: E731
+                             sc.width, sc.height, schedule=sched)
+    ta, tb = mk(), mk()
+    ta.ensure_capacity(slack=1.0)
+    ta._alloc_isect(ta.capacity * 16, ta.seg_cap * 16)       # the oversized run, on the current stream only
+    tb.ensure_capacity(slack=1.0)
+    tight = (tb.m_max_seen + 64, (tb.max_tile_seen // 128 + 1) * 128)
+    w = [synth.weight_map("weighted", sc.gt[v]).cuda() for v in range(2)]
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    ta.train_steps([0, 1], w)
+    train_steps_multi([tb], [[0, 1]], [w], [side])
+    for t in (ta, tb):
+        assert math.isfinite(t.pop_loss()) and t.overflow_events == 0
+    torch.cuda.synchronize()
+    for t in (ta, tb):
+        t.logit_opacities.fill_(float(torch.logit(torch.tensor(0.9))))   # "training" raises the opacities
+    tb._alloc_isect(*tight)                                   # buffers that the next steps overflow
+    torch.cuda.synchronize()
+    for t in (ta, tb):
+        t.train_steps([0, 1, 0, 1], w * 2)                    # on the current stream
+    la, lb = ta.pop_loss(), tb.pop_loss()                     # (no synchronisation in between)
+    assert tb.overflow_events >= 1 and ta.overflow_events == 0 and not tb.overflowed()
+    assert abs(la - lb) <= 1e-6 * abs(la)
+    for k, v in ta.state_dict().items():
+        assert_close(tb.state_dict()[k], v, rtol=1e-6, name=k)
+    assert_close(tb.absgrads, ta.absgrads, rtol=1e-6, name="absgrads")
+    assert tb.adam_step == ta.adam_step and tb.step == ta.step
+
+
+def test_a_run_longer_than_the_tag_window_is_chunked_and_replayable(env):
+    """One train_steps of more than MAX_WS_TAG // 2 steps goes out as windows that are read back in between: the same
+    state as the same steps in two calls, and an overflow after it is replayed (the journal holds the last window only)."""
+    _lib, synth, O = env
+    from edgegaussians_amd import EdgeTrainer
+    from edgegaussians_amd.journal import WINDOW_TAGS
+    sc = _scene(synth, n=4000, w=96, h=80, views=3)
+    mk = lambda: EdgeTrainer(sc.means, sc.log_scales, sc.quats, sc.logit_opacities, sc.viewmats, sc.Ks, sc.gt,  # noqa: E731
+                             sc.width, sc.height)
+    a, b = mk(), mk()
+    a.ensure_capacity()
+    b.ensure_capacity()
+    assert a.max_tile_seen > 256  # (segments of 128 keys overflow below)
+    K = _lib.MAX_WS_TAG // 2 + 100
+    wm = [synth.weight_map("weighted", sc.gt[v]).cuda() for v in range(3)]
+    views = [k % 3 for k in range(K)]
+    a.train_steps(views, [wm[v] for v in views])
+    assert len(a._journal) == 100
+    b.train_steps(views[:WINDOW_TAGS], [wm[v] for v in views[:WINDOW_TAGS]])
+    b.train_steps(views[WINDOW_TAGS:], [wm[v] for v in views[WINDOW_TAGS:]])
+    for t in (a, b):
+        t._alloc_isect(t.capacity // 4, 128)                  # the next step overflows
+        t.train_step(0, wm[0])
+        assert math.isfinite(t.pop_loss()) and t.overflow_events >= 1 and not t.overflowed()
+    assert a.step == b.step == K + 1
+    for x, y in ((a.means, b.means), (a.log_scales, b.log_scales), (a.quats, b.quats), (a.logit_opacities, b.logit_opacities),
+                 (a.adam_m, b.adam_m), (a.adam_v, b.adam_v), (a.absgrads, b.absgrads)):
+        assert torch.equal(x, y)
+
+
 def test_roctx_ranges_do_not_change_a_step(env):
     """eg_roctx_enable(1) wraps the stages of eg_train_step in roctx ranges (SURVEY 5: tracing; rocprofv3 --marker-trace);
     with or without them the step is the same."""

@@ -10,6 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import bench  # noqa: E402
+from edgegaussians_amd.journal import Steps  # noqa: E402
 
 name = next((a for a in sys.argv[1:] if a.startswith("config")), "config2")
 tr, sc, whole, ratio, poses = bench.build_trainer(name, 0, "cuda:0", name != "config1")
@@ -30,11 +31,7 @@ for rep in range(REPS):
     vs = [(rep * K + s) % V for s in range(K)]
     wm = [ratio(v) if s % 5 == 0 else whole for s, v in enumerate(vs)]
     t = tick("weight maps (4 draws)", t)
-    tr._reserve_tags(K); t = tick("reserve tags", t)
-    if not tr._journal:
-        tr._snapshot()
-    t = tick("snapshot", t)
-    tr._journal.extend(("1", v, w, tr.epoch, tr.loss_scale) for v, w in zip(vs, wm)); t = tick("journal", t)
+    tr.prologue(Steps(vs, wm)); t = tick("prologue (tags, snapshot, journal)", t)
     a, va, wa = tr._steps_begin(vs, wm); t = tick("steps_begin (argument block)", t)
     from edgegaussians_amd._lib import call, ptr, stream
     import ctypes as C
