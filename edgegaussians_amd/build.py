@@ -25,11 +25,7 @@ SOURCES = ["project.hip", "binning.hip", "composite.hip", "composite_wave.hip", 
 # (profiles/r03_slp_ab.txt): footprint backward -12 % on top of its own rewrite, projection backward -4 %.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-slp-vectorize",
          "-Wall", "-Wno-unused-function"]
-# EG_DEV_SWITCHES=1 at BUILD time compiles the A/B environment switches of the kernels' launchers in (NOTES_r04.md);
-# a release build reads no environment variable on the product path except EG_FWD_PROF (the profiling instantiation)
-if os.environ.get("EG_DEV_SWITCHES"):
-    FLAGS.append("-DEG_DEV_SWITCHES")
-FLAGS += os.environ.get("EG_EXTRA_HIPCC_FLAGS", "").split()  # (development: compile-time A/B legs)
+FLAGS += os.environ.get("EG_EXTRA_HIPCC_FLAGS", "").split()  # (development: e.g. -DEG_SORT_PROF, -DEG_BF_PROF)
 
 
 def _hipcc() -> str:
@@ -46,7 +42,7 @@ def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     if not os.path.exists(STAMP) or open(STAMP).read() != " ".join(FLAGS):
-        return True  # (built with other flags, e.g. a development build with EG_DEV_SWITCHES)
+        return True  # (built with other flags, e.g. a development build with EG_EXTRA_HIPCC_FLAGS)
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in SOURCES + ["common.h", "composite.h", "project_dev.h", "footprint_dev.h"]]
     deps.append(os.path.join(HERE, "..", "include", "edgegs.h"))

@@ -38,12 +38,6 @@
 
 namespace eg {
 
-#ifndef EG_BF_WAVES_PER_EU
-#define EG_BF_WAVES_PER_EU 4
-#endif
-#ifndef EG_BF_HOIST
-#define EG_BF_HOIST 0  // (1: phase 2's loads requested before the walks -- measured 17.8 against 17.5 us at config 1, profiles/r06_misc_ab.txt)
-#endif
 constexpr int kBFWaves = 8;                 // waves per workgroup
 constexpr int kBFGauss = 8 * kBFWaves;      // Gaussians per workgroup = lanes of the phase-2 wave
 constexpr int kBFTouched = 512;             // touched-tile list (beyond it: the wave sweeps the whole histogram)
@@ -66,9 +60,9 @@ struct FusedBwdArgs {
 
 // Phase 2 of the fused kernel: projection VJP + absgrads + Adam of Gaussian g of
 // view k, then the projection + exact tile binning of the NEXT view with the updated parameters still in registers; one
-// Gaussian per lane of ONE wave, no workgroup barrier.  raw / ag0 / mm / vv: the Gaussian's parameters, absgrad accumulator
-// and Adam moments as loaded by the caller (EG_BF_HOIST) or to be loaded here; ga / gb: its g2d record.  s_hist [T] zeroed,
-// s_base [T], s_touched [kBFTouched], s_ntouched zeroed: the wave's LDS.
+// Gaussian per lane of ONE wave, no workgroup barrier.  raw / mm / vv: zeroed storage for the Gaussian's parameters and
+// Adam moments, loaded here; ga / gb: its g2d record.  s_hist [T] zeroed, s_base [T], s_touched [kBFTouched], s_ntouched
+// zeroed: the wave's LDS.
 struct TailLds {
   int *hist, *base, *touched, *ntouched;
 };
@@ -84,7 +78,7 @@ struct TailLds {
 #else
 #define EG_BF_STAMP2(k_) do {} while (0)
 #endif
-__device__ __forceinline__ void gaussian_tail(const FusedBwdArgs &a, const int g, const int lane, Raw raw, const float ag0,
+__device__ __forceinline__ void gaussian_tail(const FusedBwdArgs &a, const int g, const int lane, Raw raw,
                                               float (&mm)[11], float (&vv)[11], const float4 ga, const float4 gb,
                                               const TailLds lds, unsigned long long *prof_rec) {
   const int width = a.width, height = a.height, N = a.N;
@@ -94,9 +88,9 @@ __device__ __forceinline__ void gaussian_tail(const FusedBwdArgs &a, const int g
   int &s_ntouched = *lds.ntouched;
   const bool alive = g < N;
   if (alive) {
-#if !EG_BF_HOIST
+    // (loaded here, not before the walks: requested there they measured 17.8 against 17.5 us at config 1,
+    // profiles/r06_misc_ab.txt)
     raw = load_raw(a.means, a.quats, a.scales, a.opacities, g);
-#endif
     const int radius = __float_as_int(splat[2 * g + 1].w);
     const size_t oM = 0, oS = 3 * (size_t)N, oQ = 6 * (size_t)N, oO = 10 * (size_t)N;
     const Cam cam = load_cam(a.viewmat, a.K);
@@ -107,18 +101,13 @@ __device__ __forceinline__ void gaussian_tail(const FusedBwdArgs &a, const int g
     for (int k = 0; k < 4; ++k) gr.quat[k] = 0.f;
     gr.opac = 0.f;
     if (radius > 0) {
-#if EG_BF_HOIST
-      const float ag = ag0;
-#else
       const float ag = a.absgrads ? a.absgrads[g] : 0.f;
-#endif
       Fwd f;
       forward_geom(cam, raw, width, height, -3.0e38f, 3.0e38f, a.eps2d, a.flags, f);
       backward_geom(cam, f, a.eps2d, a.flags, ga, gb, false, 0.f, 0.f, gr);
       if (a.absgrads) a.absgrads[g] = ag + sqrtf(ga.z * ga.z + ga.w * ga.w);
     }
     EG_BF_STAMP2(3);  // parameters loaded, forward recomputed, projection VJP
-#if !EG_BF_HOIST
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       mm[k] = a.am[oM + 3 * g + k]; vv[k] = a.av[oM + 3 * g + k];
@@ -127,7 +116,6 @@ __device__ __forceinline__ void gaussian_tail(const FusedBwdArgs &a, const int g
 #pragma unroll
     for (int k = 0; k < 4; ++k) { mm[6 + k] = a.am[oQ + 4 * g + k]; vv[6 + k] = a.av[oQ + 4 * g + k]; }
     mm[10] = a.am[oO + g]; vv[10] = a.av[oO + g];
-#endif
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       adam1(raw.m[k], gr.mean[k], mm[k], vv[k], 0, a.hyper);
@@ -218,7 +206,7 @@ __device__ __forceinline__ void gaussian_tail(const FusedBwdArgs &a, const int g
   EG_BF_STAMP2(7);  // keys stored
 }
 
-__global__ void __launch_bounds__(64 * kBFWaves) __attribute__((amdgpu_waves_per_eu(EG_BF_WAVES_PER_EU, EG_BF_WAVES_PER_EU)))
+__global__ void __launch_bounds__(64 * kBFWaves) __attribute__((amdgpu_waves_per_eu(4, 4)))
 gaussian_bwd_fused_kernel(const FusedBwdArgs a) {
   // LDS: a workgroup keeps its allocation until its LAST wave ends, i.e. through phase 2, where one wave of eight is left:
   // what a workgroup holds decides how many footprint walks run next to the projection chains (a first version with
@@ -253,29 +241,12 @@ gaussian_bwd_fused_kernel(const FusedBwdArgs a) {
 #define EG_BF_STAMP(k_) do {} while (0)
 #endif
   EG_BF_STAMP(0);
-  // (EG_BF_HOIST: what phase 2 reads of its Gaussian -- 11 parameters, the absgrad accumulator, 22 Adam moments -- requested
-  // HERE by the wave that will run it, before the walks, 35 registers held through phase 1.  Built and measured: no gain,
-  // the round trip hides behind the other waves' walks anyway; off.)
   const int g2 = blockIdx.x * kBFGauss + lane;  // phase 2's Gaussian of this lane (first wave)
+  // (phase 2's storage is declared out here: inside gaussian_tail the kernel's registers are allocated differently)
   Raw raw = {};
-  float ag0 = 0.f, mm[11], vv[11];
+  float mm[11], vv[11];
 #pragma unroll
   for (int k = 0; k < 11; ++k) mm[k] = vv[k] = 0.f;
-#if EG_BF_HOIST
-  if (wv == 0 && g2 < a.N) {
-    const size_t N_ = (size_t)a.N, oS = 3 * N_, oQ = 6 * N_, oO = 10 * N_;
-    raw = load_raw(a.means, a.quats, a.scales, a.opacities, g2);
-    ag0 = a.absgrads ? a.absgrads[g2] : 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      mm[k] = a.am[3 * g2 + k]; vv[k] = a.av[3 * g2 + k];
-      mm[3 + k] = a.am[oS + 3 * g2 + k]; vv[3 + k] = a.av[oS + 3 * g2 + k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { mm[6 + k] = a.am[oQ + 4 * g2 + k]; vv[6 + k] = a.av[oQ + 4 * g2 + k]; }
-    mm[10] = a.am[oO + g2]; vv[10] = a.av[oO + g2];
-  }
-#endif
 
   // ---------------------------------------------------------------- phase 1: footprint walks (footprint_bwd_kernel's body)
   if (a.loss_part && blockIdx.x == 0 && wv == 1) {  // (the second wave: the first one sizes the footprints)
@@ -387,7 +358,7 @@ gaussian_bwd_fused_kernel(const FusedBwdArgs a) {
 #else
     unsigned long long *pr = nullptr;
 #endif
-    gaussian_tail(a, g2, lane, raw, ag0, mm, vv, ga, gb, lds, pr);
+    gaussian_tail(a, g2, lane, raw, mm, vv, ga, gb, lds, pr);
   }
 }
 

@@ -278,14 +278,9 @@ __device__ __forceinline__ unsigned block_reduce_u32(unsigned v, bool take_max, 
 }
 
 constexpr int kMaxBucketFill = 96;  // beyond this a bucket's rank pass degenerates: use the network
-#ifndef EG_SORT_BM
-#define EG_SORT_BM 2  // (round 5, final kernel, same box: 7.81 / 11.45 / 31.07 -> 7.59 / 11.22 / 30.14 us at configs 1 / 2 / 3; 4: config 3 36.3)
-#endif
-#ifndef EG_SORT_RANK_G
-#define EG_SORT_RANK_G 1
-#endif
-constexpr int kSortBM = EG_SORT_BM;          // buckets per thread of the bucket + rank sort
-constexpr int kSortRankG = EG_SORT_RANK_G;   // keys a thread ranks side by side (their LDS reads in flight together)
+// buckets per thread of the bucket + rank sort (round 5, final kernel, same box: 7.81 / 11.45 / 31.07 -> 7.59 / 11.22 / 30.14 us
+// at configs 1 / 2 / 3; 4: config 3 36.3)
+constexpr int kSortBM = 2;
 
 // Segmented layout (eg_project_emit): tile t owns keys[t * seg_cap ...), its population sits in
 // cursor[t] and the first of its items (128-Gaussian slices) in item_first[t].  The small variant
@@ -306,7 +301,6 @@ struct SegTable {
   // the compositing kernel returns them to zero -- and the last tile's workgroup leaves the totals
   // [4]: M, sticky overflow flag, items, largest tile population.
   int *total;
-  int *total_flag = nullptr;   // the view's [4] totals for a kernel that does not form them (`total` == nullptr): only [1], the sticky overflow flag, is raised
   // optional output for the wave-autonomous forward (composite_wave.hip): one 16-byte record per item
   // {tile, slice | slices << 16, rec_tag, end of the TILE's keys}   (the slice's first key is tile * seg_cap + 128 slice)
   int4 *item_rec;
@@ -331,9 +325,6 @@ struct SegTable {
   // dispatched right behind its front ones and sat waiting for their anchor's inclusive granule, half of the forward's
   // wave slots at 500 k Gaussians; dispatched after every tile's front they find the dead word set and leave at once.
   const int *item_front = nullptr;
-  // round 6, without `total`, xcd_shift > 0 (and item_front, total_flag): the XCD-aware placement on grids above 2048 tiles --
-  // tiles dealt to the XCDs in bands of 2^xcd_shift tile ROWS, xcd = (ty >> xcd_shift) & 7, positions from the two prefixes the
-  // projection's scan leaves anyway (see the kernel); class boundary EG_FRONT_LARGE; every tile has a record (no skip_empty)
   int middle_out = 0;   // workgroup -> tile assignment of the small sort variant (see the kernel)
   // Round 5.  Every record carries the CALL TAG of the forward that will read it in word 2 (the forward validates a
   // record by its tag: the table may have holes, and a record of an earlier call is not mistaken for this call's).
@@ -366,15 +357,8 @@ struct SegTable {
   unsigned long long *prof = nullptr;
 #endif
 };
-#ifndef EG_XCD_SHIFT_DEFAULT
-#define EG_XCD_SHIFT_DEFAULT 1
-#endif
 constexpr int kXcdMinTiles = 512;  // XCD-aware placement on grids of 512 .. 2048 tiles (the reference's 512 x 512 images: 1024)
-constexpr int kXcdShiftDefault = EG_XCD_SHIFT_DEFAULT;  // XCD-aware record placement: tiles per block side = 2^shift (0 = off)
-#ifndef EG_SORT_GRID_DIV
-#define EG_SORT_GRID_DIV 1
-#endif
-constexpr int kSortGridDiv = EG_SORT_GRID_DIV;  // tiles per workgroup of the small sort variant (launch_tile_sort)
+constexpr int kXcdShiftDefault = 1;  // XCD-aware record placement: tiles per block side = 2^shift
 constexpr int kFrontDefault = 4;  // class boundary of the dispatch order (slices); SegTable::slice_major carries it
 
 // THREADS = number of buckets; CAP = keys per buffer (two buffers).  n_lo < n handled here.
@@ -384,13 +368,7 @@ template <int THREADS, int CAP, bool LARGE, bool PREFIX3 = false>
 // (512-thread variant: two workgroups per CU need 4 waves per SIMD, i.e. at most 128 VGPRs; the 256-thread variant at
 // 128 VGPRs -- three dwords spilled -- fits FOUR workgroups per CU instead of three: config 3's 7500 tiles 36.9 -> 29.4 us.
 // Pushing either further -- 6 or 8 waves per SIMD -- spills the keys and costs 5-12 us: measured)
-#ifndef EG_SORT_WAVES
-#define EG_SORT_WAVES 4
-#endif
-#ifndef EG_SORT_WAVES_256
-#define EG_SORT_WAVES_256 4
-#endif
-__global__ void __launch_bounds__(THREADS, THREADS == 512 ? EG_SORT_WAVES : (THREADS == 256 ? EG_SORT_WAVES_256 : 1))
+__global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 1 : 4)
 tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ offsets, int T,
                  long long capacity, int small_cap, int *__restrict__ flatten_ids,
                  long long *__restrict__ isect_ids, const SegTable seg_, const Batch bt) {
@@ -657,59 +635,18 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
         kept = min(seg.cursor[tile], seg.seg_cap);  // every thread reads it; reset after the barrier
         first = seg.item_first[tile];
         items = min(max(1, (kept + 127) >> 7), max(0, seg.max_items - first));
-        // Round 6: XCD-aware record placement above 2048 tiles, WITHOUT another scan.  The tiles are dealt to the XCDs in
-        // BANDS of 2^xcd_shift tile rows, xcd = (ty >> shift) & 7: a band is a contiguous run of tile indices, a list is
-        // every eighth band, and the projection's scan already left the two exclusive prefixes over ALL tiles -- F (front-class
-        // items: item_front) and A (items: item_first).  Tile t's place in its list follows from their values at t and at the
-        // boundaries of the list's bands -- a dozen loads that travel with the tile's own, summed by the first wave:
-        //   k0   = sum over the list's bands in front of (F(end) - F(start)) + F(t) - F(start of t's band)
-        //   l0k1 = the list's front total + the same sums of G = A - F (deep-class items)
-        // (2 x 2 blocks dealt round-robin, as on the small grids, need a prefix per list: sixteen more sums in the projection
-        // kernel's serial tail measured +1.7 / +4.3 us per step at 800 x 800 / 1600 x 1200 -- profiles/r06_xcd_large_ab.txt.)
-        int k0 = 0, l0k1 = 0, myx = -1;
-        if (seg.xcd_shift > 0 && seg.item_front && seg.item_rec && seg.total_flag) {
-          const int ftot = seg.item_front[T];
-          if (ftot >= 0) {  // (< 0: the view overflowed the item capacity -- item order, see below)
-            const int band_tiles = seg.tw << seg.xcd_shift, nb = (T + band_tiles - 1) / band_tiles;
-            const int b = (int)(((float)tile + 0.5f) * seg.inv_tw) >> seg.xcd_shift;
-            myx = b & 7;
-            if (tid < 64) {
-              int fb = 0, gb = 0, ft = 0;
-              for (int bj = myx + 8 * tid; bj < nb; bj += 8 * 64) {
-                const int s0 = bj * band_tiles, e0 = min(T, s0 + band_tiles);
-                const int Fs = seg.item_front[s0], Fe = seg.item_front[e0];
-                const int As = seg.item_first[s0], Ae = e0 < T ? seg.item_first[e0] : seg.total_flag[2];
-                const int df = Fe - Fs, dg = (Ae - As) - df;
-                ft += df;
-                if (bj < b) { fb += df; gb += dg; }
-              }
-              fb = wave_scan_dpp(fb, 0, OpAdd()); gb = wave_scan_dpp(gb, 0, OpAdd()); ft = wave_scan_dpp(ft, 0, OpAdd());
-              if (tid == 63) {
-                const int s0 = b * band_tiles;
-                const int Ft = seg.item_front[tile], Fs = seg.item_front[s0], As = seg.item_first[s0];
-                s_pre[0][0] = fb + (Ft - Fs);
-                s_pre[1][0] = ft + gb + ((first - Ft) - (As - Fs));
-              }
-            }
-          }
-        }
         __syncthreads();
-        if (myx >= 0) { k0 = s_pre[0][0]; l0k1 = s_pre[1][0]; }
         if (tid == 0) {
           seg.cursor[tile] = 0;  // ready for the next step
           seg.tile_start[tile] = tile * seg.seg_cap;
           seg.tile_end[tile] = tile * seg.seg_cap + kept;
           seg.item_end[tile] = first + items;
         }
-        bool rec_over = false;
         for (int i = tid; i < items; i += THREADS) {
           seg.item_tile[first + i] = tile;
           if (seg.item_rec) {
             int disp = first + i;
-            if (myx >= 0) {
-              disp = 8 * (i < EG_FRONT_LARGE ? k0 + i : l0k1 + (i - EG_FRONT_LARGE)) + myx;
-              if (disp >= seg.max_items) rec_over = true;  // (the longest list does not fit the table: grow + replay)
-            } else if (seg.item_front) {
+            if (seg.item_front) {
               // (ftot < 0: the view overflowed the item capacity and the projection's scan said so -- item order, which
               // has no holes when tiles are truncated; the caller grows the buffers and replays)
               const int fpre = seg.item_front[tile], ftot = seg.item_front[T];
@@ -719,7 +656,6 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
               seg.item_rec[disp] = make_int4(tile, i | (items << 16), (int)seg.rec_tag, tile * seg.seg_cap + kept);
           }
         }
-        if (rec_over) seg.total_flag[1] = 1;  // sticky: only the host clears it
       }
       start = (long long)tile * seg.seg_cap;
       end = start + kept;
@@ -814,52 +750,17 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
         }
       __syncthreads();
       EG_SP_TICK(4);  // 4: scatter
-      if (kSortRankG == 1) {
-        for (int i = tid; i < n; i += THREADS) {
-          const unsigned long long k = kout[i];
-          const unsigned d = (unsigned)(k >> 32);
-          const int bk = min(NB - 1, (int)((float)(d - dmin) * scale));
-          const int b0 = hist[bk], b1 = b0 + cursor[bk];
-          int rank = 0;
-          for (int q = b0; q < b1; ++q) rank += (kout[q] < k) ? 1 : 0;
-          const long long o = start + b0 + rank;
-          const int gid = (int)(unsigned)(k & 0xffffffffull);
-          flatten_ids[o] = gid;
-          if (isect_ids) isect_ids[o] = ((long long)tile << 32) | (long long)(k >> 32);
-        }
-      } else {
-        // kSortRankG keys of a thread step through their buckets side by side: one round trip to LDS per step of all of
-        // them instead of one per key and step (the fullest tile's threads rank CAP / THREADS keys each)
-        constexpr int G = kSortRankG;
-        for (int i0 = tid; i0 < n; i0 += G * THREADS) {
-          unsigned long long k[G];
-          int b0[G], f[G], rank[G], fmax = 0;
-#pragma unroll
-          for (int g = 0; g < G; ++g) {
-            const int i = min(i0 + g * THREADS, n - 1);
-            k[g] = kout[i];
-            const unsigned d = (unsigned)(k[g] >> 32);
-            const int bk = min(NB - 1, (int)((float)(d - dmin) * scale));
-            b0[g] = hist[bk];
-            f[g] = (i0 + g * THREADS < n) ? cursor[bk] : 0;
-            rank[g] = 0;
-            fmax = max(fmax, f[g]);
-          }
-          for (int q = 0; q < fmax; ++q) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-              const unsigned long long o_ = kout[min(b0[g] + q, n - 1)];
-              rank[g] += (q < f[g] && o_ < k[g]) ? 1 : 0;
-            }
-          }
-#pragma unroll
-          for (int g = 0; g < G; ++g)
-            if (i0 + g * THREADS < n) {
-              const long long o = start + b0[g] + rank[g];
-              flatten_ids[o] = (int)(unsigned)(k[g] & 0xffffffffull);
-              if (isect_ids) isect_ids[o] = ((long long)tile << 32) | (long long)(k[g] >> 32);
-            }
-        }
+      for (int i = tid; i < n; i += THREADS) {
+        const unsigned long long k = kout[i];
+        const unsigned d = (unsigned)(k >> 32);
+        const int bk = min(NB - 1, (int)((float)(d - dmin) * scale));
+        const int b0 = hist[bk], b1 = b0 + cursor[bk];
+        int rank = 0;
+        for (int q = b0; q < b1; ++q) rank += (kout[q] < k) ? 1 : 0;
+        const long long o = start + b0 + rank;
+        const int gid = (int)(unsigned)(k & 0xffffffffull);
+        flatten_ids[o] = gid;
+        if (isect_ids) isect_ids[o] = ((long long)tile << 32) | (long long)(k >> 32);
       }
 #ifdef EG_SORT_PROF
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1019,11 +920,7 @@ static int launch_tile_sort(uint64_t *keys, const int32_t *offsets, int32_t T, i
   // want 512 threads (config 2: 16.0 -> 13.1 us; 500 k @1200x680: 45 -> 41) -- unless the grid has thousands of
   // small tiles (200 k @1600x1200: 33 -> 44 with 512), where the extra waves cost more than the fullest tile gains
   // (a batch of C views multiplies the grid: config 2 with 4 views per launch sequence 221 -> 278 us with 512)
-  bool wide = max_tile_hint > 1536 && (C == 1 ? T <= 4096 : T * C <= 2048);
-#ifdef EG_DEV_SWITCHES
-  static const int wide_env = getenv("EG_SORT_WIDE") ? atoi(getenv("EG_SORT_WIDE")) : -1;  // (A/B switch)
-  if (wide_env >= 0) wide = wide_env != 0;
-#endif
+  const bool wide = max_tile_hint > 1536 && (C == 1 ? T <= 4096 : T * C <= 2048);
   if (!g_sort_attr_set) {
     (void)hipFuncSetAttribute((const void *)tile_sort_kernel<1024, kLarge, true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLargeLds);
@@ -1034,18 +931,10 @@ static int launch_tile_sort(uint64_t *keys, const int32_t *offsets, int32_t T, i
   // LDS that would all find nothing to do: ~3 us) is skipped and the small variant owns EVERY tile -- a
   // tile that outgrew the hint is then still sorted correctly, by the slower paths of the small variant.
   const bool small_only = max_tile_hint > 0 && (int64_t)max_tile_hint * 5 / 4 <= kSmall;
-  // workgroups of the small variant: one per tile -- or (grid_div > 1) one per grid_div tiles, which the kernel's
-  // grid-stride loop pairs middle-out rank b with rank b + T / grid_div: a central tile and a border tile.  Round 6 measured
-  // 2 ("one workgroup retires a run of empty tiles"): 7.7 -> 10.1 us at config 1, 11.8 -> 12.4 at config 2
-  // (profiles/r06_misc_ab.txt) -- the second tile's round trip to memory starts after the first tile's sort; stays 1
-  int grid_div = kSortGridDiv;
-#ifdef EG_DEV_SWITCHES
-  static const int div_env = getenv("EG_SORT_GRID_DIV") ? atoi(getenv("EG_SORT_GRID_DIV")) : 0;  // (A/B switch)
-  if (div_env > 0) grid_div = div_env;
-#endif
-  const int grid_x = cdiv(T, grid_div);
+  // workgroups of the small variant: one per tile (two tiles per workgroup measured 7.7 -> 10.1 us at config 1, 11.8 -> 12.4
+  // at config 2, profiles/r06_misc_ab.txt: the second tile's round trip to memory starts after the first tile's sort)
 #define EG_SORT_SMALL(TH_, P3_)                                                                                          \
-  tile_sort_kernel<TH_, kSmall, false, P3_><<<dim3(grid_x, C), TH_, kSmall * 8 + 2 * TH_ * 4 * kSortBM, as_stream(stream)>>>( \
+  tile_sort_kernel<TH_, kSmall, false, P3_><<<dim3(T, C), TH_, kSmall * 8 + 2 * TH_ * 4 * kSortBM, as_stream(stream)>>>( \
       (unsigned long long *)keys, offsets, T, (long long)capacity, small_only ? 0x7fffffff : kSmall, flatten_ids,            \
       (long long *)isect_ids, seg, bt)
   const bool prefix3 = seg.total != nullptr && T > 2 * kPrefixBatchTiles;
@@ -1104,23 +993,10 @@ extern "C" int eg_sort_segments(uint64_t *keys, int32_t *tile_cursor, int32_t T,
 namespace eg {
 int record_xcd_shift(int T, bool prefix_here, bool has_item_rec, int C) {
   // (small grids stay dense: eight lists over a few dozen tiles are not balanced, and nothing there misses an L2)
-  // Round 6 built the placement for grids ABOVE 2048 tiles as well (bands of tile rows: tile_sort_kernel) and measured it
-  // (profiles/r06_xcd_large_ab.txt): the forward's fabric traffic falls from 3.4x / 3.1x to 1.6x / 1.4x of the algorithmic
-  // bytes at 1600 x 1200 / 1200 x 680 -- and the forward takes 138 / 126 us instead of 133 / 116 (eight lists of unequal work;
-  // with 2 x 2 blocks and a per-list scan in the projection's tail 134 / 117 and +4 us in that tail): the launch is not
-  // traffic-bound.  OFF there; EG_XCD_LARGE=1 in a development build turns it on.
-  int shift = (has_item_rec && C == 1 && T >= kXcdMinTiles) ? kXcdShiftDefault : 0;
-  int xcd_large = 0;
-#ifdef EG_DEV_SWITCHES
-  static const int xcd_large_env = getenv("EG_XCD_LARGE") ? atoi(getenv("EG_XCD_LARGE")) : 0;  // (A/B switch)
-  xcd_large = xcd_large_env;
-#endif
-  if (!prefix_here && !xcd_large) shift = 0;
-#ifdef EG_DEV_SWITCHES
-  static const int xcd_env = getenv("EG_XCD_SHIFT") ? atoi(getenv("EG_XCD_SHIFT")) : -1;  // (A/B switch)
-  if (xcd_env >= 0 && shift > 0) shift = xcd_env;
-#endif
-  return shift;
+  // Without "prefix here" (above kPrefixHereMaxTiles tiles) it stays off: measured there (profiles/r06_xcd_large_ab.txt),
+  // the forward's fabric traffic fell from 3.4x / 3.1x to 1.6x / 1.4x of the algorithmic bytes at 1600 x 1200 / 1200 x 680
+  // -- and the forward took 138 / 126 us instead of 133 / 116 (eight lists of unequal work): it is not traffic-bound.
+  return (prefix_here && has_item_rec && C == 1 && T >= kXcdMinTiles) ? kXcdShiftDefault : 0;
 }
 
 int launch_sort_segments(uint64_t *keys, int32_t *tile_cursor, int32_t T, int32_t seg_cap, int32_t *flatten_ids,
@@ -1128,9 +1004,8 @@ int launch_sort_segments(uint64_t *keys, int32_t *tile_cursor, int32_t T, int32_
                          int32_t *item_tile, int32_t max_items, int32_t max_tile_hint, const Batch &bt, int C,
                          hipStream_t st, int32_t *total_prefix_here, int32_t *item_rec, const int32_t *item_front,
                          uint32_t rec_tag, int32_t tiles_per_row, const float *gt, const float *wmap, void *workspace,
-                         int32_t width, int32_t height, int32_t front_slices, int32_t *total_flag) {
+                         int32_t width, int32_t height, int32_t front_slices) {
   SegTable seg;
-  seg.total_flag = total_flag;
   seg.cursor = tile_cursor; seg.seg_cap = seg_cap;
   seg.tile_start = tile_start; seg.tile_end = tile_end;
   seg.item_first = item_first; seg.item_end = item_end;
@@ -1156,25 +1031,8 @@ int launch_sort_segments(uint64_t *keys, int32_t *tile_cursor, int32_t T, int32_
     seg.skip_empty = 1;
     seg.gt = gt; seg.wmap = wmap; seg.width = width; seg.height = height;
     seg.loss_part = carve_workspace(workspace, max_items, T).loss_part;
-#ifdef EG_DEV_SWITCHES
-    static const int skip_env = getenv("EG_SKIP_EMPTY") ? atoi(getenv("EG_SKIP_EMPTY")) : 1;  // (A/B switch)
-    seg.skip_empty = skip_env;
-#endif
   }
   seg.xcd_shift = tiles_per_row > 0 ? record_xcd_shift(T, total_prefix_here != nullptr, item_rec != nullptr, C) : 0;
-  if (!total_prefix_here) {
-    // above 2048 tiles the placement works from the projection scan's two prefixes (item_first, item_front: EG_FLAG_FRONT_PREFIX)
-    if (!(seg.xcd_shift > 0 && item_front && total_flag)) seg.xcd_shift = 0;
-  }
-#ifdef EG_DEV_SWITCHES  // A/B switches of development builds (edgegaussians_amd/build.py, EG_DEV_SWITCHES=1)
-  static const int front = getenv("EG_FRONT_SLICES") ? atoi(getenv("EG_FRONT_SLICES")) : -2;  // (-2: not set)
-  static const int middle_out = getenv("EG_SORT_MIDDLE_OUT") ? atoi(getenv("EG_SORT_MIDDLE_OUT")) : 1;
-  if (front != -2) seg.slice_major = front < 0 ? 0 : (front > 15 ? 15 : front);
-  seg.middle_out = middle_out;
-  static const int front_large = getenv("EG_FRONT_LARGE") ? atoi(getenv("EG_FRONT_LARGE")) : 1;
-  if (!front_large) seg.item_front = nullptr;
-#endif
-
   return launch_tile_sort(keys, nullptr, T, (int64_t)T * seg_cap, flatten_ids, nullptr, max_tile_hint, seg,
                           (eg_stream_t)st, bt, C);
 }

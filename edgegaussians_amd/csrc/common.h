@@ -67,7 +67,7 @@ int launch_sort_segments(uint64_t *keys, int32_t *tile_cursor, int32_t T, int32_
                          hipStream_t st, int32_t *total_prefix_here = nullptr, int32_t *item_rec = nullptr,
                          const int32_t *item_front = nullptr, uint32_t rec_tag = 0, int32_t tiles_per_row = 0,
                          const float *gt = nullptr, const float *wmap = nullptr, void *workspace = nullptr, int32_t width = 0,
-                         int32_t height = 0, int32_t front_slices = 0, int32_t *total_flag = nullptr);
+                         int32_t height = 0, int32_t front_slices = 0);
 bool wave_forward_selected(int channels, const void *render, const void *alphas, const void *last_ids, const void *vpix,
                            const void *gtstop, const void *wmap, const void *item_rec, int chain_tag);
 int launch_composite_fwd_segments(const float *splat, const int32_t *tile_start, const int32_t *tile_end,
@@ -103,10 +103,7 @@ int launch_project_bwd_emit(float *means, float *quats, float *scales, float *op
                             float *m, float *v, const eg_adam_hyper &hyper, int32_t *tile_cursor, int32_t seg_cap,
                             uint64_t *keys, int32_t *item_first, int32_t max_items, int32_t *total, int32_t *ticket,
                             hipStream_t st);
-#ifndef EG_FUSED_BWD_MAX_GAUSSIANS
-#define EG_FUSED_BWD_MAX_GAUSSIANS 32768
-#endif
-constexpr int kFusedBwdMaxGaussians = EG_FUSED_BWD_MAX_GAUSSIANS;  // (see step.hip fused_backward_pays)
+constexpr int kFusedBwdMaxGaussians = 32768;  // (see step.hip fused_backward_pays)
 // round 6 (backward_fused.hip): footprint backward + projection backward + Adam + the next view's projection and binning
 // in ONE kernel, tile grids of <= kPrefixHereMaxTiles tiles; g2d optional (the record stays in LDS)
 int launch_gaussian_bwd_fused(float *means, float *quats, float *scales, float *opacities, const float *viewmat,

@@ -517,7 +517,8 @@ struct WaveArgs {
   int width, height, tw, n_tiles;
   unsigned tag;
   float loss_scale;
-  int max_anchored;  // tiles of more slices look back over all aggregates (kMaxAnchoredSlices; 0 in an A/B build leg)
+  int max_anchored;  // kMaxAnchoredSlices: tiles of more slices look back over all aggregates (an argument: the constant
+                     // folded in changes this kernel's code, a separate experiment)
   const int *item_first;  // [T]: the tile's first item in the contiguous per-tile numbering (hand-over storage)
   int seg_cap;            // keys per tile segment: slice s of tile t starts at key t * seg_cap + 128 s
 };
@@ -821,11 +822,6 @@ int launch_wave_fwd(const float4 *splat, const TileTable tt, const int32_t *flat
     (void)hipMalloc((void **)&g_prof, (size_t)max_items * 32 * sizeof(unsigned long long));
   }
   if (timed) (void)hipMemsetAsync(g_prof, 0, (size_t)max_items * 32 * sizeof(unsigned long long), s);
-  int max_anchored = kMaxAnchoredSlices;
-#ifdef EG_DEV_SWITCHES
-  static const int anchor_env = getenv("EG_WAVE_ANCHOR") ? atoi(getenv("EG_WAVE_ANCHOR")) : 1;
-  if (!anchor_env) max_anchored = 0;
-#endif
   (void)max_tile_hint;
   WaveArgs a;
   a.splat = splat; a.item_rec = tt.item_rec; a.total = total; a.flat = flatten_ids; a.cursor_reset = tt.cursor_reset;
@@ -833,7 +829,7 @@ int launch_wave_fwd(const float4 *splat, const TileTable tt, const int32_t *flat
   a.loss_part = ws.loss_part;
   a.gt = gt; a.wmap = wmap; a.alphas = alphas; a.gtstop = (StopRec *)gtstop; a.prof = g_prof;
   a.width = width; a.height = height; a.tw = tw; a.n_tiles = tw * th;
-  a.tag = tag; a.loss_scale = loss_scale; a.max_anchored = max_anchored; a.item_first = tt.item_first;
+  a.tag = tag; a.loss_scale = loss_scale; a.max_anchored = kMaxAnchoredSlices; a.item_first = tt.item_first;
   a.seg_cap = tt.seg_cap;
   if (tt.seg_cap <= 0) {
     set_error("composite_fwd(wave): the item records need the segment capacity");

@@ -94,7 +94,7 @@ def _tensors(x):
 
 class StepJournal:
     """`tr` is the owning trainer: the journal calls its `_snapshot`, `_restore`, `flush`, `_zero_workspaces`, `_ctl_bits`
-    and reads `chained_forward`, `epoch`, `loss_scale`."""
+    and reads `epoch`, `loss_scale`."""
 
     def __init__(self, tr):
         self.tr, self.entries = tr, []  # type: List[Entry]
@@ -119,7 +119,7 @@ class StepJournal:
         tr = self.tr
         if self.entries and self._tags + n > WINDOW_TAGS:
             tr.flush()
-        if tr.chained_forward and self.tag + n > MAX_WS_TAG:
+        if self.tag + n > MAX_WS_TAG:
             if self.entries:
                 tr.flush()
             elif tr._ctl_bits()[1]:  # nothing to replay, but the stall bit of control word 3 must not be zeroed unread
@@ -154,7 +154,7 @@ class StepJournal:
         put the current ones back.  The window's tags are reserved first: the range cannot wrap inside the replay."""
         tr = self.tr
         assert self._tags <= MAX_WS_TAG, "journal longer than the tag range"
-        if tr.chained_forward and self.tag + self._tags > MAX_WS_TAG:
+        if self.tag + self._tags > MAX_WS_TAG:
             tr._zero_workspaces()
             self.tag = 0
         now = tr.epoch, tr.loss_scale

@@ -23,7 +23,6 @@ Differences from the reference that are deliberate (documented in DESIGN.md):
 from __future__ import annotations
 
 import contextlib
-import os
 
 import ctypes as C
 import math
@@ -78,11 +77,15 @@ class LRSchedule:
 class EdgeTrainer:
     """Device-resident training state + fused step.  One instance per GPU (one process per GPU)."""
 
+    # every step's forward takes a call tag and may run chained (exact transmittance stop inside the kernel); a constant,
+    # kept because callers and tests read it
+    chained_forward = True
+
     def __init__(self, means: Tensor, log_scales: Tensor, quats: Tensor, logit_opacities: Tensor,
                  viewmats: Tensor, Ks: Tensor, gt: Tensor, width: int, height: int,
                  device: str = "cuda", schedule: Optional[LRSchedule] = None,
                  betas=(0.9, 0.999), eps: float = 1e-8, keep_images: bool = False,
-                 spatial_order: bool = False, segmented: Optional[bool] = None, replay_on_overflow: bool = True,
+                 spatial_order: bool = False, segmented: bool = True, replay_on_overflow: bool = True,
                  seed: int = 0):
         _lib.load()
         # replay_on_overflow: the steps enqueued since the last read-back (pop_loss) are journalled and the
@@ -101,11 +104,10 @@ class EdgeTrainer:
         self.rewalk_hint = -1  # re-walk list length seen at the last read-back (launch-shape hint; -1 = unknown)
         self._projected: Optional[int] = None  # view already projected + binned by apply_adam(next_view=...)
         self._dp = None  # the DataParallelStep driving this trainer (dist.py), if any: read-backs and replays are collective
-        self.chained_forward = bool(int(os.environ.get("EG_CHAINED", "1")))
         # round 6 (eg_step_args.two_kernel_backward): inside a native run of steps on a tile grid of <= 2048 tiles the backward of
-        # a scene of <= 32768 Gaussians is ONE kernel (csrc/backward_fused.hip); != 0 (development: EG_TWO_KERNEL_BACKWARD=1)
-        # keeps the two kernels of rounds 1-5 -- the same parameters bit for bit (tests/test_gpu_parity.py)
-        self.two_kernel_backward = int(os.environ.get("EG_TWO_KERNEL_BACKWARD", "0"))  # eg_step_args.two_kernel_backward
+        # a scene of <= 32768 Gaussians is ONE kernel (csrc/backward_fused.hip); != 0 (set by tests) keeps the two kernels of
+        # rounds 1-5 -- the same parameters bit for bit (tests/test_gpu_parity.py)
+        self.two_kernel_backward = 0
         # noise of duplicate() comes from a dedicated generator seeded with (seed, event number): identical
         # on every data-parallel rank whatever else the ranks drew (edge_gs.py:462-467 uses the global RNG)
         self.seed = int(seed)
@@ -113,10 +115,10 @@ class EdgeTrainer:
         # keep_images: also materialise render / alphas / last_ids / vpix every step (the training step
         # itself needs none of them: its backward reads only the packed gtstop record)
         self.keep_images = bool(keep_images)
-        # segmented (default; EG_SEGMENTED=0 or segmented=False selects the count / scan / emit sequence of
-        # the operator path): the training step bins with fixed per-tile key segments -- projection +
-        # binning in one kernel, no emit pass; same results, the isect buffers become [T * seg_cap]
-        self.segmented = bool(int(os.environ.get("EG_SEGMENTED", "1"))) if segmented is None else bool(segmented)
+        # segmented (default; segmented=False selects the count / scan / emit sequence of the operator path): the
+        # training step bins with fixed per-tile key segments -- projection + binning in one kernel, no emit pass; same
+        # results, the isect buffers become [T * seg_cap]
+        self.segmented = bool(segmented)
         self.seg_cap = 0
         self.dev = torch.device(device)
         f = dict(device=self.dev, dtype=torch.float32)
@@ -391,7 +393,7 @@ class EdgeTrainer:
         a.wmap = wmap.data_ptr()
         a.loss_scale = self.loss_scale
         a.rewalk_hint = self._rewalk_arg(fused_adam)
-        a.ws_tag = self._journal.take(n_tags) if self.chained_forward else 0
+        a.ws_tag = self._journal.take(n_tags)
         a.two_kernel_backward = 1 if (self.two_kernel_backward or getattr(self, "_side_by_side", False)) else 0
         if fused_adam:
             a.absgrads = ptr(self.absgrads)
@@ -601,7 +603,7 @@ class EdgeTrainer:
             wp[i] = w.data_ptr()
         a.loss_scale = self.loss_scale
         a.max_tile_hint = getattr(self, "max_tile_seen", 0)
-        a.ws_tag = self._journal.take(1) if self.chained_forward else 0
+        a.ws_tag = self._journal.take(1)
         journalled = fused_adam if journalled is None else journalled
         a.rewalk_hint = (_lib.REWALK_SPECULATE if (journalled and self.replay_on_overflow and b["rewalk_hint"] == 0
                                                    and self.rewalk_hint in (0, -1)) else b["rewalk_hint"])

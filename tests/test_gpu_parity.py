@@ -2399,9 +2399,8 @@ def test_item_records_follow_the_dispatch_order_contract(env, size):
     of its tiles first (slices [0, 9) when the forward runs in chained mode), tile by tile, then the deeper slices; no other
     index below max_items carries the call's tag.
     Larger grids: slices [0, 9) of every tile first (the projection's scan supplies the prefix: EG_FLAG_FRONT_PREFIX), then the
-    deeper slices, indices [0, n_items) without holes.  (Round 6 built the XCD-aware placement for them as well -- bands of two
-    tile rows, xcd = (ty >> 1) % 8 -- and measured the forward slower with it: off, profiles/r06_xcd_large_ab.txt; the branch
-    above checks it when a development build turns it on.)"""
+    deeper slices, indices [0, n_items) without holes.  (Round 6 built the XCD-aware placement for them as well and measured
+    the forward slower with it: removed, profiles/r06_xcd_large_ab.txt.)"""
     import numpy as np
     _lib, synth, O = env
     from edgegaussians_amd import EdgeTrainer
@@ -2461,14 +2460,12 @@ def test_item_records_follow_the_dispatch_order_contract(env, size):
     order = np.lexsort((np.arange(len(rec)), pairs))
     same_tile = tile[order][1:] == tile[order][:-1]
     assert (np.diff(where[order])[same_tile] > 0).all(), "a slice was dispatched before a slice in front of it"
-    if any(k in os.environ for k in ("EG_FRONT_SLICES", "EG_FRONT_LARGE", "EG_XCD_SHIFT")):
-        return
     # (the class boundary: 9 when the step's forward runs in chained mode -- a grad_step without a journal does --, 4 otherwise)
     front_small = 9 if tr._rewalk_arg(False) != -2 else 4
     if xcd_shift > 0:
-        front = front_small if size == "small_grid" else 9  # kFrontChained / kFrontDefault; EG_FRONT_LARGE above 2048 tiles
+        front = front_small  # kFrontChained / kFrontDefault
         ty, tx = np.divmod(tile, tw)
-        xcd = ((tx >> 1) + 3 * (ty >> 1)) % 8 if size == "small_grid" else (ty >> 1) % 8
+        xcd = ((tx >> 1) + 3 * (ty >> 1)) % 8
         assert np.array_equal(where % 8, xcd), "a record sits in another XCD's list"
         assert len(np.unique(xcd)) == 8
         span = 0
@@ -2483,11 +2480,6 @@ def test_item_records_follow_the_dispatch_order_contract(env, size):
             assert n_a < m.sum() and (slx[:n_a] < front).all() and (slx[n_a:] >= front).all()
             assert (np.diff(tix[:n_a]) >= 0).all() and (np.diff(tix[n_a:]) >= 0).all()
         assert span <= tr.max_items and where.max() < span
-        if size == "large_grid":
-            # the prefix the projection's scan left behind (ticket[1 .. T + 1]): front-class items in front of every tile
-            fp = tr.ticket.cpu().numpy()
-            fr = np.minimum(per_tile, front)
-            assert fp[0] == 0 and np.array_equal(fp[1:T + 1], np.concatenate([[0], np.cumsum(fr)[:-1]])) and fp[T + 1] == fr.sum()
     else:
         assert np.array_equal(where, np.arange(len(rec)))  # no holes
         front = 9 if size == "large_grid" else front_small  # EG_FRONT_LARGE / the step's class boundary

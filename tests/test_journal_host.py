@@ -14,7 +14,7 @@ class HostTrainer(EdgeTrainer):
 
     def __init__(self, replay_on_overflow=True):
         self._journal = StepJournal(self)
-        self.replay_on_overflow, self.chained_forward = replay_on_overflow, True
+        self.replay_on_overflow = replay_on_overflow
         self.capacity, self.epoch, self.loss_scale = 1, 0, 1.0
         self._loss_buf = torch.zeros(65)
         self.loss_acc, self._n_marks = self._loss_buf[:1], 0
