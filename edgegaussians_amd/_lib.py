@@ -84,7 +84,6 @@ _SIGS = {
     "eg_composite_fwd_segments": [_vp] * 7 + [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp],
     "eg_composite_fwd": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp,
                          _vp, _vp, _i64, _vp, _vp, _i32, _vp],
-    "eg_composite_bwd": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "eg_composite_bwd_colors": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "eg_project_bwd": [_vp] * 6 + [_i32, _i32, _i32, _f, _u32] + [_vp] * 9 + [_vp],
     "eg_absgrad_accum": [_vp, _i32, _vp, _vp],

@@ -93,7 +93,8 @@ extern "C" int eg_tile_emit_sort_cams(const float *means2d, const int32_t *radii
 
 // compositing forward of every camera: splat [C, N, 8]; colors NULL (all ones), [N, D] (colors_per_camera = 0) or [C, N, D];
 // images [C, H, W, ...]; offsets / flatten_ids / item_offsets / total / workspace: HOST arrays of C device pointers (the
-// last three NULL or per-entry NULL = the one-workgroup-per-tile kernel); gtstop [C, H, W, 3] or NULL
+// last three NULL or per-entry NULL = the one-workgroup-per-tile kernel); gtstop [C, H, W, 3] or NULL (it needs the
+// slice-parallel forward: unit colours and every camera's item tables)
 extern "C" int eg_composite_fwd_cams(int32_t C, const float *splat, int32_t N, const float *colors, int32_t colors_per_camera,
                                      int32_t channels, const int32_t *const *offsets, const int32_t *const *flatten_ids,
                                      int32_t width, int32_t height, float *render, float *alphas, int32_t *last_ids,
@@ -111,7 +112,7 @@ extern "C" int eg_composite_fwd_cams(int32_t C, const float *splat, int32_t N, c
                                     render + hw * (size_t)channels * c, alphas + hw * c, last_ids + hw * c, nullptr, nullptr,
                                     1.0f, nullptr, nullptr, sliced ? item_offsets[c] : nullptr, sliced ? total[c] : nullptr,
                                     sliced ? max_items_host[c] : 0, sliced ? workspace[c] : nullptr,
-                                    (gtstop && sliced) ? gtstop + 3 * hw * c : nullptr, -1, stream);
+                                    gtstop ? gtstop + 3 * hw * c : nullptr, -1, stream);
     if (rc) return rc;
   }
   return EG_OK;

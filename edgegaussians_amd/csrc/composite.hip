@@ -7,8 +7,8 @@
 //
 // Work decomposition: the reference's scenes put nearly all Gaussians into the ~13x13 central tiles
 // (the object spans ~200 px), so "one workgroup per tile" leaves >80 % of the 256 CUs idle while a
-// few workgroups walk thousands of Gaussians serially (measured: 1.2 ms).  Both passes therefore
-// run one 256-thread workgroup per ITEM = (tile, slice of <= 128 depth-sorted Gaussians); the item
+// few workgroups walk thousands of Gaussians serially (measured: 1.2 ms).  The unit-colour forward
+// therefore runs one 256-thread workgroup per ITEM = (tile, slice of <= 128 depth-sorted Gaussians); the item
 // table is the second scan produced by eg_tile_offsets (an empty tile owns one empty item, which
 // finalises its pixels).
 //
@@ -23,21 +23,17 @@
 //   re-walk: the transmittance stop (T <= 1e-4) is only DETECTED on the slice products; the slice in which
 //            it falls is put on a compact list and resolved exactly by this kernel
 // (front-to-back compositing is associative: (C1,T1) o (C2,T2) = (C1 + T1 C2, T1 T2); with unit
-// colours C = 1 - T, so only T travels).  General colours use the classic one-workgroup-per-tile
-// kernel below.
+// colours C = 1 - T, so only T travels).  The training step takes the wave-autonomous forward of
+// composite_wave.hip, or -- when it keeps its images and pixels do stop -- the chained kernel below: slice, combine
+// and exact stop in one launch.  General colours, and unit colours without item tables, use the classic
+// one-workgroup-per-tile kernel below.
 //
-// Backward (unit colours -- the reference passes colours == 1, edge_gs.py:247): with c == 1 and no
-// background, pix = 1 - T_final, hence dpix/dalpha_i = T_final / (1 - alpha_i) for EVERY contributing
-// Gaussian: the pass is order-independent.  That allows the wave64-native transposition
-//     lane = Gaussian, loop = pixels of the tile
-// in which each lane accumulates its own Gaussian's 8 partial derivatives in registers: no
-// cross-lane reduction at all (a 32-lane-warp design spends 5 shuffles x 9 values per Gaussian per
-// warp here) and one set of atomics per (Gaussian, tile, pixel-split) instead of one per warp.
-// Pixels with zero upstream gradient are compacted away first (the reference's `bg_edge_ratio`
-// strategy leaves ~1.5 % of the pixels active).
+// Backward, unit colours without colour gradients (the reference passes colours == 1, edge_gs.py:247): with c == 1
+// and no background, pix = 1 - T_final, hence dpix/dalpha_i = T_final / (1 - alpha_i) for EVERY contributing
+// Gaussian: the pass is order-independent, and the footprint kernel below sums each Gaussian over its own pixels.
 //
-// General colours keep the classic order-dependent pixel-per-lane backward with wave64 butterfly
-// reductions (eg_composite_bwd_colors); it is off the reference's path and not tuned.
+// General colours, and callers that want colour gradients, take the classic order-dependent pixel-per-lane backward
+// with wave64 butterfly reductions (eg_composite_bwd_colors); it is off the reference's path and not tuned.
 #include <cstdlib>
 
 #include "common.h"
@@ -139,130 +135,10 @@ composite_fwd_kernel(const float4 *__restrict__ splat, const float *__restrict__
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// backward, unit colours: lane = Gaussian, loop over the tile's active pixels
-__global__ void __launch_bounds__(256)
-composite_bwd_unit_kernel(const float4 *__restrict__ splat, const int *__restrict__ offsets,
-                          const int *__restrict__ flat, int width, int height, int tw, int th,
-                          const float *__restrict__ alphas, const int *__restrict__ last_ids,
-                          const float *__restrict__ vpix, float *__restrict__ g2d) {
-  __shared__ float4 sP[kTilePix];  // px, py, v*T_final, last id (int bits) -- compacted
-  __shared__ int sCnt[4];
-  __shared__ int sMaxLast[4];
-
-  const int tile = xcd_tile(blockIdx.x, tw * th);
-  const int start = offsets[tile], end = offsets[tile + 1];
-  const int n = end - start;
-  if (n <= 0) return;
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int ty = tile / tw, tx = tile - ty * tw;
-  const int i = ty * kTile + (tid >> 4), j = tx * kTile + (tid & 15);
-  const bool inside = (i < height) && (j < width);
-  float gT = 0.f;
-  int last = -1;
-  if (inside) {
-    const int p = i * width + j;
-    const float a = alphas[p];
-    const float v = vpix[p];
-    if (a > 0.f && v != 0.f) {  // a > 0 <=> at least one Gaussian contributed to this pixel
-      gT = v * (1.f - a);
-      last = last_ids[p];
-    }
-  }
-  const bool active = (last >= 0) && (gT != 0.f);
-  const unsigned long long bal = __ballot(active);
-  const int wave_cnt = __popcll(bal);
-  const int rank = __popcll(bal & ((1ull << lane) - 1ull));
-  int wmax = last;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d, 64));
-  if (lane == 0) { sCnt[wv] = wave_cnt; sMaxLast[wv] = wmax; }
-  __syncthreads();
-  int pre = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) pre += (w < wv) ? sCnt[w] : 0;
-  const int n_act = sCnt[0] + sCnt[1] + sCnt[2] + sCnt[3];
-  const int max_last = max(max(sMaxLast[0], sMaxLast[1]), max(sMaxLast[2], sMaxLast[3]));
-  if (n_act == 0) return;
-  if (active) sP[pre + rank] = make_float4((float)j + 0.5f, (float)i + 0.5f, gT, __int_as_float(last));
-  __syncthreads();
-
-  // work items = (64-Gaussian chunk) x (pixel split); only Gaussians up to max_last can contribute
-  const int n_live = min(n, max_last - start + 1);
-  const int n_chunks = (n_live + 63) >> 6;
-  const int splits = (n_chunks >= 4) ? 1 : ((n_chunks == 2) ? 2 : 4);
-  const int n_items = n_chunks * splits;
-  for (int item = wv; item < n_items; item += 4) {
-    const int chunk = item / splits, sp = item - chunk * splits;
-    const int q0 = (n_act * sp) / splits, q1 = (n_act * (sp + 1)) / splits;
-    const int idx = start + (chunk << 6) + lane;
-    const bool have = idx < start + n_live;
-    int g = 0;
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-    if (have) {
-      g = flat[idx];
-      s0 = splat[2 * g];
-      s1 = splat[2 * g + 1];
-    }
-    const float x = s0.x, y = s0.y, ca = s0.z, cb = s0.w, cc = s1.x, o = s1.y;
-    const float thr = have ? __logf(255.f * o) + kThrMargin : -1.f;
-    float ax = 0.f, ay = 0.f, aax = 0.f, aay = 0.f, aa = 0.f, ab = 0.f, ac = 0.f, ao = 0.f;
-    bool hit = false;
-    for (int q = q0; q < q1; ++q) {
-      const float4 P = sP[q];
-      const float dx = x - P.x, dy = y - P.y;
-      const float sigma = 0.5f * (ca * dx * dx + cc * dy * dy) + cb * dx * dy;
-      bool valid = (idx <= __float_as_int(P.w)) && (sigma >= 0.f) && (sigma <= thr);
-      if (!__any(valid)) continue;
-      const float vis = __expf(-sigma);
-      const float araw = o * vis;
-      const float alpha = fminf(kAlphaMax, araw);
-      valid = valid && (alpha >= kAlphaMin);
-      if (valid) {
-        hit = true;
-        const float v_alpha = P.z * __builtin_amdgcn_rcpf(1.f - alpha);  // dL/dalpha = v * T_final / (1 - alpha)
-        if (araw <= kAlphaMax) {
-          const float v_sigma = -araw * v_alpha;
-          const float gx = v_sigma * (ca * dx + cb * dy);
-          const float gy = v_sigma * (cb * dx + cc * dy);
-          ax += gx; ay += gy;
-          aax += fabsf(gx); aay += fabsf(gy);
-          aa += 0.5f * v_sigma * dx * dx;
-          ab += v_sigma * dx * dy;
-          ac += 0.5f * v_sigma * dy * dy;
-          ao += vis * v_alpha;
-        }
-      }
-    }
-    if (hit) {
-      float *dst = g2d + (size_t)g * 8;
-      unsafeAtomicAdd(dst + 0, ax);
-      unsafeAtomicAdd(dst + 1, ay);
-      unsafeAtomicAdd(dst + 2, aax);
-      unsafeAtomicAdd(dst + 3, aay);
-      unsafeAtomicAdd(dst + 4, aa);
-      unsafeAtomicAdd(dst + 5, ab);
-      unsafeAtomicAdd(dst + 6, ac);
-      unsafeAtomicAdd(dst + 7, ao);
-    }
-  }
-}
-
-// largest t with item_offsets[t] <= b (item_offsets[T] = n_items > b): the tile owning item b
-__device__ __forceinline__ int item_tile(const int *__restrict__ item_offsets, int T, int b) {
-  int lo = 0, hi = T;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (item_offsets[mid] <= b) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// The same lookup done by the whole 256-thread workgroup in two parallel probes (256 samples at a
-// fixed stride, then the entries of the selected stride) instead of log2(T) dependent loads by
-// everyone: the serial search was 10-13 global-memory latencies at the head of every workgroup.
-// Contains two workgroup barriers; `s_tmp` is 5 ints of LDS.
+// The tile owning item b -- the largest t with item_offsets[t] <= b (item_offsets[T] = n_items > b) -- looked up by
+// the whole 256-thread workgroup in two parallel probes (256 samples at a fixed stride, then the entries of the
+// selected stride) instead of log2(T) dependent loads by everyone: a serial binary search was 10-13 global-memory
+// latencies at the head of every workgroup.  Contains two workgroup barriers; `s_tmp` is 5 ints of LDS.
 __device__ __forceinline__ int item_tile_coop(const int *__restrict__ item_offsets, int T, int b, int *s_tmp) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int S = (T + 256) / 256;  // ceil((T + 1) / 256) entries per sample
@@ -577,10 +453,10 @@ composite_slice_fwd_kernel(const float4 *__restrict__ splat, const TileTable tt_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Chained forward: slice products, phase B and the EXACT transmittance stop in ONE kernel (used by the training
-// step whenever pixels do reach the stop, i.e. for most of a real training run).  Every slice workgroup of a tile
-// publishes its per-pixel product and last contributor (device-scope stores, then a per-item flag carrying the
-// caller's tag) and then LOOKS BACK: it waits for the flags of the slices in front of it -- lower block indices,
+// Chained forward: slice products, phase B and the EXACT transmittance stop in ONE kernel (used by a training step
+// that keeps its images, EdgeTrainer(keep_images=True), whenever pixels do reach the stop).  Every slice workgroup
+// of a tile publishes its per-pixel product and last contributor (device-scope stores, then a per-item flag carrying
+// the caller's tag) and then LOOKS BACK: it waits for the flags of the slices in front of it -- lower block indices,
 // dispatched earlier, never waiting on it, so the wait cannot deadlock (the decoupled look-back idiom of
 // single-pass scans) -- and multiplies their products up to its own slice.  That tells each pixel, in every slice
 // workgroup, whether its stop fell in an earlier slice (nothing to do), falls in THIS slice (resolved on the spot
@@ -651,7 +527,6 @@ __device__ __forceinline__ int exact_walk(const QuadLists &ql, int wv, int n_min
   return lastpos;
 }
 
-template <int CH>
 __global__ void __launch_bounds__(256)
 composite_chained_fwd_kernel(const float4 *__restrict__ splat, const TileTable tt_, const int *__restrict__ total,
                              const int *__restrict__ flat, int width, int height, int tw, int th, const SliceWs ws_,
@@ -666,7 +541,7 @@ composite_chained_fwd_kernel(const float4 *__restrict__ splat, const TileTable t
   const TileTable tt = view_of(tt_, bt, bv);
   const SliceWs ws = view_of(ws_, bt, bv);
   total += 4 * bv; flat += bv * bt.keys; splat += bv * bt.splat4;
-  if (render) render += bv * bt.pixels * CH;
+  if (render) render += bv * bt.pixels;
   if (alphas) alphas += bv * bt.pixels;
   if (last_ids) last_ids += bv * bt.pixels;
   if (vpix) vpix += bv * bt.pixels;
@@ -781,7 +656,7 @@ composite_chained_fwd_kernel(const float4 *__restrict__ splat, const TileTable t
   // pixels that never stop
   float l = 0.f;
   if (cross || (inside && !before && s_me == ns - 1))
-    l = finalize_pixel<CH>(i * width + j, T, last, cross && found, flat, render, alphas, last_ids, has_loss, gt_p, w_p,
+    l = finalize_pixel<1>(i * width + j, T, last, cross && found, flat, render, alphas, last_ids, has_loss, gt_p, w_p,
                            loss_scale, vpix, gtstop, splat);
   if (has_loss && loss_out) block_loss_add(l, sRed, loss_out);
 }
@@ -942,117 +817,8 @@ composite_rewalk_fwd_kernel(const float4 *__restrict__ splat, const TileTable tt
   }
 }
 
-// backward, unit colours, one workgroup per item: lane = Gaussian of the slice, loop = active pixels
-__global__ void __launch_bounds__(256)
-composite_bwd_item_kernel(const float4 *__restrict__ splat, const int *__restrict__ offsets,
-                          const int *__restrict__ item_offsets, const int *__restrict__ total,
-                          const int *__restrict__ flat, int width, int height, int tw, int th,
-                          const float *__restrict__ alphas, const int *__restrict__ last_ids,
-                          const float *__restrict__ vpix, float *__restrict__ g2d) {
-  __shared__ float4 sP[kTilePix];  // px, py, v*T_final, last id (int bits) -- compacted
-  __shared__ int sCnt[4];
-  __shared__ int sMaxLast[4];
-  const int b = blockIdx.x;
-  if (b >= total[2]) return;
-  const int tile = item_tile(item_offsets, tw * th, b);
-  const int start = offsets[tile] + (b - item_offsets[tile]) * kSlice;
-  const int end = min(offsets[tile + 1], start + kSlice);
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int ty = tile / tw, tx = tile - ty * tw;
-  const int i = ty * kTile + (tid >> 4), j = tx * kTile + (tid & 15);
-  const bool inside = (i < height) && (j < width);
-  float gT = 0.f;
-  int last = -1;
-  if (inside) {
-    const int p = i * width + j;
-    const float a = alphas[p];
-    const float v = vpix[p];
-    if (a > 0.f && v != 0.f) {  // a > 0 <=> at least one Gaussian contributed to this pixel
-      const int l = last_ids[p];
-      if (l >= start) { gT = v * (1.f - a); last = l; }  // nothing of this slice contributes otherwise
-    }
-  }
-  const bool active = (last >= 0) && (gT != 0.f);
-  const unsigned long long bal = __ballot(active);
-  const int rank = __popcll(bal & ((1ull << lane) - 1ull));
-  int wmax = last;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d, 64));
-  if (lane == 0) { sCnt[wv] = __popcll(bal); sMaxLast[wv] = wmax; }
-  __syncthreads();
-  int pre = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) pre += (w < wv) ? sCnt[w] : 0;
-  const int n_act = sCnt[0] + sCnt[1] + sCnt[2] + sCnt[3];
-  const int max_last = max(max(sMaxLast[0], sMaxLast[1]), max(sMaxLast[2], sMaxLast[3]));
-  if (n_act == 0) return;
-  if (active) sP[pre + rank] = make_float4((float)j + 0.5f, (float)i + 0.5f, gT, __int_as_float(last));
-  __syncthreads();
-
-  const int n_live = min(end, max_last + 1) - start;  // Gaussians past every pixel's stop are dead
-  if (n_live <= 0) return;
-  const int n_chunks = (n_live + 63) >> 6;
-  const int splits = (n_chunks >= 4) ? 1 : ((n_chunks == 2) ? 2 : 4);
-  const int n_items = n_chunks * splits;
-  for (int item = wv; item < n_items; item += 4) {
-    const int chunk = item / splits, sp = item - chunk * splits;
-    const int q0 = (n_act * sp) / splits, q1 = (n_act * (sp + 1)) / splits;
-    const int idx = start + (chunk << 6) + lane;
-    const bool have = idx < start + n_live;
-    int g = 0;
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-    if (have) {
-      g = flat[idx];
-      s0 = splat[2 * g];
-      s1 = splat[2 * g + 1];
-    }
-    const float x = s0.x, y = s0.y, ca = s0.z, cb = s0.w, cc = s1.x, o = s1.y;
-    const float thr = have ? __logf(255.f * o) + kThrMargin : -1.f;
-    float ax = 0.f, ay = 0.f, aax = 0.f, aay = 0.f, aa = 0.f, ab = 0.f, ac = 0.f, ao = 0.f;
-    bool hit = false;
-    for (int q = q0; q < q1; ++q) {
-      const float4 P = sP[q];
-      const float dx = x - P.x, dy = y - P.y;
-      const float sigma = 0.5f * (ca * dx * dx + cc * dy * dy) + cb * dx * dy;
-      bool valid = (idx <= __float_as_int(P.w)) && (sigma >= 0.f) && (sigma <= thr);
-      if (!__any(valid)) continue;
-      const float vis = __expf(-sigma);
-      const float araw = o * vis;
-      const float alpha = fminf(kAlphaMax, araw);
-      valid = valid && (alpha >= kAlphaMin);
-      if (valid) {
-        hit = true;
-        const float v_alpha = P.z * __builtin_amdgcn_rcpf(1.f - alpha);  // dL/dalpha = v * T_final / (1 - alpha)
-        if (araw <= kAlphaMax) {
-          const float v_sigma = -araw * v_alpha;
-          const float gx = v_sigma * (ca * dx + cb * dy);
-          const float gy = v_sigma * (cb * dx + cc * dy);
-          ax += gx; ay += gy;
-          aax += fabsf(gx); aay += fabsf(gy);
-          aa += 0.5f * v_sigma * dx * dx;
-          ab += v_sigma * dx * dy;
-          ac += 0.5f * v_sigma * dy * dy;
-          ao += vis * v_alpha;
-        }
-      }
-    }
-    if (hit) {
-      float *dst = g2d + (size_t)g * 8;
-      unsafeAtomicAdd(dst + 0, ax);
-      unsafeAtomicAdd(dst + 1, ay);
-      unsafeAtomicAdd(dst + 2, aax);
-      unsafeAtomicAdd(dst + 3, aay);
-      unsafeAtomicAdd(dst + 4, aa);
-      unsafeAtomicAdd(dst + 5, ab);
-      unsafeAtomicAdd(dst + 6, ac);
-      unsafeAtomicAdd(dst + 7, ao);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
-// Footprint backward for unit colours (the fused training path): no tile lists, no atomics.
+// Footprint backward for unit colours (the training step and the eager operator): no tile lists, no atomics.
 //
 // With colours == 1 and no background dL/dalpha_i = v_p T_final,p / (1 - alpha_i) for every Gaussian
 // that contributed to pixel p, independent of the depth order.  So a Gaussian's whole 2D gradient is
@@ -1359,19 +1125,15 @@ static int launch_sliced_fwd(const float4 *splat, const TileTable tt, int channe
   if (wave_forward_selected(channels, render, alphas, last_ids, vpix, gtstop, wmap, tt.item_rec, chain_tag))
     return launch_wave_fwd(splat, tt, flatten_ids, width, height, gt, wmap, loss_scale, total, max_items, workspace, gtstop,
                            !skip, (unsigned)chain_tag, max_tile_hint, s, bt, C);
-  // (rewalk_hint == 0 without speculation -- a caller without a journal, e.g. the data-parallel leg, that has seen no
-  // stop lately: the fused slice kernel + a 64-workgroup re-walk launch that finds an empty list is 3 us cheaper than
-  // the chained kernel's look-back, and still exact should a pixel stop after all)
+  // (rewalk_hint == 0 without speculation -- a caller that cannot replay the step and has seen no stop lately: the
+  // fused slice kernel + a 64-workgroup re-walk launch that finds an empty list is 3 us cheaper than the chained
+  // kernel's look-back, and still exact should a pixel stop after all)
   if (!skip && chain_tag > 0 && rewalk_hint != 0) {
-    // pixels do reach the stop: slice products, phase B and the exact stop in one kernel (decoupled look-back)
-    if (channels == 1)
-      composite_chained_fwd_kernel<1><<<dim3((unsigned)max_items, C), 256, 0, s>>>(
-          splat, tt, total, flatten_ids, width, height, tw, th, ws, chain_tag, render, alphas, last_ids, gt, wmap,
-          loss_scale, vpix, loss_out, (StopRec *)gtstop, bt);
-    else
-      composite_chained_fwd_kernel<3><<<dim3((unsigned)max_items, C), 256, 0, s>>>(
-          splat, tt, total, flatten_ids, width, height, tw, th, ws, chain_tag, render, alphas, last_ids, gt, wmap,
-          loss_scale, vpix, loss_out, (StopRec *)gtstop, bt);
+    // pixels do reach the stop: slice products, phase B and the exact stop in one kernel (decoupled look-back); only
+    // the training step passes a tag, and it composites one channel
+    composite_chained_fwd_kernel<<<dim3((unsigned)max_items, C), 256, 0, s>>>(
+        splat, tt, total, flatten_ids, width, height, tw, th, ws, chain_tag, render, alphas, last_ids, gt, wmap, loss_scale,
+        vpix, loss_out, (StopRec *)gtstop, bt);
     timing_mark(kMarkSlice, s);
     timing_mark(kMarkRewalk, s);
     return check_launch("composite_fwd(chained)");
@@ -1479,24 +1241,6 @@ extern "C" int eg_composite_fwd_segments(const float *splat, const int32_t *tile
   return launch_sliced_fwd((const float4 *)splat, tt, 1, flatten_ids, width, height, render, alphas, last_ids, gt, wmap,
                            loss_scale, vpix, loss_out, total, max_items, workspace, gtstop, rewalk_hint,
                            as_stream(stream));
-}
-
-extern "C" int eg_composite_bwd(const float *splat, const int32_t *offsets, const int32_t *flatten_ids,
-                                int32_t width, int32_t height, const float *alphas, const int32_t *last_ids,
-                                const float *vpix, float *g2d, const int32_t *item_offsets, const int32_t *total,
-                                int64_t max_items, eg_stream_t stream) {
-  EG_REQUIRE(width > 0 && height > 0, "bad sizes");
-  EG_REQUIRE(splat && offsets && alphas && last_ids && vpix && g2d, "null pointer");
-  const int tw = cdiv(width, kTile), th = cdiv(height, kTile);
-  if (item_offsets && total && max_items > 0)
-    composite_bwd_item_kernel<<<(unsigned)max_items, 256, 0, as_stream(stream)>>>(
-        (const float4 *)splat, offsets, item_offsets, total, flatten_ids, width, height, tw, th, alphas, last_ids,
-        vpix, g2d);
-  else
-    composite_bwd_unit_kernel<<<tw * th, 256, 0, as_stream(stream)>>>((const float4 *)splat, offsets, flatten_ids,
-                                                                      width, height, tw, th, alphas, last_ids,
-                                                                      vpix, g2d);
-  return check_launch("composite_bwd");
 }
 
 extern "C" int eg_composite_bwd_footprint(const float *splat, int32_t N, int32_t width, int32_t height,

@@ -117,37 +117,34 @@ class _Compositing(torch.autograd.Function):
         alphas = torch.empty(Cn, height, width, 1, device=dev)
         last_ids = torch.empty(Cn, height, width, dtype=torch.int32, device=dev)
         # unit colours: the sliced forward leaves the per-pixel record {T_final, stop id, stop depth} that the
-        # order-independent footprint backward reads (deterministic, no atomics, no zero-fill of the gradients)
-        sliced = unit_colors and all(n > 0 for n in n_items)
-        gtstop = torch.empty(Cn, height, width, 3, device=dev) if sliced else None
+        # order-independent footprint backward reads (deterministic, no atomics, no zero-fill of the gradients).
+        # (n_items >= 1 per camera: eg_tile_offsets gives every tile, empty or not, at least one item)
+        gtstop = torch.empty(Cn, height, width, 3, device=dev) if unit_colors else None
         # (round 6: ONE native call for the C cameras; the arrays whose sizes differ per camera go as host arrays of pointers)
         T = offsets[0].shape[0] - 1
-        ws = [(_lib.composite_workspace(n_items[c], T, dev) if (unit_colors and n_items[c] > 0) else None) for c in range(Cn)]
+        ws = [_lib.composite_workspace(n, T, dev) if unit_colors else None for n in n_items]
         PV = C.c_void_p * Cn
         call("eg_composite_fwd_cams", Cn, ptr(splat), N, None if unit_colors else ptr(colors_c), 1 if colors_c.dim() == 3 else 0, D,
              PV(*[ptr(o) for o in offsets]), PV(*[ptr(f) for f in flatten_ids]), width, height, ptr(render), ptr(alphas),
              ptr(last_ids), PV(*[ptr(t) if w is not None else None for t, w in zip(item_offsets, ws)]),
              PV(*[ptr(t) if w is not None else None for t, w in zip(totals, ws)]),
-             (C.c_int64 * Cn)(*[int(n) for n in n_items]), PV(*[ptr(w) for w in ws]), ptr(gtstop) if sliced else None, stream())
-        ctx.save_for_backward(means2d, splat, colors_c, alphas, last_ids, *offsets, *flatten_ids, *item_offsets,
-                              *totals)
+             (C.c_int64 * Cn)(*[int(n) for n in n_items]), PV(*[ptr(w) for w in ws]), ptr(gtstop), stream())
+        ctx.save_for_backward(means2d, splat, colors_c, alphas, last_ids, *offsets, *flatten_ids)
         ctx.gtstop = gtstop
-        ctx.cfg = (width, height, absgrad, unit_colors, Cn, tuple(n_items))
+        ctx.cfg = (width, height, absgrad, unit_colors, Cn)
         ctx.mark_non_differentiable(last_ids)
         return render, alphas, last_ids
 
     @staticmethod
     def backward(ctx, v_render, v_alphas, _v_last):
-        width, height, absgrad, unit_colors, Cn, n_items = ctx.cfg
+        width, height, absgrad, unit_colors, Cn = ctx.cfg
         saved = ctx.saved_tensors
         means2d, splat, colors, alphas, last_ids = saved[:5]
         offsets, flatten_ids = saved[5:5 + Cn], saved[5 + Cn:5 + 2 * Cn]
-        item_offsets, totals = saved[5 + 2 * Cn:5 + 3 * Cn], saved[5 + 3 * Cn:5 + 4 * Cn]
         N, D = means2d.shape[1], colors.shape[-1]
         dev = means2d.device
         need_vcol = ctx.needs_input_grad[2]
-        v_colors = None
-        if unit_colors and not need_vcol and ctx.gtstop is not None:
+        if unit_colors and not need_vcol:
             # footprint backward: every Gaussian sums over its own footprint in the {v * T_final, stop} record
             rec = ctx.gtstop.clone()
             rec[..., 0] *= (v_render.sum(-1) + v_alphas[..., 0])
@@ -160,22 +157,15 @@ class _Compositing(torch.autograd.Function):
         g2d = torch.zeros(Cn, N, 8, device=dev)
         v_render = v_render.contiguous()
         v_alphas = v_alphas.contiguous()
-        if unit_colors and not need_vcol:
-            vpix = (v_render.sum(-1) + v_alphas[..., 0]).contiguous()
-            for c in range(Cn):
-                call("eg_composite_bwd", ptr(splat[c]), ptr(offsets[c]), ptr(flatten_ids[c]), width, height,
-                     ptr(alphas[c]), ptr(last_ids[c]), ptr(vpix[c]), ptr(g2d[c]),
-                     ptr(item_offsets[c]), ptr(totals[c]), n_items[c], stream())
-        else:
-            per_cam = colors.dim() == 3
-            v_colors = torch.zeros(Cn, N, D, device=dev) if need_vcol else None
-            for c in range(Cn):
-                call("eg_composite_bwd_colors", ptr(splat[c]), ptr(colors[c] if per_cam else colors), D,
-                     ptr(offsets[c]), ptr(flatten_ids[c]), width, height, ptr(alphas[c]), ptr(last_ids[c]),
-                     ptr(v_render[c]), ptr(v_alphas[c]), ptr(g2d[c]),
-                     ptr(v_colors[c]) if v_colors is not None else None, stream())
-            if v_colors is not None and not per_cam:
-                v_colors = v_colors.sum(0)
+        per_cam = colors.dim() == 3
+        v_colors = torch.zeros(Cn, N, D, device=dev) if need_vcol else None
+        for c in range(Cn):
+            call("eg_composite_bwd_colors", ptr(splat[c]), ptr(colors[c] if per_cam else colors), D,
+                 ptr(offsets[c]), ptr(flatten_ids[c]), width, height, ptr(alphas[c]), ptr(last_ids[c]),
+                 ptr(v_render[c]), ptr(v_alphas[c]), ptr(g2d[c]),
+                 ptr(v_colors[c]) if v_colors is not None else None, stream())
+        if v_colors is not None and not per_cam:
+            v_colors = v_colors.sum(0)
         if absgrad:
             means2d.absgrad = g2d[..., 2:4].contiguous()
         return (g2d[..., 0:2].contiguous(), g2d[..., 4:7].contiguous(), v_colors, g2d[..., 7].contiguous(),

@@ -161,7 +161,8 @@ int eg_composite_fwd_segments(const float *splat, const int32_t *tile_start, con
  * channels = 1 or 3.  colors == NULL means "all ones" (the reference's colours, edge_gs.py:247).
  * Fused weighted-L1 (edge_gs.py:279,288-324 in weight-map form): when wmap != NULL,
  * channel 0 is clamped to [0,1], loss_out[0] += sum_p wmap_p*|c0_p - gt_p| and
- * vpix[p] = loss_scale * wmap_p * sign(c0_p - gt_p) (the upstream gradient of eg_composite_bwd).
+ * vpix[p] = loss_scale * wmap_p * sign(c0_p - gt_p) (the upstream gradient dL/dc0: v_render of
+ * eg_composite_bwd_colors with one channel).
  * Slice-parallel mode (unit colours only): pass item_offsets + total from eg_tile_offsets, an upper
  * bound max_items >= total[2] (e.g. ceil(capacity/128) + T) and a workspace of
  * eg_composite_workspace_bytes(max_items, T) bytes; one workgroup runs per (tile, 128-Gaussian slice; an
@@ -195,17 +196,10 @@ int eg_composite_fwd(const float *splat, const float *colors /*[N,channels]|NULL
                      hint >= -1 (what EdgeTrainer's journal does), then zero the word*/,
                      eg_stream_t stream);
 
-/* ---- G8: compositing backward for unit colours (replaces gsplat rasterize_to_pixels bwd for the
- * reference's call).  vpix[p] = sum_k dL/drender[p,k] + dL/dalpha[p].  Accumulates
- * into g2d with float atomics. */
-int eg_composite_bwd(const float *splat, const int32_t *offsets, const int32_t *flatten_ids,
-                     int32_t width, int32_t height, const float *alphas, const int32_t *last_ids,
-                     const float *vpix, float *g2d /*[N,8] accumulated*/,
-                     const int32_t *item_offsets /*[T+1]|NULL*/, const int32_t *total /*[4]|NULL*/,
-                     int64_t max_items, eg_stream_t stream);
-
-/* ---- G8 (general colours): order-dependent backward with per-Gaussian colours, channels = 3.
- * v_colors may be NULL. */
+/* ---- G8: compositing backward (replaces gsplat rasterize_to_pixels bwd), order-dependent: general
+ * colours, or unit colours when the caller wants their gradient.  channels = 1 or 3; colors == NULL means "all ones".
+ * Accumulates into g2d with float atomics.  v_colors may be NULL.  Unit colours without a colour gradient take
+ * eg_composite_bwd_footprint. */
 int eg_composite_bwd_colors(const float *splat, const float *colors, int32_t channels,
                             const int32_t *offsets, const int32_t *flatten_ids, int32_t width, int32_t height,
                             const float *alphas, const int32_t *last_ids, const float *v_render,

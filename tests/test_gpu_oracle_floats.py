@@ -3,8 +3,8 @@
 north_star: "tile/pixel indexing bit-exact".  Whether a pixel's last contributor, its alpha and the
 per-Gaussian 2-D gradients agree can only be asked on identical inputs: these tests hand the C oracle's
 projected means2d / conics / opacities and its sorted tile lists to `eg_composite_fwd` (the classic tile
-kernel AND the slice -> combine -> re-walk path), `eg_composite_bwd` (operator path) and
-`eg_composite_bwd_footprint` (fused path), and compare
+kernel AND the slice -> combine -> re-walk path), `eg_composite_bwd_colors` (the operator's backward for
+general colours) and `eg_composite_bwd_footprint` (fused path), and compare
 
   * last_ids  -- EXACT on every pixel outside the quantified borderline set (tests/util.py),
   * alphas    -- 1e-4 on the same pixels,
@@ -88,8 +88,7 @@ def _composite_fwd(_lib, splat, offs, flat, W, H, sliced, gt=None, wmap=None):
          ptr(gt), ptr(wmap), 1.0, ptr(vpix), ptr(loss), ptr(item_offsets), ptr(total), max(n_items, 1) if sliced else 0,
          ptr(ws), ptr(gtstop), -1, stream())
     torch.cuda.synchronize()
-    return dict(render=render[..., 0], alphas=alphas, last=last, vpix=vpix, loss=loss, gtstop=gtstop,
-                item_offsets=item_offsets, total=total, n_items=n_items)
+    return dict(render=render[..., 0], alphas=alphas, last=last, vpix=vpix, loss=loss, gtstop=gtstop)
 
 
 @pytest.mark.parametrize("kind", ["spread", "stops", "deep"])
@@ -126,7 +125,7 @@ def test_composite_forward_pixel_indexing_exact_on_oracle_floats(env, kind, slic
 
 
 @pytest.mark.parametrize("kind", ["spread", "stops", "deep"])
-def test_composite_backward_on_oracle_floats(env, kind):
+def test_footprint_and_colors_backward_on_oracle_floats(env, kind):
     """2-D gradients (v_means2d, |v_means2d|, v_conics, v_opacity) of both backward kernels against the C
     oracle's sequential back-to-front walk, same floats, same bins, borderline pixels zero-weighted."""
     _lib, synth, CO = env
@@ -151,20 +150,19 @@ def test_composite_backward_on_oracle_floats(env, kind):
     assert abs(float(out["loss"]) - loss_o) <= 1e-4 * abs(loss_o)
     g2d_f = torch.full((N, 8), float("nan"), device="cuda")
     call("eg_composite_bwd_footprint", ptr(splat), N, W, H, ptr(out["gtstop"]), ptr(g2d_f), stream())
-    # (ii) operator path: item-parallel backward from (alphas, last_ids, vpix)
-    g2d_i = torch.zeros(N, 8, device="cuda")
-    call("eg_composite_bwd", ptr(splat), ptr(offs), ptr(flat), W, H, ptr(out["alphas"]), ptr(out["last"]),
-         ptr(out["vpix"]), ptr(g2d_i), ptr(out["item_offsets"]), ptr(out["total"]), max(out["n_items"], 1), stream())
-    # (iii) operator path, one workgroup per tile
-    g2d_t = torch.zeros(N, 8, device="cuda")
-    call("eg_composite_bwd", ptr(splat), ptr(offs), ptr(flat), W, H, ptr(out["alphas"]), ptr(out["last"]),
-         ptr(out["vpix"]), ptr(g2d_t), None, None, 0, stream())
+    # (ii) operator path for general colours: order-dependent backward from (alphas, last_ids), here with colours all
+    #      ones, v_render = vpix, v_alphas = 0
+    ones = torch.ones(N, 1, device="cuda")
+    v_alphas = torch.zeros(H, W, device="cuda")
+    g2d_c = torch.zeros(N, 8, device="cuda")
+    call("eg_composite_bwd_colors", ptr(splat), ptr(ones), 1, ptr(offs), ptr(flat), W, H, ptr(out["alphas"]),
+         ptr(out["last"]), ptr(out["vpix"]), ptr(v_alphas), ptr(g2d_c), None, stream())
     torch.cuda.synchronize()
     vis = torch.from_numpy(fw["radii"] > 0)
     names = ("v_means2d", "v_means2d_abs", "v_conics", "v_opacity")
     cols = ((0, 2), (2, 4), (4, 7), (7, 8))
     errs = {}
-    for tag, g in (("footprint", g2d_f), ("item", g2d_i), ("tile", g2d_t)):
+    for tag, g in (("footprint", g2d_f), ("colors", g2d_c)):
         g = g.cpu()
         for name, (c0, c1) in zip(names, cols):
             a, b = g[vis][:, c0:c1], torch.from_numpy(ref)[vis][:, c0:c1]
