@@ -33,7 +33,9 @@
 // Gaussian: the pass is order-independent, and the footprint kernel below sums each Gaussian over its own pixels.
 //
 // General colours, and callers that want colour gradients, take the classic order-dependent pixel-per-lane backward
-// with wave64 butterfly reductions (eg_composite_bwd_colors); it is off the reference's path and not tuned.
+// with wave64 butterfly reductions (eg_composite_bwd_colors); it is off the reference's path and not tuned.  gsplat's
+// depth render modes and backgrounds run the same two classic kernels with a depth channel and / or a background
+// (eg_composite_{fwd,bwd}_modes_cams, ModeArgs below).
 #include <cstdlib>
 
 #include "common.h"
@@ -42,18 +44,50 @@
 namespace eg {
 
 
-template <int CH, bool UNIT>
+// The render-mode entries (eg_composite_{fwd,bwd}_modes_cams) instantiate the classic kernels with DEPTH and / or BG:
+// one launch for C cameras (blockIdx.y = camera, ModeArgs), the projection depth (s1.z of the splat record) composited
+// as one more channel after the CH colour channels (CH = 0: depth only), and a background under the final
+// transmittance.  The defaults are the single-camera kernels of the other entries, whose code they leave as it was.
+struct ModeArgs {
+  const float *bg;  // [C, CH] with BG
+  float *v_depths;  // [C, N] (backward, DEPTH), accumulated
+  int N;
+  int colors_per_camera;
+};
+
+// flatten_ids of the mode entries: the C cameras' lists one after the other, offsets [C, T+1] local to each list
+__device__ __forceinline__ int camera_list_base(const int *__restrict__ offsets, int T, int c) {
+  int base = 0;
+  for (int k = 0; k < c; ++k) base += offsets[(size_t)k * (T + 1) + T];
+  return base;
+}
+
+template <int CH, bool UNIT, bool DEPTH = false, bool BG = false>
 __global__ void __launch_bounds__(256)
 composite_fwd_kernel(const float4 *__restrict__ splat, const float *__restrict__ colors,
                      const int *__restrict__ offsets, const int *__restrict__ flat, int width, int height,
                      int tw, int th, float *__restrict__ render, float *__restrict__ alphas,
                      int *__restrict__ last_ids, const float *__restrict__ gt, const float *__restrict__ wmap,
-                     float loss_scale, float *__restrict__ vpix, float *__restrict__ loss_out) {
+                     float loss_scale, float *__restrict__ vpix, float *__restrict__ loss_out, const ModeArgs ma) {
+  constexpr bool kModes = DEPTH || BG;
+  constexpr int NC = CH + (DEPTH ? 1 : 0);  // channels of a rendered pixel
+  static_assert(NC >= 1, "nothing to composite");
   __shared__ float4 sA[kTilePix];  // x, y, a, b
-  __shared__ float4 sB[kTilePix];  // c, o, sigma threshold, -
-  __shared__ float sC[UNIT ? 1 : kTilePix * CH];
+  __shared__ float4 sB[kTilePix];  // c, o, sigma threshold, depth (DEPTH)
+  __shared__ float sC[(UNIT || CH == 0) ? 1 : kTilePix * CH];
   __shared__ float sRed[4];
 
+  if constexpr (kModes) {
+    const int c = blockIdx.y, T = tw * th;
+    const size_t hw = (size_t)width * height;
+    flat += camera_list_base(offsets, T, c);
+    offsets += (size_t)c * (T + 1);
+    splat += 2 * (size_t)ma.N * c;
+    if (ma.colors_per_camera) colors += (size_t)ma.N * CH * c;
+    render += hw * NC * c;
+    alphas += hw * c;
+    last_ids += hw * c;
+  }
   const int tile = xcd_tile(blockIdx.x, tw * th);
   const int tid = threadIdx.x;
   const int ty = tile / tw, tx = tile - ty * tw;
@@ -63,9 +97,9 @@ composite_fwd_kernel(const float4 *__restrict__ splat, const float *__restrict__
   const int start = offsets[tile], end = offsets[tile + 1];
 
   float T = 1.f;
-  float pix[CH];
+  float pix[NC];
 #pragma unroll
-  for (int k = 0; k < CH; ++k) pix[k] = 0.f;
+  for (int k = 0; k < NC; ++k) pix[k] = 0.f;
   int last = 0;
   bool done = !inside;
 
@@ -76,7 +110,7 @@ composite_fwd_kernel(const float4 *__restrict__ splat, const float *__restrict__
       const int g = flat[idx];
       const float4 s0 = splat[2 * g], s1 = splat[2 * g + 1];
       sA[tid] = s0;
-      sB[tid] = make_float4(s1.x, s1.y, __logf(255.f * s1.y) + kThrMargin, 0.f);
+      sB[tid] = make_float4(s1.x, s1.y, __logf(255.f * s1.y) + kThrMargin, DEPTH ? s1.z : 0.f);
       if (!UNIT) {
 #pragma unroll
         for (int k = 0; k < CH; ++k) sC[tid * CH + k] = colors[(size_t)g * CH + k];
@@ -101,6 +135,7 @@ composite_fwd_kernel(const float4 *__restrict__ splat, const float *__restrict__
 #pragma unroll
         for (int k = 0; k < CH; ++k) pix[k] += sC[t * CH + k] * w;
       }
+      if constexpr (DEPTH) pix[CH] += B.w * w;
       last = base + t;
       T = next_T;
     }
@@ -111,9 +146,13 @@ composite_fwd_kernel(const float4 *__restrict__ splat, const float *__restrict__
     const int p = i * width + j;
     alphas[p] = 1.f - T;
     last_ids[p] = last;
+    if constexpr (BG) {  // (the depth channel's background is 0)
 #pragma unroll
-    for (int k = 0; k < CH; ++k) render[(size_t)p * CH + k] = pix[k];
-    if (wmap) {
+      for (int k = 0; k < CH; ++k) pix[k] += T * ma.bg[(size_t)blockIdx.y * CH + k];
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) render[(size_t)p * NC + k] = pix[k];
+    if (!kModes && wmap) {
       const float w = wmap[p];
       const float c0 = fminf(fmaxf(pix[0], 0.f), 1.f);
       const float d = c0 - gt[p];
@@ -123,7 +162,7 @@ composite_fwd_kernel(const float4 *__restrict__ splat, const float *__restrict__
       if (vpix) vpix[p] = loss_scale * w * sgn * pass;
     }
   }
-  if (wmap && loss_out) {
+  if (!kModes && wmap && loss_out) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d, 64);
     if ((tid & 63) == 0) sRed[tid >> 6] = l;
@@ -971,19 +1010,37 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-template <int CH>
+template <int CH, bool DEPTH = false, bool BG = false>
 __global__ void __launch_bounds__(256)
 composite_bwd_colors_kernel(const float4 *__restrict__ splat, const float *__restrict__ colors,
                             const int *__restrict__ offsets, const int *__restrict__ flat, int width,
                             int height, int tw, int th, const float *__restrict__ alphas,
                             const int *__restrict__ last_ids, const float *__restrict__ v_render,
                             const float *__restrict__ v_alphas, float *__restrict__ g2d,
-                            float *__restrict__ v_colors) {
+                            float *__restrict__ v_colors, const ModeArgs ma) {
+  constexpr bool kModes = DEPTH || BG;
+  constexpr int NC = CH + (DEPTH ? 1 : 0);  // channels of a rendered pixel
+  constexpr int CA = CH > 0 ? CH : 1;       // (array extent: the depth-only mode has no colour channel)
+  static_assert(NC >= 1, "nothing to composite");
   __shared__ float4 sA[kTilePix];
-  __shared__ float4 sB[kTilePix];
-  __shared__ float sC[kTilePix * CH];
+  __shared__ float4 sB[kTilePix];  // c, o, -, depth (DEPTH)
+  __shared__ float sC[kTilePix * CA];
   __shared__ int sG[kTilePix];
 
+  if constexpr (kModes) {
+    const int c = blockIdx.y, T = tw * th;
+    const size_t hw = (size_t)width * height, n = (size_t)ma.N;
+    flat += camera_list_base(offsets, T, c);
+    offsets += (size_t)c * (T + 1);
+    splat += 2 * n * c;
+    if (ma.colors_per_camera) colors += n * CH * c;
+    alphas += hw * c;
+    last_ids += hw * c;
+    v_render += hw * NC * c;
+    if (v_alphas) v_alphas += hw * c;
+    g2d += 8 * n * c;
+    if (v_colors) v_colors += n * CH * c;
+  }
   const int tile = xcd_tile(blockIdx.x, tw * th);
   const int start = offsets[tile], end = offsets[tile + 1];
   if (end <= start) return;
@@ -996,9 +1053,16 @@ composite_bwd_colors_kernel(const float4 *__restrict__ splat, const float *__res
 
   const float T_final = inside ? 1.f - alphas[p] : 1.f;
   float T = T_final;
-  float buffer[CH], vr[CH];
+  float buffer[CA], vr[CA];
 #pragma unroll
-  for (int k = 0; k < CH; ++k) { buffer[k] = 0.f; vr[k] = inside ? v_render[(size_t)p * CH + k] : 0.f; }
+  for (int k = 0; k < CH; ++k) { buffer[k] = 0.f; vr[k] = inside ? v_render[(size_t)p * NC + k] : 0.f; }
+  float buffer_d = 0.f, vr_d = 0.f;  // the depth channel (DEPTH)
+  if constexpr (DEPTH) vr_d = inside ? v_render[(size_t)p * NC + CH] : 0.f;
+  float bg_vr = 0.f;  // sum_k bg[k] v_render[k] (BG)
+  if constexpr (BG) {
+#pragma unroll
+    for (int k = 0; k < CH; ++k) bg_vr += ma.bg[(size_t)blockIdx.y * CH + k] * vr[k];
+  }
   const float va_pix = (inside && v_alphas) ? v_alphas[p] : 0.f;
   // a pixel nothing contributed to has alpha == 0 exactly; mark it with last = -1
   const int bin_final = (inside && alphas[p] > 0.f) ? last_ids[p] : -1;
@@ -1017,7 +1081,7 @@ composite_bwd_colors_kernel(const float4 *__restrict__ splat, const float *__res
       const float4 s0 = splat[2 * g], s1 = splat[2 * g + 1];
       sG[tid] = g;
       sA[tid] = s0;
-      sB[tid] = make_float4(s1.x, s1.y, 0.f, 0.f);
+      sB[tid] = make_float4(s1.x, s1.y, DEPTH ? s1.z : 0.f, 0.f);
 #pragma unroll
       for (int k = 0; k < CH; ++k) sC[tid * CH + k] = colors ? colors[(size_t)g * CH + k] : 1.f;
     }
@@ -1034,9 +1098,10 @@ composite_bwd_colors_kernel(const float4 *__restrict__ splat, const float *__res
         if (sigma < 0.f || alpha < kAlphaMin) valid = false;
       }
       if (!__any(valid)) continue;
-      float r_rgb[CH];
+      float r_rgb[CA];
 #pragma unroll
       for (int k = 0; k < CH; ++k) r_rgb[k] = 0.f;
+      float r_d = 0.f;
       float gx = 0.f, gy = 0.f, ga = 0.f, gb = 0.f, gc = 0.f, go = 0.f;
       if (valid) {
         const float ra = 1.f / (1.f - alpha);
@@ -1048,7 +1113,12 @@ composite_bwd_colors_kernel(const float4 *__restrict__ splat, const float *__res
           r_rgb[k] = fac * vr[k];
           v_alpha += (sC[t * CH + k] * T - buffer[k] * ra) * vr[k];
         }
+        if constexpr (DEPTH) {
+          r_d = fac * vr_d;
+          v_alpha += (B.z * T - buffer_d * ra) * vr_d;
+        }
         v_alpha += T_final * ra * va_pix;
+        if constexpr (BG) v_alpha += -T_final * ra * bg_vr;
         if (B.y * vis <= kAlphaMax) {
           const float v_sigma = -B.y * vis * v_alpha;
           gx = v_sigma * (A.z * dx + A.w * dy);
@@ -1060,12 +1130,14 @@ composite_bwd_colors_kernel(const float4 *__restrict__ splat, const float *__res
         }
 #pragma unroll
         for (int k = 0; k < CH; ++k) buffer[k] += sC[t * CH + k] * fac;
+        if constexpr (DEPTH) buffer_d += B.z * fac;
       }
       const float agx = wave_sum(fabsf(gx)), agy = wave_sum(fabsf(gy));
       gx = wave_sum(gx); gy = wave_sum(gy);
       ga = wave_sum(ga); gb = wave_sum(gb); gc = wave_sum(gc); go = wave_sum(go);
 #pragma unroll
       for (int k = 0; k < CH; ++k) r_rgb[k] = wave_sum(r_rgb[k]);
+      if constexpr (DEPTH) r_d = wave_sum(r_d);
       if (lane == 0) {
         const int g = sG[t];
         float *dst = g2d + (size_t)g * 8;
@@ -1081,6 +1153,7 @@ composite_bwd_colors_kernel(const float4 *__restrict__ splat, const float *__res
 #pragma unroll
           for (int k = 0; k < CH; ++k) unsafeAtomicAdd(v_colors + (size_t)g * CH + k, r_rgb[k]);
         }
+        if constexpr (DEPTH) unsafeAtomicAdd(ma.v_depths + (size_t)blockIdx.y * ma.N + g, r_d);
       }
     }
   }
@@ -1191,7 +1264,7 @@ extern "C" int eg_composite_fwd(const float *splat, const float *colors, int32_t
 #define EG_LAUNCH_FWD(CH, UNIT)                                                                              \
   composite_fwd_kernel<CH, UNIT><<<tw * th, 256, 0, s>>>((const float4 *)splat, colors, offsets, flatten_ids, \
                                                         width, height, tw, th, render, alphas, last_ids, gt,  \
-                                                        wmap, loss_scale, vpix, loss_out)
+                                                        wmap, loss_scale, vpix, loss_out, ModeArgs{})
   if (channels == 1) { if (colors) EG_LAUNCH_FWD(1, false); else EG_LAUNCH_FWD(1, true); }
   else               { if (colors) EG_LAUNCH_FWD(3, false); else EG_LAUNCH_FWD(3, true); }
 #undef EG_LAUNCH_FWD
@@ -1299,10 +1372,80 @@ extern "C" int eg_composite_bwd_colors(const float *splat, const float *colors, 
   if (channels == 1)
     composite_bwd_colors_kernel<1><<<tw * th, 256, 0, s>>>((const float4 *)splat, colors, offsets, flatten_ids,
                                                           width, height, tw, th, alphas, last_ids, v_render,
-                                                          v_alphas, g2d, v_colors);
+                                                          v_alphas, g2d, v_colors, ModeArgs{});
   else
     composite_bwd_colors_kernel<3><<<tw * th, 256, 0, s>>>((const float4 *)splat, colors, offsets, flatten_ids,
                                                           width, height, tw, th, alphas, last_ids, v_render,
-                                                          v_alphas, g2d, v_colors);
+                                                          v_alphas, g2d, v_colors, ModeArgs{});
   return check_launch("composite_bwd_colors");
 }
+
+// ---------------------------------------------------------------------------------------------
+// gsplat's render modes and backgrounds for C cameras, one launch each way (gridDim.y = camera): the classic kernels
+// with the depth channel and / or the background (ModeArgs above)
+// (a macro, not a function: the error message names the entry point)
+#define EG_MODES_CHECK(C, N, channels, depth, width, height)                                       \
+  EG_REQUIRE(C >= 1 && C <= 65535 && N >= 0 && width > 0 && height > 0, "bad sizes");              \
+  EG_REQUIRE(channels == 0 || channels == 1 || channels == 3, "channels must be 0, 1 or 3");        \
+  EG_REQUIRE(channels > 0 || depth, "zero colour channels need the depth channel")
+
+#define EG_MODES_DISPATCH(LAUNCH)                                     \
+  do {                                                                \
+    if (depth) {                                                      \
+      if (channels == 0) LAUNCH(0, true, false);                      \
+      else if (channels == 1) { if (bg) LAUNCH(1, true, true); else LAUNCH(1, true, false); } \
+      else { if (bg) LAUNCH(3, true, true); else LAUNCH(3, true, false); } \
+    } else {                                                          \
+      if (channels == 1) LAUNCH(1, false, true); else LAUNCH(3, false, true); \
+    }                                                                 \
+  } while (0)
+
+extern "C" int eg_composite_fwd_modes_cams(int32_t C, const float *splat, int32_t N, const float *colors,
+                                           int32_t colors_per_camera, int32_t channels, int32_t depth,
+                                           const float *backgrounds, const int32_t *offsets,
+                                           const int32_t *flatten_ids, int32_t width, int32_t height, float *render,
+                                           float *alphas, int32_t *last_ids, eg_stream_t stream) {
+  EG_MODES_CHECK(C, N, channels, depth, width, height);
+  EG_REQUIRE(depth || backgrounds, "without the depth channel or a background this is eg_composite_fwd_cams");
+  EG_REQUIRE(splat && offsets && flatten_ids && render && alphas && last_ids, "null pointer");
+  EG_REQUIRE(channels == 0 || colors, "null colors (channels > 0)");
+  const int tw = cdiv(width, kTile), th = cdiv(height, kTile);
+  const float *bg = channels > 0 ? backgrounds : nullptr;  // (the depth channel's background is 0)
+  const ModeArgs ma = {bg, nullptr, N, colors_per_camera != 0};
+  hipStream_t s = as_stream(stream);
+#define EG_LAUNCH_FWD_MODES(CH, DEPTH, BG)                                                                   \
+  composite_fwd_kernel<CH, false, DEPTH, BG><<<dim3(tw * th, C), 256, 0, s>>>(                                \
+      (const float4 *)splat, colors, offsets, flatten_ids, width, height, tw, th, render, alphas, last_ids,      \
+      nullptr, nullptr, 1.f, nullptr, nullptr, ma)
+  EG_MODES_DISPATCH(EG_LAUNCH_FWD_MODES);
+#undef EG_LAUNCH_FWD_MODES
+  return check_launch("composite_fwd_modes_cams");
+}
+
+extern "C" int eg_composite_bwd_modes_cams(int32_t C, const float *splat, int32_t N, const float *colors,
+                                           int32_t colors_per_camera, int32_t channels, int32_t depth,
+                                           const float *backgrounds, const int32_t *offsets,
+                                           const int32_t *flatten_ids, int32_t width, int32_t height,
+                                           const float *alphas, const int32_t *last_ids, const float *v_render,
+                                           const float *v_alphas, float *g2d, float *v_colors, float *v_depths,
+                                           eg_stream_t stream) {
+  EG_MODES_CHECK(C, N, channels, depth, width, height);
+  EG_REQUIRE(depth || backgrounds, "without the depth channel or a background this is eg_composite_bwd_colors");
+  EG_REQUIRE(splat && offsets && flatten_ids && alphas && last_ids && v_render && g2d, "null pointer");
+  EG_REQUIRE(channels == 0 || colors, "null colors (channels > 0)");
+  EG_REQUIRE(!depth || v_depths, "null v_depths (depth channel)");
+  const int tw = cdiv(width, kTile), th = cdiv(height, kTile);
+  const float *bg = channels > 0 ? backgrounds : nullptr;
+  if (channels == 0) v_colors = nullptr;
+  const ModeArgs ma = {bg, v_depths, N, colors_per_camera != 0};
+  hipStream_t s = as_stream(stream);
+#define EG_LAUNCH_BWD_MODES(CH, DEPTH, BG)                                                                   \
+  composite_bwd_colors_kernel<CH, DEPTH, BG><<<dim3(tw * th, C), 256, 0, s>>>(                               \
+      (const float4 *)splat, colors, offsets, flatten_ids, width, height, tw, th, alphas, last_ids, v_render,   \
+      v_alphas, g2d, v_colors, ma)
+  EG_MODES_DISPATCH(EG_LAUNCH_BWD_MODES);
+#undef EG_LAUNCH_BWD_MODES
+  return check_launch("composite_bwd_modes_cams");
+}
+#undef EG_MODES_DISPATCH
+#undef EG_MODES_CHECK

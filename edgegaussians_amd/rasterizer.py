@@ -172,6 +172,56 @@ class _Compositing(torch.autograd.Function):
                 None, None, None, None, None, None, None, None, None, None)
 
 
+class _ModeCompositing(torch.autograd.Function):
+    """gsplat ``rasterize_to_pixels`` (packed=False) for C cameras with the projection depth as an extra last channel
+    and / or ``backgrounds`` [C, D]: one native call each way (eg_composite_{fwd,bwd}_modes_cams).  `colors` is None
+    in the depth-only modes.  The depth channel reads the depths from the packed record; its gradient goes to
+    `depths`, and from there through the projection backward."""
+
+    @staticmethod
+    def forward(ctx, means2d, conics, colors, opacities, depths, backgrounds, width, height, offsets, flatten_ids,
+                absgrad, packed_splat, depth):
+        Cn, N = means2d.shape[0], means2d.shape[1]
+        dev = means2d.device
+        D = colors.shape[-1] if colors is not None else 0
+        colors_c = colors.contiguous() if colors is not None else None
+        bg = backgrounds.contiguous() if backgrounds is not None else None
+        render = torch.empty(Cn, height, width, D + int(depth), device=dev)
+        alphas = torch.empty(Cn, height, width, 1, device=dev)
+        last_ids = torch.empty(Cn, height, width, dtype=torch.int32, device=dev)
+        per_cam = int(colors_c is not None and colors_c.dim() == 3)
+        call("eg_composite_fwd_modes_cams", Cn, ptr(packed_splat), N, ptr(colors_c), per_cam, D, int(depth), ptr(bg),
+             ptr(offsets), ptr(flatten_ids), width, height, ptr(render), ptr(alphas), ptr(last_ids), stream())
+        ctx.save_for_backward(means2d, packed_splat, colors_c, bg, alphas, last_ids, offsets, flatten_ids)
+        ctx.cfg = (width, height, absgrad, depth, D, per_cam)
+        ctx.mark_non_differentiable(last_ids)
+        return render, alphas, last_ids
+
+    @staticmethod
+    def backward(ctx, v_render, v_alphas, _v_last):
+        width, height, absgrad, depth, D, per_cam = ctx.cfg
+        means2d, splat, colors, bg, alphas, last_ids, offsets, flatten_ids = ctx.saved_tensors
+        Cn, N = means2d.shape[0], means2d.shape[1]
+        dev = means2d.device
+        v_render = v_render.contiguous()
+        v_alphas = v_alphas.contiguous()
+        g2d = torch.zeros(Cn, N, 8, device=dev)
+        v_colors = torch.zeros(Cn, N, D, device=dev) if (D > 0 and ctx.needs_input_grad[2]) else None
+        v_depths = torch.zeros(Cn, N, device=dev) if depth else None
+        call("eg_composite_bwd_modes_cams", Cn, ptr(splat), N, ptr(colors), per_cam, D, int(depth), ptr(bg), ptr(offsets),
+             ptr(flatten_ids), width, height, ptr(alphas), ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(g2d),
+             ptr(v_colors), ptr(v_depths), stream())
+        if v_colors is not None and not per_cam:
+            v_colors = v_colors.sum(0)
+        v_bg = None
+        if bg is not None and ctx.needs_input_grad[5]:  # (gsplat computes it in torch the same way)
+            v_bg = (v_render[..., :D] * (1.0 - alphas)).sum((1, 2))
+        if absgrad:
+            means2d.absgrad = g2d[..., 2:4].contiguous()
+        return (g2d[..., 0:2].contiguous(), g2d[..., 4:7].contiguous(), v_colors, g2d[..., 7].contiguous(), v_depths, v_bg,
+                None, None, None, None, None, None, None)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Fast path for the reference's exact call pattern (edge_gs.py:247-279): one camera, colours == 1 without grad.
 # ONE autograd node over the kernels of the training step (segmented binning with tight tile boxes -> per-tile sort ->
@@ -589,6 +639,50 @@ def isect_tiles_and_sort_cams(means2d: Tensor, radii: Tensor, depths: Tensor, co
             [item_offsets[c] for c in range(Cn)], [total[c] for c in range(Cn)], n_items, extra)
 
 
+RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
+
+
+def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
+                        radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased):
+    """`rasterization` with a depth channel and / or backgrounds: the general two-node path (projection -> compositing)
+    with the compositing of eg_composite_{fwd,bwd}_modes_cams, which takes `depths` as an input."""
+    N, Cn = means.shape[0], viewmats.shape[0]
+    depth = render_mode != "RGB"
+    if render_mode in ("D", "ED"):
+        colors, backgrounds = None, None  # (gsplat: the depth is the only channel, its background is 0)
+    radii, means2d, depths, conics, comps, tpg, counts, _splat = _Projection.apply(
+        means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
+        float(near_plane), float(far_plane), float(radius_clip), antialiased)
+    opac = opacities[None, :].expand(Cn, N)
+    if antialiased:
+        opac = opac * comps
+    tw, th = math.ceil(width / TILE), math.ceil(height / TILE)
+    tile_bits = int(math.floor(math.log2(tw * th))) + 1
+    with torch.no_grad():
+        o_l, f_l, i_l, Ms = isect_tiles_and_sort_cams(means2d.contiguous(), radii, depths.contiguous(), counts, width,
+                                                      height)[:4]
+        offsets = torch.stack(o_l)  # [C, T+1], each row local to its camera's list
+        flat = torch.cat(f_l) if sum(Ms) > 0 else torch.zeros(1, dtype=torch.int32, device=means.device)
+        bases = [sum(Ms[:c]) for c in range(Cn)]
+        binfo = {"isect_ids": torch.cat([i_l[c] | (c << (32 + tile_bits)) for c in range(Cn)]),
+                 "flatten_ids": torch.cat([f_l[c] + c * N for c in range(Cn)]),
+                 "isect_offsets": torch.stack([(o_l[c][:-1] + bases[c]).reshape(th, tw) for c in range(Cn)])}
+    render, alphas, last_ids = _ModeCompositing.apply(
+        means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+        bool(absgrad), _splat, depth)
+    if render_mode in ("ED", "RGB+ED"):
+        render = torch.cat([render[..., :-1], render[..., -1:] / alphas.clamp(min=1e-10)], dim=-1)
+    info = {
+        "camera_ids": None, "gaussian_ids": None,
+        "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
+        "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
+        **binfo,
+        "width": width, "height": height, "tile_size": TILE, "n_cameras": Cn,
+        "last_ids": last_ids,
+    }
+    return render, alphas, info
+
+
 def rasterization(
     means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor, colors: Tensor,
     viewmats: Tensor, Ks: Tensor, width: int, height: int,
@@ -597,9 +691,16 @@ def rasterization(
     backgrounds: Optional[Tensor] = None, render_mode: str = "RGB", sparse_grad: bool = False,
     absgrad: bool = False, rasterize_mode: str = "classic", channel_chunk: int = 32,
 ) -> Tuple[Tensor, Tensor, Dict]:
-    """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``; supports the
-    subset the reference reaches (edge_gs.py:250-268): packed=False, sh_degree=None,
-    backgrounds=None, render_mode='RGB', tile_size=16, colours of 1 or 3 channels."""
+    """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``, for packed=False,
+    sh_degree=None, tile_size=16 and colours of 1 or 3 channels (the reference's call, edge_gs.py:250-268, is
+    render_mode='RGB' without backgrounds).
+
+    ``render_mode``: "RGB", "D", "ED", "RGB+D" or "RGB+ED", as in gsplat: the "+D" modes append the projection depth
+    as one more channel (``render`` [C,H,W,D+1]), "D" / "ED" render the depth alone ([C,H,W,1], ``colors`` unused), and
+    the "ED" modes divide that channel by ``alphas.clamp(min=1e-10)``.  ``backgrounds`` [C,D] (fp32, on the device)
+    is added under the final transmittance of the colour channels (the depth channel's background is 0; the depth-only
+    modes ignore it) and receives a gradient when it requires one.  The depth channel's gradient reaches ``means``,
+    ``quats`` and ``scales`` through ``info["depths"]``."""
     N = means.shape[0]
     Cn = viewmats.shape[0]
     _check(means, (N, 3), "means")
@@ -608,10 +709,10 @@ def rasterization(
     _check(opacities, (N,), "opacities")
     _check(viewmats, (Cn, 4, 4), "viewmats")
     _check(Ks, (Cn, 3, 3), "Ks")
-    if render_mode != "RGB":
-        raise NotImplementedError("render_mode other than 'RGB' is outside the reference's path")
-    if sh_degree is not None or backgrounds is not None:
-        raise NotImplementedError("sh_degree / backgrounds are outside the reference's path")
+    if render_mode not in RENDER_MODES:
+        raise ValueError(f"Unknown render_mode: {render_mode}")
+    if sh_degree is not None:
+        raise NotImplementedError("sh_degree is outside the reference's path")
     if packed or sparse_grad:
         raise NotImplementedError("packed / sparse_grad are outside the reference's path (edge_gs.py:261,265)")
     if tile_size != TILE:
@@ -625,8 +726,13 @@ def rasterization(
     D = colors.shape[-1]
     if D not in (1, 3):
         raise NotImplementedError("colors must have 1 or 3 channels")
+    if backgrounds is not None:
+        _check(backgrounds, (Cn, D), "backgrounds")
     width, height = int(width), int(height)
     antialiased = rasterize_mode == "antialiased"
+    if render_mode != "RGB" or backgrounds is not None:
+        return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
+                                   far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased)
 
     if (Cn == 1 and colors.dim() == 2 and not colors.requires_grad and float(eps2d) == 0.3 and float(near_plane) == 0.01
             and float(far_plane) == 1e10 and float(radius_clip) == 0.0 and N > 0 and _FAST_ENABLED):

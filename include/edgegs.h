@@ -564,6 +564,35 @@ int eg_composite_fwd_cams(int32_t C, const float *splat /*[C,N,8]*/, int32_t N, 
 int eg_composite_bwd_footprint_cams(const float *splat /*[C,N,8]*/, int32_t N, int32_t C, int32_t width, int32_t height,
                                     const float *gtstop /*[C,H,W,3]*/, float *g2d /*[C,N,8]*/, eg_stream_t stream);
 
+/* ---- gsplat's render modes and backgrounds (rasterization(render_mode="D" | "ED" | "RGB+D" | "RGB+ED", backgrounds=...))
+ * for C cameras, one launch each way (gridDim.y = camera) of the classic one-workgroup-per-tile kernels.  A rendered pixel
+ * holds the `channels` colour channels (0, 1 or 3) and then, with depth != 0, the depth channel: the projection depth of
+ * each Gaussian (word 6 of its splat record) composited like a colour.  channels == 0 (depth only) needs depth != 0;
+ * with channels > 0, colors is required ([N, channels], or [C, N, channels] with colors_per_camera != 0): unlike
+ * eg_composite_fwd, NULL does not mean unit colours.  backgrounds [C, channels] or NULL: pix[k] += T_final * bg[k] on
+ * the colour channels (the depth channel's background is 0; ignored when channels == 0).  At least one of depth /
+ * backgrounds is given (otherwise the call is eg_composite_fwd_cams).  offsets [C, T+1]: row c is camera c's scan,
+ * local to its own list; flatten_ids: the C cameras' sorted lists one after the other (camera c's starts at the sum of
+ * offsets[c'][T] over c' < c).  render [C, H, W, channels + (depth != 0)], alphas / last_ids [C, H, W] (last_ids local to
+ * the camera's list, as eg_composite_fwd_cams writes them).
+ * The backward takes the forward's alphas / last_ids and v_render [C, H, W, channels + (depth != 0)], v_alphas
+ * [C, H, W] or NULL; it ACCUMULATES with float atomics into g2d [C, N, 8] (the layout of eg_composite_fwd's splat-side
+ * record: v_means2d, |v_means2d|, v_conics, v_opacities), v_colors [C, N, channels] or NULL, and, with depth != 0,
+ * v_depths [C, N] (dL/d(projection depth), for eg_project_bwd_cams): the caller zeroes them.  The background's own
+ * gradient sum_pixels v_render * (1 - alpha) is left to the caller. */
+int eg_composite_fwd_modes_cams(int32_t C, const float *splat /*[C,N,8]*/, int32_t N, const float *colors,
+                                int32_t colors_per_camera, int32_t channels, int32_t depth,
+                                const float *backgrounds /*[C,channels] or NULL*/, const int32_t *offsets /*[C,T+1]*/,
+                                const int32_t *flatten_ids, int32_t width, int32_t height, float *render, float *alphas,
+                                int32_t *last_ids, eg_stream_t stream);
+int eg_composite_bwd_modes_cams(int32_t C, const float *splat /*[C,N,8]*/, int32_t N, const float *colors,
+                                int32_t colors_per_camera, int32_t channels, int32_t depth,
+                                const float *backgrounds /*[C,channels] or NULL*/, const int32_t *offsets /*[C,T+1]*/,
+                                const int32_t *flatten_ids, int32_t width, int32_t height, const float *alphas,
+                                const int32_t *last_ids, const float *v_render, const float *v_alphas /*or NULL*/,
+                                float *g2d /*[C,N,8]*/, float *v_colors /*[C,N,channels] or NULL*/,
+                                float *v_depths /*[C,N], with depth*/, eg_stream_t stream);
+
 /* ---- the drop-in operator's fast path in two calls (edgegaussians_amd/rasterizer.py: the reference's own call of
  * gsplat.rasterization -- one camera, colours == 1 without grad, edge_gs.py:247-279 -- and its autograd backward).
  * eg_operator_fwd: projection + exact tile binning -> per-tile sort -> the training step's wave-autonomous forward in its
