@@ -9,6 +9,8 @@
 // shells of cells with a K-best list in registers; the search stops when the K-th distance is inside
 // the scanned block.  Exact (not approximate) neighbours.
 // The two losses are streaming per-Gaussian kernels that produce value and gradient in one pass.
+#include <algorithm>
+
 #include "common.h"
 
 namespace eg {
@@ -366,6 +368,186 @@ knn_wave_kernel(const float *__restrict__ pts, int N, int K, int *__restrict__ o
 }
 
 // ---------------------------------------------------------------------------------------------
+// Cross-set nearest neighbour (eg_nn_query_small / eg_nn_query_auto): for each of Q queries the nearest of M targets --
+// the queries are NOT among the targets, self is not excluded.  The role layout of the searches above with K = 1: a
+// lane holds a candidate, a wavefront owns a few queries (coordinates wave-uniform), and the "list" is one running
+// minimum per lane over the 64-bit key (bits of d2) << 32 | target index -- d2 >= +0, so its bit pattern orders like
+// the float, and among equal d2 the lowest index wins -- folded over the wave by a DPP reduction when the wave needs
+// it.  No ballot, no insertion, no LDS, no atomics: sub x 3, mul, fma x 2, one 64-bit compare, two selects per
+// (query, 64 candidates).
+constexpr unsigned long long kNoKey = ~0ull;
+
+__device__ __forceinline__ unsigned long long nn_key(float d2, int j) {
+  return ((unsigned long long)(unsigned)__float_as_int(d2) << 32) | (unsigned)j;
+}
+
+// minimum of the key over the wave, in every lane (the six DPP steps of wave_scan_dpp on both halves of the key; lanes
+// a shift leaves without a source read the identity)
+__device__ __forceinline__ unsigned long long wave_min_key(unsigned long long k) {
+#define EG_KEY_STEP(ctrl, rmask)                                                                            \
+  {                                                                                                         \
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(k >> 32), ctrl, rmask, 0xf, false); \
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)k, ctrl, rmask, 0xf, false);         \
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;                                       \
+    k = o < k ? o : k;                                                                                      \
+  }
+  EG_KEY_STEP(0x111, 0xf);  // row_shr:1
+  EG_KEY_STEP(0x112, 0xf);  // row_shr:2
+  EG_KEY_STEP(0x114, 0xf);  // row_shr:4
+  EG_KEY_STEP(0x118, 0xf);  // row_shr:8
+  EG_KEY_STEP(0x142, 0xa);  // row_bcast:15 -> rows 1 and 3
+  EG_KEY_STEP(0x143, 0xc);  // row_bcast:31 -> rows 2 and 3
+#undef EG_KEY_STEP
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(k >> 32), 63);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)k, 63);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// Exhaustive: every wavefront streams ALL targets, 64 per round (the next round's in flight), against its NQ queries.
+template <int NQ>
+__global__ void __launch_bounds__(256)
+nn_query_wave_kernel(const float *__restrict__ qs, int Q, const float *__restrict__ ts, int M,
+                     int *__restrict__ out_idx, float *__restrict__ out_d2) {
+  const int lane = threadIdx.x & 63;
+  const int q0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 4 + (threadIdx.x >> 6)) * NQ);
+  if (q0 >= Q) return;
+  float qx[NQ], qy[NQ], qz[NQ];
+  unsigned long long best[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const size_t qi = (size_t)min(q0 + q, Q - 1);
+    qx[q] = qs[3 * qi]; qy[q] = qs[3 * qi + 1]; qz[q] = qs[3 * qi + 2];
+    best[q] = kNoKey;
+  }
+  size_t cn = (size_t)min(lane, M - 1);
+  float cx = ts[3 * cn], cy = ts[3 * cn + 1], cz = ts[3 * cn + 2];
+  for (int c0 = 0; c0 < M; c0 += 64) {
+    const int c = c0 + lane;
+    const float x = cx, y = cy, z = cz;
+    cn = (size_t)min(c + 64, M - 1);  // (c + 64 <= M + 126: no overflow for M <= 2^29)
+    cx = ts[3 * cn]; cy = ts[3 * cn + 1]; cz = ts[3 * cn + 2];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const unsigned long long k = c < M ? nn_key(dist2(qx[q] - x, qy[q] - y, qz[q] - z), c) : kNoKey;
+      best[q] = k < best[q] ? k : best[q];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const unsigned long long k = wave_min_key(best[q]);
+    if (lane == q && q0 + q < Q) {
+      out_idx[q0 + q] = (int)(unsigned)k;
+      out_d2[q0 + q] = __int_as_float((int)(k >> 32));
+    }
+  }
+}
+
+// Grid: the targets AND the queries are counting-sorted by the cell of the targets' grid (a query outside the box is
+// clamped into a boundary cell), so that consecutive wavefronts walk the same cells.  A wavefront answers NQ
+// cell-ordered queries one after the other: the 3 x 3 x 3 block round the query's cell first, rows dealt to groups of
+// lanes as in knn_grid_wave_kernel.  The block [x0,x1] x [y0,y1] x [z0,z1] settles the query when its best d2 is within
+// the squared distance from the query's REAL position to the nearest face of the block that is not a face of the grid
+// (no target lies beyond the grid) -- measured in cell units with the expression cell_of_point sorted the targets by,
+// less a slack for its rounding.  Measured from the clamped cell instead, an outside query would stop at a target of
+// its boundary cell although a nearer one sits a few cells along the face.  Unsettled with a candidate known: ONE more
+// block, the cells the ball of that radius round the real position touches; nothing found yet: the cube doubles.  A
+// block of more rows than the exhaustive scan costs (or a fourth block) -> all records, 64 at a time.
+constexpr int kNNQueryBlocks = 4;
+constexpr float kNNGapSlack = 1e-6f;  // ~16 ulp of the cell coordinate: (x - ox) * inv_cell rounds twice
+
+__device__ __forceinline__ int clamp_cell(float f, int n) {
+  return (int)fminf(fmaxf(floorf(f), 0.f), (float)(n - 1));  // (clamped as a float: no out-of-range conversion)
+}
+
+template <int NQ>
+__global__ void __launch_bounds__(256)
+nn_query_grid_kernel(int Q, int M, const Grid *__restrict__ gp, const int *__restrict__ cell_start,
+                     const float4 *__restrict__ tsorted, const float4 *__restrict__ qsorted, int *__restrict__ out_idx,
+                     float *__restrict__ out_d2, int brute_rows) {
+  const Grid g = *gp;
+  const int lane = threadIdx.x & 63;
+  const int q0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 4 + (threadIdx.x >> 6)) * NQ);
+  for (int q = 0; q < NQ && q0 + q < Q; ++q) {
+    const float4 me = qsorted[q0 + q];  // (the same address in every lane)
+    const float fx = (me.x - g.ox) * g.inv_cell, fy = (me.y - g.oy) * g.inv_cell, fz = (me.z - g.oz) * g.inv_cell;
+    const int cx = clamp_cell(fx, g.nx), cy = clamp_cell(fy, g.ny), cz = clamp_cell(fz, g.nz);
+    const float slack = kNNGapSlack * (fmaxf(fmaxf(fabsf(fx), fabsf(fy)), fabsf(fz)) + (float)g.nx);
+    int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.nx - 1);
+    int y0 = max(cy - 1, 0), y1 = min(cy + 1, g.ny - 1);
+    int z0 = max(cz - 1, 0), z1 = min(cz + 1, g.nz - 1);
+    unsigned long long best = kNoKey;
+    bool settled = false;
+    for (int it = 0; it < kNNQueryBlocks; ++it) {
+      const int ny = y1 - y0 + 1, nrows = ny * (z1 - z0 + 1);
+      if (nrows > brute_rows) break;
+      // rows per round and lanes per row: up to 9 rows get 7 lanes each, more 4 lanes x 16 rows at a time
+      const int G = (nrows <= 9) ? 9 : 16, LPR = (nrows <= 9) ? 7 : 4;
+      const int rho = (nrows <= 9) ? (lane * 37) >> 8 : lane >> 2;  // lane / LPR (exact for lane < 64)
+      const int u = lane - rho * LPR;
+      for (int row0 = 0; row0 < nrows; row0 += G) {
+        int s = 0, e = 0;
+        const int rr = row0 + rho;
+        if (rho < G && rr < nrows) {
+          const int zz = rr / ny, yy = rr - zz * ny;
+          const int row = ((z0 + zz) * g.ny + (y0 + yy)) * g.nx;
+          s = cell_start[row + x0];
+          e = cell_start[row + x1 + 1];
+        }
+        const int longest = __builtin_amdgcn_readlane(wave_scan_dpp(e - s, 0, OpMaxI()), 63);
+        float4 c4 = tsorted[min(s + u, M - 1)];
+        for (int k = u; k < longest + u; k += LPR) {  // (uniform trip count: `longest` is)
+          const float4 cur = c4;
+          const int idx = s + k;
+          c4 = tsorted[min(idx + LPR, M - 1)];  // the next round's candidate is in flight
+          const unsigned long long key =
+              idx < e ? nn_key(dist2(me.x - cur.x, me.y - cur.y, me.z - cur.z), __float_as_int(cur.w)) : kNoKey;
+          best = key < best ? key : best;
+        }
+      }
+      best = wave_min_key(best);
+      float gap = 3.0e38f;  // to the nearest face of the block that has cells behind it, in cells
+      if (x0 > 0) gap = fminf(gap, fx - (float)x0);
+      if (x1 < g.nx - 1) gap = fminf(gap, (float)(x1 + 1) - fx);
+      if (y0 > 0) gap = fminf(gap, fy - (float)y0);
+      if (y1 < g.ny - 1) gap = fminf(gap, (float)(y1 + 1) - fy);
+      if (z0 > 0) gap = fminf(gap, fz - (float)z0);
+      if (z1 < g.nz - 1) gap = fminf(gap, (float)(z1 + 1) - fz);
+      const float bd = __int_as_float((int)(best >> 32));  // (NaN pattern while nothing is found: compares false)
+      const float reach = (gap - slack) * g.cell;
+      settled = gap > 1.0e38f || (best != kNoKey && reach > 0.f && bd <= reach * reach * 0.999998f);
+      if (settled) break;
+      if (best != kNoKey && bd < 3.0e38f) {
+        const float rad = sqrtf(bd) * g.inv_cell * 1.00001f + 2.f * slack;
+        x0 = clamp_cell(fx - rad, g.nx); x1 = clamp_cell(fx + rad, g.nx);
+        y0 = clamp_cell(fy - rad, g.ny); y1 = clamp_cell(fy + rad, g.ny);
+        z0 = clamp_cell(fz - rad, g.nz); z1 = clamp_cell(fz + rad, g.nz);
+      } else {
+        const int r = 2 << it;
+        x0 = max(cx - r, 0); x1 = min(cx + r, g.nx - 1);
+        y0 = max(cy - r, 0); y1 = min(cy + r, g.ny - 1);
+        z0 = max(cz - r, 0); z1 = min(cz + r, g.nz - 1);
+      }
+    }
+    if (!settled) {  // far from everything, or a ball that covers much of the grid: all records, 64 at a time
+      float4 c4 = tsorted[min(lane, M - 1)];
+      for (int s0 = 0; s0 < M; s0 += 64) {
+        const float4 cur = c4;
+        c4 = tsorted[min(s0 + 64 + lane, M - 1)];
+        const unsigned long long key =
+            s0 + lane < M ? nn_key(dist2(me.x - cur.x, me.y - cur.y, me.z - cur.z), __float_as_int(cur.w)) : kNoKey;
+        best = key < best ? key : best;
+      }
+      best = wave_min_key(best);
+    }
+    if (lane == 0) {
+      const int i = __float_as_int(me.w);
+      out_idx[i] = (int)(unsigned)best;
+      out_d2[i] = __int_as_float((int)(best >> 32));
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // direction loss (edge_gs.py:346-373): 1 - mean_i mean_k | m_i . unit(mu_i - mu_nn(i,k)) |
 // with m_i = column argmax_k(scale) of R(q_i).  One thread per Gaussian: value (sum of alignments, the
 // caller forms 1 - sum / (N k)) and UNSCALED gradients d(sum)/d{mu, q} (the caller multiplies by
@@ -581,7 +763,23 @@ ratio_loss_kernel(const float *__restrict__ log_scales, int N, float *__restrict
 
 using namespace eg;
 
-// count -> scan -> scatter (points in cell order) -> wave-cooperative query; grid by value (host) or by pointer (device)
+// count -> chained scan -> scatter: `points` in cell order (x y z index) in `sorted`, the cells' first records in
+// cell_start.  Grid by value (host) or by pointer (device); cell_counts is zero on entry and on exit.  `carry`: the chain
+// words of the scan (8 bytes per scan workgroup, `carry_bytes` available), free to be overwritten afterwards.
+static int sort_by_cell(const float *points, int32_t N, const Grid &g, const Grid *gp, int C, int32_t *cell_of,
+                        int32_t *cell_counts, int32_t *cell_start, float *sorted, void *carry, int64_t carry_bytes,
+                        hipStream_t st) {
+  const int scan_blocks = cdiv(C + 1, 256 * kScanPer);
+  EG_REQUIRE((int64_t)scan_blocks * 8 <= carry_bytes, "grid too fine for the number of points");
+  knn_count_kernel<<<cdiv(N, 256), 256, 0, st>>>(points, N, g, gp, cell_of, cell_counts);
+  if (hipMemsetAsync(carry, 0, sizeof(unsigned long long) * scan_blocks, st) != hipSuccess)
+    return check_launch("knn scan memset");
+  knn_scan_kernel<<<scan_blocks, 256, 0, st>>>(cell_counts, C, cell_start, (unsigned long long *)carry);
+  knn_scatter_kernel<<<cdiv(N, 256), 256, 0, st>>>(points, cell_of, N, cell_start, cell_counts, (float4 *)sorted);
+  return EG_OK;
+}
+
+// counting sort (points in cell order) -> wave-cooperative query; grid by value (host) or by pointer (device)
 static int knn_grid_search(const float *points, int32_t N, int32_t K, const Grid &g, const Grid *gp, int C,
                            int32_t *cell_of, int32_t *cell_counts, int32_t *cell_start, float *sorted,
                            int32_t *out_idx, float *out_d2, eg_stream_t stream, float *kth = nullptr,
@@ -591,14 +789,9 @@ static int knn_grid_search(const float *points, int32_t N, int32_t K, const Grid
   // beyond this radius the scan is the cheaper way to settle an outlier
   int r_brute = 1;
   while ((2 * (2 * r_brute) + 1) * (2 * (2 * r_brute) + 1) * 15 < N) r_brute *= 2;
-  knn_count_kernel<<<cdiv(N, 256), 256, 0, st>>>(points, N, g, gp, cell_of, cell_counts);
   // (the chain words of the scan live at the head of `sorted`, which the scatter kernel fills afterwards)
-  const int scan_blocks = cdiv(C + 1, 256 * kScanPer);
-  EG_REQUIRE((int64_t)scan_blocks * 8 <= (int64_t)N * 16, "grid too fine for the number of points");
-  if (hipMemsetAsync(sorted, 0, sizeof(unsigned long long) * scan_blocks, st) != hipSuccess)
-    return check_launch("knn scan memset");
-  knn_scan_kernel<<<scan_blocks, 256, 0, st>>>(cell_counts, C, cell_start, (unsigned long long *)sorted);
-  knn_scatter_kernel<<<cdiv(N, 256), 256, 0, st>>>(points, cell_of, N, cell_start, cell_counts, (float4 *)sorted);
+  const int rc = sort_by_cell(points, N, g, gp, C, cell_of, cell_counts, cell_start, sorted, sorted, (int64_t)N * 16, st);
+  if (rc) return rc;
   knn_grid_wave_kernel<4><<<cdiv(N, 16), 256, 0, st>>>(N, K, g, gp, cell_start, (const float4 *)sorted, out_idx, out_d2,
                                                        r_brute, kth, kth_slack);
   return check_launch("knn");
@@ -666,6 +859,57 @@ extern "C" int eg_knn_small(const float *points, int32_t N, int32_t K, int32_t *
   else
     knn_wave_kernel<2><<<cdiv(N, 8), 256, 0, st>>>(points, N, K, out_idx, out_d2);
   return check_launch("knn_small");
+}
+
+// queries and targets are indexed with 32-bit integers (3 i and 4 i included)
+constexpr int64_t kNNQueryMaxPoints = 1ll << 29;
+
+extern "C" int eg_nn_query_small(const float *queries, int64_t Q, const float *targets, int64_t M, int32_t *out_idx,
+                                 float *out_d2, eg_stream_t stream) {
+  EG_REQUIRE(Q >= 0 && M >= 1, "bad sizes (Q >= 0, M >= 1)");
+  EG_REQUIRE(Q <= kNNQueryMaxPoints && M <= kNNQueryMaxPoints, "Q, M <= 2^29 (32-bit indices)");
+  if (Q == 0) return EG_OK;
+  EG_REQUIRE(queries && targets && out_idx && out_d2, "null pointer");
+  EG_REQUIRE(Q * M <= (1ll << 40), "Q * M <= 2^40 pairs (use the grid search, eg_nn_query_auto)");
+  hipStream_t st = as_stream(stream);
+  // queries per wave: more of them amortise the candidate stream, fewer give the chip more waves
+  if (Q >= 16384)
+    nn_query_wave_kernel<8><<<cdiv(Q, 32), 256, 0, st>>>(queries, (int)Q, targets, (int)M, out_idx, out_d2);
+  else if (Q >= 4096)
+    nn_query_wave_kernel<4><<<cdiv(Q, 16), 256, 0, st>>>(queries, (int)Q, targets, (int)M, out_idx, out_d2);
+  else
+    nn_query_wave_kernel<2><<<cdiv(Q, 8), 256, 0, st>>>(queries, (int)Q, targets, (int)M, out_idx, out_d2);
+  return check_launch("nn_query_small");
+}
+
+extern "C" int eg_nn_query_auto(const float *queries, int64_t Q, const float *targets, int64_t M, int32_t *cell_of,
+                                int32_t *cell_counts, int32_t *cell_start, float *sorted_targets, float *sorted_queries,
+                                void *grid_scratch, int32_t *out_idx, float *out_d2, eg_stream_t stream) {
+  EG_REQUIRE(Q >= 0 && M >= 1, "bad sizes (Q >= 0, M >= 1)");
+  EG_REQUIRE(Q <= kNNQueryMaxPoints && M <= kNNQueryMaxPoints, "Q, M <= 2^29 (32-bit indices)");
+  if (Q == 0) return EG_OK;
+  EG_REQUIRE(queries && targets && cell_of && cell_counts && cell_start && sorted_targets && sorted_queries &&
+                 grid_scratch && out_idx && out_d2, "null pointer");
+  const int D = eg_knn_auto_dims((int32_t)M, 1), C = D * D * D;
+  hipStream_t st = as_stream(stream);
+  unsigned *mm = (unsigned *)grid_scratch;  // 6 extrema + ticket (all zero between calls)
+  Grid *gp = (Grid *)(mm + 8);
+  knn_bbox_kernel<<<min(cdiv(M, 2048), 128), 256, 0, st>>>(targets, (int)M, mm, D, gp);
+  Grid g = {};
+  g.nx = g.ny = g.nz = D;  // (only the pointer's copy is read by the kernels)
+  // the queries first: cell_of, cell_counts (back to zero) and cell_start are then free for the targets, and the chain
+  // words of both scans live at the head of sorted_targets, which the targets' scatter fills last (C + 1 <= 2 M + 8)
+  int rc = sort_by_cell(queries, (int)Q, g, gp, C, cell_of, cell_counts, cell_start, sorted_queries, sorted_targets,
+                        M * 16, st);
+  if (rc) return rc;
+  rc = sort_by_cell(targets, (int)M, g, gp, C, cell_of, cell_counts, cell_start, sorted_targets, sorted_targets, M * 16,
+                    st);
+  if (rc) return rc;
+  // a block of R rows costs ~R / 16 rounds of row look-ups, the exhaustive scan M / 64 rounds of candidates
+  const int brute_rows = (int)std::max<int64_t>(27, M / 16);
+  nn_query_grid_kernel<4><<<cdiv(Q, 16), 256, 0, st>>>((int)Q, (int)M, gp, cell_start, (const float4 *)sorted_targets,
+                                                       (const float4 *)sorted_queries, out_idx, out_d2, brute_rows);
+  return check_launch("nn_query_auto");
 }
 
 extern "C" int eg_direction_loss(const float *means, const float *quats, const float *log_scales,

@@ -4,10 +4,11 @@ Host-side mirror of `/root/reference/edgegaussians/edge_extraction/filtering.py`
     filter_by_projection   :80-123   -> eg_project_visibility (one N x V kernel instead of a V-iteration
                                         numpy loop with a Python list round trip per view)
     filter_by_opacity      :71-77    -> one comparison
-`filter_stat_outliers` (:59-69) is Open3D's statistical outlier removal; it is outside SURVEY 8 and is
-not provided here.
+    filter_stat_outliers   :59-69    -> the existing exact kNN (eg_knn_small / eg_knn_auto) + a few reductions;
+                                        the reference calls Open3D's remove_statistical_outlier
 
-Same argument meaning and return value as the reference: a boolean inlier mask of shape [N].
+Same argument meaning and return value as the reference: a boolean inlier mask of shape [N] from the first two, the
+ascending int64 INDICES of the inliers from `filter_stat_outliers` (the reference applies it first, fit_edges.py:20-45).
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 from ._lib import call, ptr, stream
+from .regularizers import knn
 
 
 def pack_cameras(cameras: Sequence[Dict], device) -> torch.Tensor:
@@ -47,3 +49,40 @@ def filter_by_projection(gaussian_means, edge_images, cameras: Sequence[Dict], v
 def filter_by_opacity(opacities, min_opacity: float) -> np.ndarray:
     """filtering.py:71-77."""
     return (np.asarray(opacities) > min_opacity).reshape(-1)
+
+
+def filter_stat_outliers(means, num_nn: int = 10, std_multiplier: float = 3.0) -> np.ndarray:
+    """filtering.py:59-69: statistical outlier removal, the ascending int64 indices of the inliers.
+
+    `means`: float32 [N,3] DEVICE tensor (there is no CPU path).  The semantics are those of Open3D 0.18's
+    `PointCloud::RemoveStatisticalOutliers`, RESTATED from knowledge of its public source: Open3D is not a dependency
+    of this package and the restatement could not be pinned against it (tests compare with a float64 restatement of
+    the same formulas):
+        avg_i     = mean of the distances (not squared) from point i to its num_nn nearest points, i itself among them
+                    at distance 0: the num_nn - 1 nearest others, summed and divided by num_nn (by the number that
+                    exist when the cloud has fewer than num_nn points)
+        mean, std = over all avg_i, std with the N - 1 divisor
+        inlier    iff avg_i > 0 and avg_i < mean + std_multiplier * std
+    The neighbours come from `regularizers.knn` (exact, num_nn - 1 <= 32); mean / std / threshold are float64."""
+    if not isinstance(means, torch.Tensor) or not means.is_cuda:
+        dev = means.device if isinstance(means, torch.Tensor) else type(means).__name__
+        raise ValueError(f"means must be a device tensor (got {dev}); edgegaussians_amd has no CPU path")
+    if means.dtype != torch.float32:
+        raise TypeError(f"means must be {torch.float32}, got {means.dtype}")
+    if means.dim() != 2 or means.shape[1] != 3:
+        raise ValueError(f"means must have shape (n, 3), got {tuple(means.shape)}")
+    if not 2 <= num_nn <= 33:
+        raise ValueError(f"num_nn must be in [2, 33] (the kNN kernels list up to 32 other points), got {num_nn}")
+    if std_multiplier <= 0:
+        raise ValueError("std_multiplier must be positive")
+    N = means.shape[0]
+    if N == 0:
+        return np.zeros(0, dtype=np.int64)
+    idx, dist = knn(means, num_nn - 1, want_dist=True)
+    found = idx >= 0  # (a cloud of fewer than num_nn points: the missing neighbours are listed as -1)
+    total = torch.where(found, dist, torch.zeros_like(dist)).double().sum(dim=1)
+    avg = total / (found.sum(dim=1) + 1).double()
+    mean = avg.mean()
+    std = ((avg - mean) ** 2).sum().div(max(N - 1, 1)).sqrt()
+    keep = (avg > 0) & (avg < mean + std_multiplier * std)
+    return torch.nonzero(keep).view(-1).cpu().numpy().astype(np.int64)

@@ -352,6 +352,26 @@ int eg_knn_auto(const float *points /*[N,3]*/, int32_t N, int32_t K, int32_t *ce
  * ~5 * 10^3 points; fastest when the rows are in spatial order (the scan starts at the queries' own rows). */
 int eg_knn_small(const float *points /*[N,3]*/, int32_t N, int32_t K, int32_t *out_idx /*[N,K]*/,
                  float *out_d2 /*[N,K] or NULL*/, eg_stream_t stream);
+/* ---- Cross-set nearest neighbour: for each of Q query points the nearest of M target points (the metrics of
+ * eval_utils.py:400-509 -- accuracy / completeness / precision / recall -- and any pred <-> gt matching).  The queries
+ * are a different set from the targets: self is NOT excluded (queries == targets finds every point itself, or a
+ * lower-indexed duplicate, at distance 0).  d2 = fma(ez, ez, fma(ey, ey, ex * ex)), e = q - t, in fp32; candidates are
+ * ordered by (d2, target index): among equal d2 the lowest index wins.  Both entries return the same bits.  Q >= 0,
+ * M >= 1, both <= 2^29; Q == 0 launches nothing.
+ * eg_nn_query_small: exhaustive, ONE launch, no scratch (Q * M <= 2^40).  A lane holds a candidate, a wavefront owns a
+ * few queries; the running minimum over the (d2, index) key lives in the lanes and is folded by a DPP reduction. */
+int eg_nn_query_small(const float *queries /*[Q,3]*/, int64_t Q, const float *targets /*[M,3]*/, int64_t M,
+                      int32_t *out_idx /*[Q]*/, float *out_d2 /*[Q] squared distances*/, eg_stream_t stream);
+/* eg_nn_query_auto: the same result on a uniform grid over the TARGETS chosen on the device as eg_knn_auto does
+ * (bounding-box reduction, D = eg_knn_auto_dims(M, 1)) -- no host sync; queries may lie anywhere (outside the box they
+ * are clamped into a boundary cell for the walk, the stopping test uses their real position).  Targets and queries are
+ * counting-sorted by cell.  Scratch, sized from (Q, M) alone: cell_of[max(Q, M)], cell_counts[D^3] (zero on entry,
+ * returned to zero), cell_start[D^3 + 1], sorted_targets[M,4], sorted_queries[Q,4], grid_scratch (64 bytes, zero on
+ * entry, returned to zero). */
+int eg_nn_query_auto(const float *queries /*[Q,3]*/, int64_t Q, const float *targets /*[M,3]*/, int64_t M,
+                     int32_t *cell_of, int32_t *cell_counts, int32_t *cell_start, float *sorted_targets,
+                     float *sorted_queries, void *grid_scratch, int32_t *out_idx /*[Q]*/, float *out_d2 /*[Q]*/,
+                     eg_stream_t stream);
 /* compute_direction_loss (edge_gs.py:346-373): sum_out[0] += sum over the counted (i,k) of
  * |m_i . unit(mu_i - mu_nn(i,k))|; g_means += and g_quats = the gradient of that SUM.  top_k <= 0 or >= K:
  * every listed neighbour counts (loss = 1 - sum/(N K), the caller scales by -lambda/(N K)); 0 < top_k < K
