@@ -7,5 +7,6 @@ kunalchelani/EdgeGaussians) behind the reference's own operator surface.
 from .rasterizer import rasterization  # noqa: F401
 from .trainer import EdgeTrainer, LRSchedule, train_steps_multi  # noqa: F401
 from .train_loop import train, train_epoch  # noqa: F401
+from . import edges  # noqa: F401  (parametric edges -> points -> metrics)
 
-__all__ = ["rasterization", "EdgeTrainer", "LRSchedule", "train", "train_epoch", "train_steps_multi"]
+__all__ = ["rasterization", "EdgeTrainer", "LRSchedule", "train", "train_epoch", "train_steps_multi", "edges"]

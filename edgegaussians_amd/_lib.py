@@ -108,6 +108,9 @@ _SIGS = {
     "eg_knn_auto": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp],
     "eg_nn_query_small": [_vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "eg_nn_query_auto": [_vp, _i64, _vp, _i64] + [_vp] * 8 + [_vp],
+    "eg_edge_sample_count": [_vp, _i32, _vp, _i32, C.c_double, _i64, _vp, _vp, _vp, _vp, _vp],
+    "eg_edge_sample_emit": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp],
+    "eg_edge_sample": [_vp, _i32, _vp, _i32, C.c_double, _i64, _i32] + [_vp] * 7 + [C.POINTER(_i32), _vp],
     "eg_direction_loss": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "eg_ratio_loss": [_vp, _i32, _vp, _vp, _vp],
     "eg_regulariser_step": [_i32] + [_vp] * 7 + [_i32, _vp, _i32, _i32, _i32, _i32, _vp, _f, _f, _vp, AdamHyper, _vp],

@@ -73,3 +73,79 @@ def export_as_ply(state: Dict[str, torch.Tensor], ply_path: str) -> None:
         torch.exp(state["gauss_params.scales"]).detach().cpu().numpy(),
         state["gauss_params.quats"].detach().cpu().numpy(),
         torch.sigmoid(state["gauss_params.opacities"]).detach().cpu().numpy(), ply_path)
+
+
+# scalar property types of the PLY format (and their sized aliases) -> numpy codes without byte order
+_PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
+                "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
+                "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_points_ply(path: str) -> np.ndarray:
+    """x y z of a PLY file's `vertex` element as float64 [N,3]: ascii or binary of either byte order, the coordinates
+    of any scalar type, any other scalar properties skipped -- the ground truth the reference ships
+    (`groundtruth/sampled_pts/*.ply`, written by Open3D: double x y z + uchar red green blue), `gaussians_filtered.ply`,
+    `edge_sampled_points_*.ply`.  A list property in the vertex element or a missing coordinate is a ValueError."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elements = None, []  # elements: [name, count, [(property, numpy code)]]
+        while True:
+            raw = f.readline()
+            if not raw:
+                raise ValueError(f"{path}: no end_header")
+            tok = raw.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "end_header":
+                break
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property":
+                if not elements:
+                    raise ValueError(f"{path}: property before any element")
+                if tok[1] == "list":
+                    elements[-1][2].append((tok[-1], None))  # (legal in a later element, e.g. face)
+                elif tok[1] not in _PLY_SCALARS:
+                    raise ValueError(f"{path}: unknown property type {tok[1]!r}")
+                else:
+                    elements[-1][2].append((tok[2], _PLY_SCALARS[tok[1]]))
+        if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+            raise ValueError(f"{path}: unknown format {fmt!r}")
+        if not elements or elements[0][0] != "vertex":
+            raise ValueError(f"{path}: the vertex element must come first")
+        _, n, props = elements[0]
+        if any(code is None for _, code in props):
+            raise ValueError(f"{path}: list property in the vertex element")
+        names = [nm for nm, _ in props]
+        missing = [c for c in "xyz" if c not in names]
+        if missing:
+            raise ValueError(f"{path}: the vertex element has no {'/'.join(missing)}")
+        if fmt == "ascii":
+            rows = [f.readline().split() for _ in range(n)]
+            if any(len(r) != len(props) for r in rows):
+                raise ValueError(f"{path}: short vertex data")
+            cols = {c: np.array([float(r[names.index(c)]) for r in rows], dtype=np.float64) for c in "xyz"}
+        else:
+            end = "<" if fmt == "binary_little_endian" else ">"
+            dt = np.dtype([(nm, end + code) for nm, code in props])
+            buf = f.read(dt.itemsize * n)
+            if len(buf) != dt.itemsize * n:
+                raise ValueError(f"{path}: short vertex data")
+            rec = np.frombuffer(buf, dtype=dt, count=n)
+            cols = {c: rec[c].astype(np.float64) for c in "xyz"}
+    return np.stack([cols["x"], cols["y"], cols["z"]], axis=1).reshape(n, 3)
+
+
+def write_points_ply(points, path: str) -> None:
+    """Points [N,3] as binary little-endian `double x y z`: what Open3D and `read_points_ply` read."""
+    if isinstance(points, torch.Tensor):
+        points = points.detach().cpu().numpy()
+    pts = np.ascontiguousarray(np.asarray(points, dtype="<f8").reshape(-1, 3))
+    header = f"ply\nformat binary_little_endian 1.0\nelement vertex {len(pts)}\n" \
+        "property double x\nproperty double y\nproperty double z\nend_header\n"
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(pts.tobytes())

@@ -43,6 +43,7 @@ typedef void *eg_stream_t; /* hipStream_t */
 #define EG_ERR_ARG (-1)     /* bad argument (null pointer, negative size, unsupported channel count) */
 #define EG_ERR_LAUNCH (-2)  /* hipGetLastError() after a launch */
 #define EG_ERR_NODEVICE (-3)
+#define EG_ERR_CAPACITY (-4) /* a result the entry itself read back does not fit the caller's buffers (eg_edge_sample) */
 
 #define EG_TILE 16
 #define EG_MAX_BATCH 8 /* views per eg_train_step_batched call */
@@ -372,6 +373,44 @@ int eg_nn_query_auto(const float *queries /*[Q,3]*/, int64_t Q, const float *tar
                      int32_t *cell_of, int32_t *cell_counts, int32_t *cell_start, float *sorted_targets,
                      float *sorted_queries, void *grid_scratch, int32_t *out_idx /*[Q]*/, float *out_d2 /*[Q]*/,
                      eg_stream_t stream);
+/* ---- Parametric edges -> points: the sampling in front of the reference's evaluation (eval_utils.py:120-398,
+ * get_pred_points_and_directions[_from_dict]; eval.py --use_parametric_edges, fit_edges.py --save_sampled_points).
+ * curves: Nc cubic Beziers, float64 control points [Nc,4,3]; lines: float64 end points [Nl,2,3].  Primitive order
+ * everywhere: all curves, then all lines (eval.py:116).  Float64 throughout; fixed summation orders and no float
+ * atomics, so two runs give the same bits.  Nc == 0 and Nl == 0 are both legal; nothing is launched for an empty side.
+ *
+ * eg_edge_sample_count: lengths[p] -- a curve's is the reference's composite Simpson sum (100 sub-intervals
+ * [i/100, (i+1)/100], on each (|B'(a)| + 4 sum_odd + 2 sum_even + |B'(b)|) h / 3 with h = (b - a) / 100 and B' the true
+ * Bezier derivative, eval_utils.py:120-165: one workgroup per curve), a line's is |p0 - p1|; counts[p] =
+ * int(length // resolution) with Python's float floor division (the floor of the exact quotient, not floor(a / b));
+ * offsets = the exclusive scan of counts (offsets[Nc + Nl] = total[0]), summed in int64.  total[0] = the number of
+ * samples (saturated at INT32_MAX), total[1] = 1 when it exceeds INT32_MAX or `capacity` (capacity < 0: no limit of the
+ * caller's), else 0.  No host sync: the caller reads total back. */
+int eg_edge_sample_count(const double *curves /*[Nc,4,3]*/, int32_t Nc, const double *lines /*[Nl,2,3]*/, int32_t Nl,
+                         double resolution /* > 0 */, int64_t capacity, double *lengths /*[Nc+Nl]*/,
+                         int32_t *counts /*[Nc+Nl]*/, int32_t *offsets /*[Nc+Nl+1]*/, int32_t *total /*[2]*/,
+                         eg_stream_t stream);
+/* eg_edge_sample_emit: one thread per sample i < min(total[0], capacity): its primitive p by binary search in offsets,
+ * k = i - offsets[p], n = counts[p], t = k * (1 / (n - 1)) as np.linspace(0, 1, n) (last sample exactly 1; n == 1:
+ * t = 0); point = [t^3 t^2 t 1] M P (eval_utils.py:312-318) resp. (1 - t) p0 + t p1, in float64, rounded once to
+ * float32.  directions (may be NULL): lines (p1 - p0) / (|p1 - p0| + 1e-6) (:389-391); curves, normalised in float64,
+ * EG_EDGE_TANGENT_REFERENCE: the reference's A (3 t^2) + B (2 t) + C (:322-368; A t^2 + B t + C is the derivative, so
+ * this is NOT the tangent away from t = 0), EG_EDGE_TANGENT_EXACT: the true derivative.  prim_ids (may be NULL): p.
+ * `capacity` = the rows of the output buffers.  Nothing at all is written while total[1] is set. */
+#define EG_EDGE_TANGENT_REFERENCE 0
+#define EG_EDGE_TANGENT_EXACT 1
+int eg_edge_sample_emit(const double *curves, int32_t Nc, const double *lines, int32_t Nl,
+                        const int32_t *counts /*[Nc+Nl]*/, const int32_t *offsets /*[Nc+Nl+1]*/,
+                        const int32_t *total /*[2]*/, int64_t capacity, int32_t tangent, float *points /*[capacity,3]*/,
+                        float *directions /*[capacity,3]|NULL*/, int32_t *prim_ids /*[capacity]|NULL*/,
+                        eg_stream_t stream);
+/* eg_edge_sample: the two in one call for a caller with buffers of `capacity` rows.  It reads total[2] back into
+ * total_host (ONE stream synchronise: not for graph capture) and launches exactly total[0] emission threads; when the
+ * samples do not fit it emits nothing and returns EG_ERR_CAPACITY (total_host tells how many there are). */
+int eg_edge_sample(const double *curves, int32_t Nc, const double *lines, int32_t Nl, double resolution,
+                   int64_t capacity, int32_t tangent, double *lengths, int32_t *counts, int32_t *offsets,
+                   int32_t *total /*[2] device*/, float *points, float *directions, int32_t *prim_ids,
+                   int32_t *total_host /*[2] host*/, eg_stream_t stream);
 /* compute_direction_loss (edge_gs.py:346-373): sum_out[0] += sum over the counted (i,k) of
  * |m_i . unit(mu_i - mu_nn(i,k))|; g_means += and g_quats = the gradient of that SUM.  top_k <= 0 or >= K:
  * every listed neighbour counts (loss = 1 - sum/(N K), the caller scales by -lambda/(N K)); 0 < top_k < K
