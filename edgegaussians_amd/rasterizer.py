@@ -24,6 +24,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from . import sh as _sh
 from ._lib import call, ptr, stream
 
 TILE = 16
@@ -643,9 +644,10 @@ RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
 
 
 def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
-                        radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased):
+                        radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree=None):
     """`rasterization` with a depth channel and / or backgrounds: the general two-node path (projection -> compositing)
-    with the compositing of eg_composite_{fwd,bwd}_modes_cams, which takes `depths` as an input."""
+    with the compositing of eg_composite_{fwd,bwd}_modes_cams, which takes `depths` as an input.  With `sh_degree`,
+    `colors` holds the coefficients and the colours are evaluated behind the projection (its radii are their mask)."""
     N, Cn = means.shape[0], viewmats.shape[0]
     depth = render_mode != "RGB"
     if render_mode in ("D", "ED"):
@@ -653,6 +655,8 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
     radii, means2d, depths, conics, comps, tpg, counts, _splat = _Projection.apply(
         means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
         float(near_plane), float(far_plane), float(radius_clip), antialiased)
+    if sh_degree is not None and colors is not None:
+        colors = _sh.view_colors(means, viewmats, colors, radii, sh_degree)
     opac = opacities[None, :].expand(Cn, N)
     if antialiased:
         opac = opac * comps
@@ -692,8 +696,16 @@ def rasterization(
     absgrad: bool = False, rasterize_mode: str = "classic", channel_chunk: int = 32,
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``, for packed=False,
-    sh_degree=None, tile_size=16 and colours of 1 or 3 channels (the reference's call, edge_gs.py:250-268, is
-    render_mode='RGB' without backgrounds).
+    tile_size=16 and colours of 1 or 3 channels (the reference's call, edge_gs.py:250-268, is render_mode='RGB'
+    without backgrounds and without sh_degree).
+
+    ``sh_degree`` = L (0..4): ``colors`` holds spherical-harmonics coefficients, [N, K, 3] shared by the cameras or
+    [C, N, K, 3], fp32 on the device, ``(L + 1) ** 2 <= K`` (the rows above are ignored and get zero gradient); anything
+    else is a ValueError.  The colour of Gaussian n in camera c is ``clamp_min(SH(means[n] - campos[c]) + 0.5, 0)``
+    with ``campos = inverse(viewmats)[:, :3, 3]`` where ``radii[c, n] > 0`` and 0 elsewhere (csrc/sh.hip); the
+    coefficients receive their gradient (summed over the cameras when shared), ``means`` receives the direction's on
+    top of the projection's, ``viewmats`` none.  These 3-channel colours take the general path (never the fast one),
+    so every render mode and ``backgrounds`` work with it; "D" / "ED" do not evaluate the harmonics.
 
     ``render_mode``: "RGB", "D", "ED", "RGB+D" or "RGB+ED", as in gsplat: the "+D" modes append the projection depth
     as one more channel (``render`` [C,H,W,D+1]), "D" / "ED" render the depth alone ([C,H,W,1], ``colors`` unused), and
@@ -712,14 +724,16 @@ def rasterization(
     if render_mode not in RENDER_MODES:
         raise ValueError(f"Unknown render_mode: {render_mode}")
     if sh_degree is not None:
-        raise NotImplementedError("sh_degree is outside the reference's path")
+        _sh.check_view_coeffs(colors, sh_degree, Cn, N)
     if packed or sparse_grad:
         raise NotImplementedError("packed / sparse_grad are outside the reference's path (edge_gs.py:261,265)")
     if tile_size != TILE:
         raise NotImplementedError("tile_size must be 16 (edge_gs.py:232)")
     if rasterize_mode not in ("classic", "antialiased"):
         raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
-    if colors.dim() == 2:
+    if sh_degree is not None:
+        pass  # (colors holds the coefficients, checked above; the colours they give have 3 channels)
+    elif colors.dim() == 2:
         _check(colors, (N, colors.shape[-1]), "colors")
     else:
         _check(colors, (Cn, N, colors.shape[-1]), "colors")
@@ -732,9 +746,9 @@ def rasterization(
     antialiased = rasterize_mode == "antialiased"
     if render_mode != "RGB" or backgrounds is not None:
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
-                                   far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased)
+                                   far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree)
 
-    if (Cn == 1 and colors.dim() == 2 and not colors.requires_grad and float(eps2d) == 0.3 and float(near_plane) == 0.01
+    if (sh_degree is None and Cn == 1 and colors.dim() == 2 and not colors.requires_grad and float(eps2d) == 0.3 and float(near_plane) == 0.01
             and float(far_plane) == 1e10 and float(radius_clip) == 0.0 and N > 0 and _FAST_ENABLED):
         # the reference's own call (edge_gs.py:247-268): colours torch.ones(N, 3) without grad, one camera
         out = _fast_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, absgrad, antialiased)
@@ -744,6 +758,8 @@ def rasterization(
     radii, means2d, depths, conics, comps, tpg, counts, _splat = _Projection.apply(
         means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
         float(near_plane), float(far_plane), float(radius_clip), antialiased)
+    if sh_degree is not None:
+        colors = _sh.view_colors(means, viewmats, colors, radii, sh_degree)
     opac = opacities[None, :].expand(Cn, N)
     if antialiased:
         opac = opac * comps

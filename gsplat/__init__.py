@@ -1,8 +1,10 @@
 """Drop-in shim: ``from gsplat import rasterization`` (reference edgegaussians/models/edge_gs.py:8)
 resolves to the MI355X-native implementation, so the reference's model class runs unchanged.
 
-Only the one symbol the reference imports is provided."""
+The reference imports ``rasterization`` alone; ``spherical_harmonics`` is there for the other callers of gsplat, whose
+``rasterization(..., sh_degree=L)`` calls it serves as well."""
 from edgegaussians_amd.rasterizer import rasterization  # noqa: F401
+from edgegaussians_amd.sh import spherical_harmonics  # noqa: F401
 
 __version__ = "1.0.0+edgegaussians_amd"
-__all__ = ["rasterization"]
+__all__ = ["rasterization", "spherical_harmonics"]

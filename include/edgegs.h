@@ -685,6 +685,29 @@ int eg_operator_bwd(const eg_operator_args *a, const float *v_alphas, int64_t v_
                     float *g2d /*[N,8]*/, float *absgrad_out /*[N,2]|NULL*/, const float *v_means2d /*[N,2]|NULL*/,
                     float *v_means, float *v_quats, float *v_scales, float *v_opacities, eg_stream_t stream);
 
+/* ---- spherical-harmonics colours (gsplat 1.0.0 `spherical_harmonics` and the sh_degree branch of `rasterization`),
+ * csrc/sh.hip.  raw[c, n, :] = sum over k < (degree + 1)^2 of Y_k(dir[c, n] / |dir[c, n]|) * coeffs[(c,) n, k, :], with the
+ * real spherical harmonics in the 3DGS / gsplat order and sign (k = l*l + l + m, Cartesian table times (-1)^m); degree 0..4,
+ * K >= (degree + 1)^2 coefficient rows per Gaussian of which the rows above the degree's are ignored.  coeffs is [N, K, 3],
+ * shared by the C cameras, or [C, N, K, 3] with coeffs_per_camera = 1 (0 or 1, nothing else).
+ * ONE entry pair with a null-pointer switch for the directions: either dirs [C, N, 3] is given (any length, normalised
+ * in the kernel; means and campos NULL), or dirs is NULL and dir[c, n] = means[n] - campos[c] (means [N, 3], campos [C, 3]).
+ * masks [C, N] bytes or NULL: where 0 the colour is 0 and no gradient flows.  clamp != 0: colors = max(raw + 0.5, 0), and
+ * the backward recomputes the gate (gradient passes where raw + 0.5 >= 0); clamp == 0: colors = raw.
+ * eg_sh_bwd takes v_colors [C, N, 3] and WRITES (no accumulation, no zeroing by the caller) v_coeffs in the shape of
+ * coeffs -- summed over the cameras when they share them, exact zeros in the rows above the degree's and where masked --
+ * and, optionally, the gradient of the directions: v_dirs [C, N, 3] (with dirs) or v_means [N, 3], summed over the cameras
+ * (with means / campos); NULL: not wanted.  One lane per Gaussian loops over the cameras: no atomics, bit-identical runs.
+ * Every argument is checked before any HIP call; N == 0 returns EG_OK without a launch. */
+int eg_sh_fwd(int32_t degree, int32_t K, int32_t C, int32_t N, const float *dirs /*[C,N,3] or NULL*/,
+              const float *means /*[N,3] or NULL*/, const float *campos /*[C,3] or NULL*/, const float *coeffs,
+              int32_t coeffs_per_camera, const uint8_t *masks /*[C,N] or NULL*/, int32_t clamp, float *colors /*[C,N,3]*/,
+              eg_stream_t stream);
+int eg_sh_bwd(int32_t degree, int32_t K, int32_t C, int32_t N, const float *dirs, const float *means, const float *campos,
+              const float *coeffs, int32_t coeffs_per_camera, const uint8_t *masks, int32_t clamp,
+              const float *v_colors /*[C,N,3]*/, float *v_coeffs, float *v_dirs /*[C,N,3] or NULL*/,
+              float *v_means /*[N,3] or NULL*/, eg_stream_t stream);
+
 /* ---- native data-parallel run (edgegaussians_amd/dist.py drives it).  RCCL is dlopen'ed from
  * `librccl_path` (NULL / "": "librccl.so" by the loader's search path) -- the library PyTorch ships, so that the process
  * holds ONE RCCL -- and the communicator is created from a 128-byte ncclUniqueId: rank 0 calls eg_dp_unique_id, the
