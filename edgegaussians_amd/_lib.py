@@ -136,6 +136,10 @@ _SIGS = {
     "eg_composite_fwd_modes_cams": [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
     "eg_composite_bwd_modes_cams": [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp],
+    "eg_composite_fwd_wide_cams": [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32,
+                                   _i32, _vp],
+    "eg_composite_bwd_wide_cams": [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _i32, _i32, _i32, _vp],
     "eg_sh_fwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp],
     "eg_sh_bwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "eg_train_step_batched": [C.POINTER(StepArgs), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp],

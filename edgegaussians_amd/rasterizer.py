@@ -223,6 +223,69 @@ class _ModeCompositing(torch.autograd.Function):
                 None, None, None, None, None, None, None)
 
 
+class _WideCompositing(torch.autograd.Function):
+    """`_ModeCompositing` for colours of any channel count D (csrc/composite_wide.hip): the D channels are composited in
+    ceil(D / chunk) launches per direction of eg_composite_{fwd,bwd}_wide_cams, each addressing its chunk inside the
+    full-width tensors (no copies).  Forward: the first chunk writes `alphas` and `last_ids`, the depth channel rides on
+    the last.  Backward: the first chunk alone receives `v_alphas`; g2d and v_depths are zeroed once and accumulated
+    over the chunks, so `absgrad` is the sum of the chunks' abs-gradients."""
+
+    @staticmethod
+    def forward(ctx, means2d, conics, colors, opacities, depths, backgrounds, width, height, offsets, flatten_ids,
+                absgrad, packed_splat, depth, chunk):
+        Cn, N = means2d.shape[0], means2d.shape[1]
+        dev = means2d.device
+        D = colors.shape[-1]
+        colors_c = colors.contiguous()
+        bg = backgrounds.contiguous() if backgrounds is not None else None
+        P = D + int(depth)
+        render = torch.empty(Cn, height, width, P, device=dev)
+        alphas = torch.empty(Cn, height, width, 1, device=dev)
+        last_ids = torch.empty(Cn, height, width, dtype=torch.int32, device=dev)
+        per_cam = int(colors_c.dim() == 3)
+        for c0 in range(0, D, chunk):
+            w = min(chunk, D - c0)
+            first, final = c0 == 0, c0 + w == D
+            call("eg_composite_fwd_wide_cams", Cn, ptr(packed_splat), N, ptr(colors_c) + 4 * c0, per_cam, w,
+                 int(depth and final), ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width,
+                 height, ptr(render) + 4 * c0, ptr(alphas) if first else None, ptr(last_ids) if first else None, w, D, P,
+                 stream())
+        ctx.save_for_backward(means2d, packed_splat, colors_c, bg, alphas, last_ids, offsets, flatten_ids)
+        ctx.cfg = (width, height, absgrad, depth, D, per_cam, chunk)
+        ctx.mark_non_differentiable(last_ids)
+        return render, alphas, last_ids
+
+    @staticmethod
+    def backward(ctx, v_render, v_alphas, _v_last):
+        width, height, absgrad, depth, D, per_cam, chunk = ctx.cfg
+        means2d, splat, colors, bg, alphas, last_ids, offsets, flatten_ids = ctx.saved_tensors
+        Cn, N = means2d.shape[0], means2d.shape[1]
+        dev = means2d.device
+        P = D + int(depth)
+        v_render = v_render.contiguous()
+        v_alphas = v_alphas.contiguous()
+        g2d = torch.zeros(Cn, N, 8, device=dev)
+        v_colors = torch.zeros(Cn, N, D, device=dev) if ctx.needs_input_grad[2] else None
+        v_depths = torch.zeros(Cn, N, device=dev) if depth else None
+        for c0 in range(0, D, chunk):
+            w = min(chunk, D - c0)
+            first, final = c0 == 0, c0 + w == D
+            call("eg_composite_bwd_wide_cams", Cn, ptr(splat), N, ptr(colors) + 4 * c0, per_cam, w, int(depth and final),
+                 ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width, height, ptr(alphas),
+                 ptr(last_ids), ptr(v_render) + 4 * c0, ptr(v_alphas) if first else None, ptr(g2d),
+                 ptr(v_colors) + 4 * c0 if v_colors is not None else None,
+                 ptr(v_depths) if (depth and final) else None, w, D, P, stream())
+        if v_colors is not None and not per_cam:
+            v_colors = v_colors.sum(0)
+        v_bg = None
+        if bg is not None and ctx.needs_input_grad[5]:  # (gsplat computes it in torch the same way)
+            v_bg = (v_render[..., :D] * (1.0 - alphas)).sum((1, 2))
+        if absgrad:
+            means2d.absgrad = g2d[..., 2:4].contiguous()
+        return (g2d[..., 0:2].contiguous(), g2d[..., 4:7].contiguous(), v_colors, g2d[..., 7].contiguous(), v_depths, v_bg,
+                None, None, None, None, None, None, None, None)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Fast path for the reference's exact call pattern (edge_gs.py:247-279): one camera, colours == 1 without grad.
 # ONE autograd node over the kernels of the training step (segmented binning with tight tile boxes -> per-tile sort ->
@@ -644,10 +707,12 @@ RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
 
 
 def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
-                        radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree=None):
+                        radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree=None, chunk=None):
     """`rasterization` with a depth channel and / or backgrounds: the general two-node path (projection -> compositing)
     with the compositing of eg_composite_{fwd,bwd}_modes_cams, which takes `depths` as an input.  With `sh_degree`,
-    `colors` holds the coefficients and the colours are evaluated behind the projection (its radii are their mask)."""
+    `colors` holds the coefficients and the colours are evaluated behind the projection (its radii are their mask).
+    With `chunk` (colours of a channel count other than 1 or 3, in any mode that renders them): the same projection,
+    binning and sort, then the compositing of eg_composite_{fwd,bwd}_wide_cams in chunks of `chunk` channels."""
     N, Cn = means.shape[0], viewmats.shape[0]
     depth = render_mode != "RGB"
     if render_mode in ("D", "ED"):
@@ -671,9 +736,14 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
         binfo = {"isect_ids": torch.cat([i_l[c] | (c << (32 + tile_bits)) for c in range(Cn)]),
                  "flatten_ids": torch.cat([f_l[c] + c * N for c in range(Cn)]),
                  "isect_offsets": torch.stack([(o_l[c][:-1] + bases[c]).reshape(th, tw) for c in range(Cn)])}
-    render, alphas, last_ids = _ModeCompositing.apply(
-        means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
-        bool(absgrad), _splat, depth)
+    if chunk is not None and colors is not None:
+        render, alphas, last_ids = _WideCompositing.apply(
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            bool(absgrad), _splat, depth, chunk)
+    else:
+        render, alphas, last_ids = _ModeCompositing.apply(
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            bool(absgrad), _splat, depth)
     if render_mode in ("ED", "RGB+ED"):
         render = torch.cat([render[..., :-1], render[..., -1:] / alphas.clamp(min=1e-10)], dim=-1)
     info = {
@@ -696,8 +766,16 @@ def rasterization(
     absgrad: bool = False, rasterize_mode: str = "classic", channel_chunk: int = 32,
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``, for packed=False,
-    tile_size=16 and colours of 1 or 3 channels (the reference's call, edge_gs.py:250-268, is render_mode='RGB'
-    without backgrounds and without sh_degree).
+    tile_size=16 and colours of any channel count D >= 1 (the reference's call, edge_gs.py:250-268, is
+    render_mode='RGB' with three channels, without backgrounds and without sh_degree).
+
+    D = 1 or 3 takes the paths described below.  Any other D -- ``colors`` [N, D] or [C, N, D], every render mode, with
+    or without ``backgrounds`` -- goes through projection, binning and the sort once and is then composited in
+    ``ceil(D / chunk)`` launches per direction, ``chunk = min(channel_chunk, 32)`` (csrc/composite_wide.hip);
+    ``channel_chunk`` must be a positive int (ValueError otherwise).  ``alphas``, ``info["last_ids"]`` and the binning
+    tensors do not depend on the chunking.  With one chunk ``info["means2d"].absgrad`` is gsplat's definition; with
+    several it is the sum of the chunks' abs-gradients (each chunk's share of dL/dmeans2d enters with its own absolute
+    value).  What gsplat 1.0.0 itself leaves there for D > channel_chunk could not be checked against gsplat.
 
     ``sh_degree`` = L (0..4): ``colors`` holds spherical-harmonics coefficients, [N, K, 3] shared by the cameras or
     [C, N, K, 3], fp32 on the device, ``(L + 1) ** 2 <= K`` (the rows above are ignored and get zero gradient); anything
@@ -738,12 +816,18 @@ def rasterization(
     else:
         _check(colors, (Cn, N, colors.shape[-1]), "colors")
     D = colors.shape[-1]
-    if D not in (1, 3):
-        raise NotImplementedError("colors must have 1 or 3 channels")
+    if isinstance(channel_chunk, bool) or not isinstance(channel_chunk, int) or channel_chunk < 1:
+        raise ValueError(f"channel_chunk must be a positive int, got {channel_chunk!r}")
+    if D < 1:
+        raise ValueError("colors must have at least one channel")
     if backgrounds is not None:
         _check(backgrounds, (Cn, D), "backgrounds")
     width, height = int(width), int(height)
     antialiased = rasterize_mode == "antialiased"
+    if D not in (1, 3) and render_mode not in ("D", "ED"):  # (the depth-only modes do not read the colours)
+        return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
+                                   far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
+                                   chunk=min(channel_chunk, 32))
     if render_mode != "RGB" or backgrounds is not None:
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                    far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree)

@@ -652,6 +652,31 @@ int eg_composite_bwd_modes_cams(int32_t C, const float *splat /*[C,N,8]*/, int32
                                 float *g2d /*[C,N,8]*/, float *v_colors /*[C,N,channels] or NULL*/,
                                 float *v_depths /*[C,N], with depth*/, eg_stream_t stream);
 
+/* ---- colours of any channel count (rasterization(colors=[..., D]) with D other than 1 or 3), csrc/composite_wide.hip:
+ * the two entries above for ONE CHUNK of a wider tensor.  `channels` (1 .. 32) is the chunk width the caller declares; it
+ * runs in the kernel instantiated for the next of 2, 4, 8, 16, 32, and `n_real` (1 .. channels) of its channels are real:
+ * only those are loaded, stored or added to.  colors / v_colors / backgrounds point at the chunk's first channel inside
+ * tensors whose rows are `color_stride` floats apart ([N, color_stride] or, with colors_per_camera != 0,
+ * [C, N, color_stride]; backgrounds [C, color_stride]); render / v_render likewise with rows of `pixel_stride` floats
+ * ([C, H, W, pixel_stride]).  With depth != 0 the depth channel is channel n_real of the chunk's pixel.  Unlike the mode
+ * entries, neither depth nor backgrounds is required, colors is.  Forward: alphas and last_ids may be NULL (not
+ * written: every chunk of a call computes the same).  Backward: accumulates like eg_composite_bwd_modes_cams; v_alphas
+ * is given with ONE chunk of a call only (it would be counted once per chunk).  The sums of a wave end in the lanes
+ * that add them: one atomic instruction per (wave, Gaussian). */
+int eg_composite_fwd_wide_cams(int32_t C, const float *splat /*[C,N,8]*/, int32_t N, const float *colors,
+                               int32_t colors_per_camera, int32_t channels, int32_t depth,
+                               const float *backgrounds /*or NULL*/, const int32_t *offsets /*[C,T+1]*/,
+                               const int32_t *flatten_ids, int32_t width, int32_t height, float *render,
+                               float *alphas /*or NULL*/, int32_t *last_ids /*or NULL*/, int32_t n_real,
+                               int32_t color_stride, int32_t pixel_stride, eg_stream_t stream);
+int eg_composite_bwd_wide_cams(int32_t C, const float *splat /*[C,N,8]*/, int32_t N, const float *colors,
+                               int32_t colors_per_camera, int32_t channels, int32_t depth,
+                               const float *backgrounds /*or NULL*/, const int32_t *offsets /*[C,T+1]*/,
+                               const int32_t *flatten_ids, int32_t width, int32_t height, const float *alphas,
+                               const int32_t *last_ids, const float *v_render, const float *v_alphas /*or NULL*/,
+                               float *g2d /*[C,N,8]*/, float *v_colors /*or NULL*/, float *v_depths /*[C,N], with depth*/,
+                               int32_t n_real, int32_t color_stride, int32_t pixel_stride, eg_stream_t stream);
+
 /* ---- the drop-in operator's fast path in two calls (edgegaussians_amd/rasterizer.py: the reference's own call of
  * gsplat.rasterization -- one camera, colours == 1 without grad, edge_gs.py:247-279 -- and its autograd backward).
  * eg_operator_fwd: projection + exact tile binning -> per-tile sort -> the training step's wave-autonomous forward in its
