@@ -511,3 +511,228 @@ def check_inside_borderline_sets(sc, view, strategy, label, trainer_kwargs=None,
                raw_grad_err_over_tolerance_outside=raw_err, loss_rel_err=abs(loss_g - loss_o) / abs(loss_o))
     record("inside_borderline_sets", **rec)
     return rec
+
+
+# ---------------------------------------------------------------------------------------------------
+# Projection and its VJP, one Gaussian at a time (tests/test_projection_host.py, tests/test_gpu_projection.py).
+# assert_close holds a tensor to 1e-4 of its LARGEST element: with O(1) cotangents on every output the means2d path
+# (fx / z, hundreds) carries v_means and every Jacobian term that reaches it through the conic is invisible.  Here
+# one output's cotangent is applied at a time and every row is held to a bound of its own,
+#     |got - ref64|_rowmax <= (ROW_FLOOR + ROW_KAPPA_FACTOR * kappa_r) * sigma_r,
+# sigma_r = the row maximum of the float64 reference, kappa_r = how far one-ulp noise on the fp32 inputs moves that row
+# of the float64 reference (relative to sigma_r): what ANY fp32 evaluation must be allowed.  ROW_FLOOR is a fifth of
+# the project's 1e-4; the factor was set on the references alone (fp32 oracle against float64 oracle: at most 0.22 of
+# the bound for the conic cotangent, 0.34 for the compensation cotangent on small Gaussians) and the host test keeps the
+# fp32 oracle within HALF the bound on every scene the device tests use.
+ROW_FLOOR = 2e-5
+ROW_KAPPA_FACTOR = 32.0
+ROW_LOOSE = 1e-4            # a row whose bound exceeds the project's tolerance counts as "loose" (share capped at 3 %)
+FWD_ROW_TOL = 2e-5          # forward outputs: per-row error against float64, relative to the row maximum
+PROJ_OUTPUTS = ("means2d", "depths", "conics", "compensations")
+PROJ_GRADS = ("means", "quats", "scales")
+PROJ_DEFAULTS = dict(near_plane=0.01, far_plane=1e10, radius_clip=0.0, eps2d=0.3)
+PROJ_SIZE = (200, 136)
+SCALE_RATIOS = (1.0, 2.2, 4.5)
+
+
+def camera_space_scene(viewmat, K, W, H, groups, n_per_group, base_scale, gen, ratios=SCALE_RATIOS):
+    """Gaussians placed in CAMERA space for the branch under test.  `groups`: ((ax_lo, ax_hi), (ay_lo, ay_hi)) in
+    half-screens from the principal point; depth U(3, 4.5); quaternions randn * U(0.5, 1.5) (un-normalised: 1/|q|
+    matters); scales base_scale * U(0.7, 1.4) * a permutation of `ratios` (well separated: nearly equal pairs make the
+    quaternion gradient a cancellation).  Returns fp32 (means [N,3], quats [N,4], scales [N,3], group index [N])."""
+    n, G = int(n_per_group), len(groups)
+    N = n * G
+    vm, Kd = viewmat.double(), K.double()
+    R, t = vm[:3, :3], vm[:3, 3]
+    fx, fy = float(Kd[0, 0]), float(Kd[1, 1])
+    u = torch.rand(N, 3, generator=gen, dtype=torch.float64)
+    lo = torch.tensor([[g[0][0], g[1][0]] for g in groups], dtype=torch.float64).repeat_interleave(n, 0)
+    hi = torch.tensor([[g[0][1], g[1][1]] for g in groups], dtype=torch.float64).repeat_interleave(n, 0)
+    a = lo + (hi - lo) * u[:, :2]
+    z = 3.0 + 1.5 * u[:, 2]
+    p_c = torch.stack([a[:, 0] * (W / 2) / fx * z, a[:, 1] * (H / 2) / fy * z, z], dim=-1)
+    means = (p_c - t) @ R                                    # R^T (p_c - t)
+    quats = torch.randn(N, 4, generator=gen, dtype=torch.float64) * (0.5 + torch.rand(N, 1, generator=gen, dtype=torch.float64))
+    size = base_scale * (0.7 + 0.7 * torch.rand(N, 1, generator=gen, dtype=torch.float64))
+    perm = torch.argsort(torch.rand(N, 3, generator=gen), dim=1)
+    scales = size * torch.tensor(ratios, dtype=torch.float64)[perm]
+    group = torch.arange(G).repeat_interleave(n)
+    return means.float().contiguous(), quats.float().contiguous(), scales.float().contiguous(), group
+
+
+def ref_project_vjps(means, quats, scales, viewmats, Ks, W, H, args, cots, dtype=torch.float64):
+    """oracle.ref_torch.project + autograd for the cameras of one call, one output's cotangent at a time.
+    cots: {output name: [C, N, k]}.  Returns (outs: {name: [C, N, k], "radii": [C, N]} detached,
+    grads: {output name: {"means" | "quats" | "scales": [N, k] summed over the cameras}})."""
+    from oracle import ref_torch as O
+    p = [t.detach().to(dtype).clone().requires_grad_(True) for t in (means, quats, scales)]
+    per_cam = [O.project(p[0], p[1], p[2], viewmats[c], Ks[c], W, H, args["near_plane"], args["far_plane"], args["eps2d"],
+                         args["radius_clip"]) for c in range(viewmats.shape[0])]
+    outs = {"radii": torch.stack([o[0] for o in per_cam])}
+    for i, name in enumerate(PROJ_OUTPUTS):
+        outs[name] = torch.stack([o[1 + i] for o in per_cam])
+    grads = {}
+    for name, cot in cots.items():
+        y = outs[name]
+        g = torch.autograd.grad(y, p, cot.to(dtype).reshape(y.shape), retain_graph=True, allow_unused=True)
+        grads[name] = {k: (gi if gi is not None else torch.zeros_like(pi)).detach() for k, gi, pi in zip(PROJ_GRADS, g, p)}
+    return {k: v.detach() for k, v in outs.items()}, grads
+
+
+def ulp_perturbed(tensors, gen):
+    """every element times 1 + 2^-23 U(-1, 1), in float64: one-ulp noise on fp32 inputs"""
+    return [t.double() * (1.0 + 2.0 ** -23 * (2.0 * torch.rand(t.shape, generator=gen, dtype=torch.float64) - 1.0))
+            for t in tensors]
+
+
+def row_kappa(ref64, perturbed):
+    """kappa_r: the largest row-max change of the float64 reference under the perturbed inputs, relative to sigma_r."""
+    ref = to_np(ref64).astype(np.float64).reshape(ref64.shape[0], -1)
+    sigma = np.abs(ref).max(axis=1)
+    k = np.zeros_like(sigma)
+    for q in perturbed:
+        k = np.maximum(k, np.abs(to_np(q).astype(np.float64).reshape(ref.shape) - ref).max(axis=1))
+    return np.where(sigma > 0, k / np.where(sigma > 0, sigma, 1.0), 0.0)
+
+
+def row_bound_ratio(got, ref64, kappa, rows=None):
+    """(largest |got - ref64|_rowmax / bound over the rows with sigma_r > 0, share of those rows whose bound exceeds
+    ROW_LOOSE, number of rows with sigma_r == 0 on which `got` is not exactly zero, number of rows over the bound)."""
+    ref = to_np(ref64).astype(np.float64).reshape(ref64.shape[0], -1)
+    g = to_np(got).astype(np.float64).reshape(ref.shape)
+    sel = np.ones(ref.shape[0], bool) if rows is None else np.asarray(to_np(rows), bool)
+    sigma = np.abs(ref).max(axis=1)
+    live = sel & (sigma > 0)
+    rel = ROW_FLOOR + ROW_KAPPA_FACTOR * np.asarray(kappa, np.float64)
+    ratio = np.abs(g - ref).max(axis=1)[live] / (rel[live] * sigma[live])
+    nonzero = int((np.abs(g[sel & (sigma == 0)]) != 0).any(axis=1).sum())
+    return (float(ratio.max(initial=0.0)), float((rel[live] > ROW_LOOSE).mean()) if live.any() else 0.0, nonzero,
+            int((ratio > 1.0).sum()))
+
+
+def row_bound_check(got, ref64, kappa, name, rows=None):
+    """The per-Gaussian comparison: |got - ref64|_rowmax <= (ROW_FLOOR + ROW_KAPPA_FACTOR kappa_r) sigma_r on every row
+    (of `rows`), exactly zero where the reference row is zero.  Returns (largest ratio to the bound, share of rows
+    whose bound exceeds ROW_LOOSE)."""
+    ratio, loose, nonzero, over = row_bound_ratio(got, ref64, kappa, rows)
+    assert nonzero == 0, f"{name}: {nonzero} rows are not exactly zero where the float64 reference is"
+    assert ratio <= 1.0, f"{name}: {over} rows over the per-row bound, the worst by {ratio:.2f} x"
+    return ratio, loose
+
+
+def fwd_row_err(got, ref64, rows):
+    """largest per-row error of a forward output relative to the row maximum of the float64 reference"""
+    ref = to_np(ref64).astype(np.float64).reshape(ref64.shape[0], -1)
+    g = to_np(got).astype(np.float64).reshape(ref.shape)
+    rows = np.asarray(to_np(rows), bool)
+    sigma = np.abs(ref).max(axis=1)[rows]
+    return float((np.abs(g - ref).max(axis=1)[rows] / np.maximum(sigma, 1e-300)).max(initial=0.0))
+
+
+def projection_borderline(means, quats, scales, viewmat, K, W, H, args):
+    """bool [N]: the Gaussians whose integer decisions (culls, radius ceil) hinge on float rounding under `args`:
+    the C oracle's set at the case's near plane and eps2d, plus the rows within REL_GAUSS of the far plane.
+    (radius_clip is taken non-integer by the cases, so the clip is borderline only where the radius ceil already is.)"""
+    from oracle import c_oracle as CO
+    b = CO.project_borderline(to_np(means), to_np(quats), to_np(scales), to_np(viewmat), to_np(K), W, H,
+                              near_plane=args["near_plane"], eps2d=args["eps2d"], rel=REL_GAUSS) > 0
+    z = (means.double() @ viewmat.double()[:3, :3].T + viewmat.double()[:3, 3])[:, 2].numpy()
+    return b | (np.abs(z - args["far_plane"]) <= REL_GAUSS * args["far_plane"])
+
+
+# The scenes and cases shared by the host test (which asserts the conditions on the inputs with the references alone)
+# and the device test.  Every float64 reference is computed once per process and never modified.
+INSIDE_GROUP = ((-0.9, 0.9), (-0.9, 0.9))
+FOV_GROUPS = (INSIDE_GROUP,                                   # 0 inside
+              ((1.05, 1.25), (-0.9, 0.9)),                    # 1 off-screen, not clamped
+              ((1.35, 1.8), (-0.9, 0.9)), ((-1.8, -1.35), (-0.9, 0.9)),     # 2, 3 clamped in x
+              ((-0.9, 0.9), (1.35, 1.8)), ((-0.9, 0.9), (-1.8, -1.35)),     # 4, 5 clamped in y
+              ((1.35, 1.7), (1.35, 1.7)))                     # 6 clamped in both
+FOV_CLAMPED_GROUPS = (2, 3, 4, 5, 6)
+PROJ_SCENES = {  # kind: (groups, n_per_group, base_scale, scale ratios, seed)
+    "inside": ((INSIDE_GROUP,), 3000, 0.02, SCALE_RATIOS, 101),
+    "small": ((INSIDE_GROUP,), 3000, 0.003, SCALE_RATIOS, 102),
+    "fov": (FOV_GROUPS, 400, 0.12, SCALE_RATIOS, 103),
+    "args": ((INSIDE_GROUP,), 3000, 0.008, SCALE_RATIOS, 106),
+    "tiny": ((INSIDE_GROUP,), 3000, 0.0025, SCALE_RATIOS, 109),
+}
+
+
+def off_default_args(eps2d, radius_clip=6.5):
+    """near / far / clip / eps2d all off their defaults and pairwise distinct: any two swapped in a call change the result"""
+    return dict(near_plane=3.3, far_plane=4.2, radius_clip=radius_clip, eps2d=eps2d)
+
+
+ALL_COTS = PROJ_OUTPUTS
+PROJ_CASES = {  # name: scene kind, camera the scene is built for, cameras of the call, arguments, cotangents checked
+    "defaults": dict(kind="inside", scene_cam=0, cams=(0,), args=PROJ_DEFAULTS, cots=("means2d", "depths", "conics")),
+    "defaults_comp": dict(kind="small", scene_cam=0, cams=(0,), args=PROJ_DEFAULTS, cots=("compensations",)),
+    "fov_cam1": dict(kind="fov", scene_cam=1, cams=(1,), args=PROJ_DEFAULTS, cots=("conics",)),
+    "fov_cam3": dict(kind="fov", scene_cam=3, cams=(3,), args=PROJ_DEFAULTS, cots=("conics",)),
+    "args_eps0.05": dict(kind="args", scene_cam=0, cams=(0,), args=off_default_args(0.05),
+                         cots=("means2d", "depths", "conics")),
+    "args_eps0.05_comp": dict(kind="tiny", scene_cam=0, cams=(0,), args=off_default_args(0.05, radius_clip=2.5),
+                              cots=("compensations",)),
+    "args_eps1": dict(kind="args", scene_cam=0, cams=(0,), args=off_default_args(1.0), cots=ALL_COTS),
+    "args_eps0": dict(kind="args", scene_cam=0, cams=(0,), args=off_default_args(0.0), cots=("conics",)),
+    "three_cams_eps0.05": dict(kind="args", scene_cam=0, cams=(0, 1, 2), args=off_default_args(0.05),
+                               cots=("means2d", "depths", "conics")),
+    "three_cams_eps1": dict(kind="args", scene_cam=0, cams=(0, 1, 2), args=off_default_args(1.0), cots=ALL_COTS),
+}
+COMP_MIN_ONE_MINUS_SQ = 0.2   # the compensation cotangent is checked on rows with 1 - comp^2 >= this (float64) ...
+COMP_MIN_SHARE = 0.9          # ... which must be at least this share of the visible rows
+
+_proj_cache = {}
+
+
+def projection_cameras():
+    if "cams" not in _proj_cache:
+        from edgegaussians_amd import synth
+        sc = synth.make_scene(8, 5, PROJ_SIZE[0], PROJ_SIZE[1], seed=0)
+        _proj_cache["cams"] = (sc.viewmats, sc.Ks)
+    return _proj_cache["cams"]
+
+
+def projection_scene(kind, scene_cam):
+    key = ("scene", kind, scene_cam)
+    if key not in _proj_cache:
+        groups, n, base, ratios, seed = PROJ_SCENES[kind]
+        vms, Ks = projection_cameras()
+        _proj_cache[key] = camera_space_scene(vms[scene_cam], Ks[scene_cam], PROJ_SIZE[0], PROJ_SIZE[1], groups, n, base,
+                                              torch.Generator().manual_seed(seed + scene_cam), ratios)
+    return _proj_cache[key]
+
+
+def projection_reference(case):
+    """Everything the comparisons of one PROJ_CASES entry need, computed once: the fp32 inputs, the N(0,1) cotangents
+    [C, N, k], the float64 outputs and per-cotangent gradients (summed over the cameras), kappa per (cotangent,
+    gradient), the per-camera integer-borderline sets, and the rows the compensation cotangent is checked on."""
+    key = ("ref", case)
+    if key in _proj_cache:
+        return _proj_cache[key]
+    spec = PROJ_CASES[case]
+    W, H = PROJ_SIZE
+    vms_all, Ks_all = projection_cameras()
+    cams = list(spec["cams"])
+    vms, Ks = vms_all[cams].contiguous(), Ks_all[cams].contiguous()
+    means, quats, scales, group = projection_scene(spec["kind"], spec["scene_cam"])
+    N, C = means.shape[0], len(cams)
+    gen = torch.Generator().manual_seed(7)
+    widths = dict(means2d=2, depths=1, conics=3, compensations=1)
+    cots = {name: torch.randn(C, N, widths[name], generator=gen) for name in PROJ_OUTPUTS}
+    cots = {name: cots[name] for name in spec["cots"]}
+    outs, grads = ref_project_vjps(means, quats, scales, vms, Ks, W, H, spec["args"], cots)
+    pert = []
+    for _ in range(4):
+        pm, pq, ps = ulp_perturbed((means, quats, scales), gen)
+        pert.append(ref_project_vjps(pm, pq, ps, vms, Ks, W, H, spec["args"], cots)[1])
+    kappa = {c: {g: row_kappa(grads[c][g], [p[c][g] for p in pert]) for g in PROJ_GRADS} for c in cots}
+    border = np.stack([projection_borderline(means, quats, scales, vms[c], Ks[c], W, H, spec["args"]) for c in range(C)])
+    vis = outs["radii"].numpy() > 0                                    # [C, N]
+    comp = outs["compensations"][..., 0].numpy() if outs["compensations"].dim() == 3 else outs["compensations"].numpy()
+    comp_ok = 1.0 - comp * comp >= COMP_MIN_ONE_MINUS_SQ               # per camera
+    comp_rows = vis.any(axis=0) & (comp_ok | ~vis).all(axis=0)         # every camera that sees the row qualifies
+    ref = dict(case=case, spec=spec, means=means, quats=quats, scales=scales, group=group, viewmats=vms, Ks=Ks, cots=cots,
+               outs=outs, grads=grads, kappa=kappa, border=border, vis=vis, comp_rows=comp_rows)
+    _proj_cache[key] = ref
+    return ref
