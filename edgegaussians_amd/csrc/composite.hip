@@ -51,7 +51,9 @@ namespace eg {
 struct ModeArgs {
   const float *bg;  // [C, CH] with BG
   float *v_depths;  // [C, N] (backward, DEPTH), accumulated
-  int N;
+  int N;            // RECORD STRIDE: camera c's splat / g2d / v_colors / v_depths (and per-camera colors) start c * N rows
+                    // in.  EG_PACKED_STRIDE (0): packed records -- every camera addresses the same [nnz, ...] arrays and
+                    // flatten_ids index the whole packed list (include/edgegs.h)
   int colors_per_camera;
 };
 

@@ -28,7 +28,7 @@ namespace eg {
 struct WideArgs {
   const float *bg;    // backgrounds of the chunk: camera c's row at bg + c * cs (BG)
   float *v_depths;    // [C, N] (backward, DEPTH), accumulated
-  int N;
+  int N;              // record stride between the cameras' blocks; EG_PACKED_STRIDE (0) = packed records (see ModeArgs)
   int colors_per_camera;
   int n_real;         // real channels of the chunk, 1 .. CH
   int cs;             // row stride (floats) of colors, v_colors and backgrounds

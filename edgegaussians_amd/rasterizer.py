@@ -101,6 +101,103 @@ class _Projection(torch.autograd.Function):
         return (v_means, v_quats, v_scales) + (None,) * 10
 
 
+_DUMMY: Dict = {}
+
+
+def _ptr_or_dummy(t: Optional[Tensor]) -> Optional[int]:
+    """`ptr`, except that an EMPTY tensor (the packed lists of a call in which no pair is visible) gives the address of
+    a small zeroed buffer instead of NULL: the compositing entries require their arrays, and with no intersection in any
+    tile their kernels never index them."""
+    if t is None or t.numel() > 0:
+        return ptr(t)
+    key = str(t.device)
+    if key not in _DUMMY:
+        _DUMMY[key] = torch.zeros(64, device=t.device)
+    return _DUMMY[key].data_ptr()
+
+
+class _PackedProjection(torch.autograd.Function):
+    """gsplat ``fully_fused_projection`` (packed=True) for C cameras (csrc/packed.hip): only the pairs (camera, Gaussian)
+    that survive every cull, in ascending order of camera * N + Gaussian.  Forward: eg_packed_count, ONE host read-back
+    (indptr, hence nnz: the synchronisation gsplat has there too), eg_packed_write.  Backward: eg_packed_bwd (dense
+    [N, k] gradients, summed over the cameras in camera order, no atomics) or, with `sparse_grad`, eg_packed_bwd_sparse
+    (sparse COO gradients of size [N, k] with indices gaussian_ids[None] and values [nnz, k], coalesced iff C == 1).
+    `holder` receives the host copy of indptr."""
+
+    @staticmethod
+    def forward(ctx, means, quats, scales, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
+                radius_clip, antialiased, sparse_grad, holder):
+        Cn, N = viewmats.shape[0], means.shape[0]
+        dev = means.device
+        tw, th = math.ceil(width / TILE), math.ceil(height / TILE)
+        means_c, quats_c, scales_c = means.contiguous(), quats.contiguous(), scales.contiguous()
+        opac_c = opac_for_splat.contiguous()
+        vm, Kc = viewmats.contiguous(), Ks.contiguous()
+        flags = _lib.FLAG_ANTIALIASED if antialiased else 0
+        # the only scratch: one int32 per workgroup of 256 pairs
+        block_base = torch.empty(Cn * math.ceil(N / 256), dtype=torch.int32, device=dev)
+        indptr = torch.empty(Cn + 1, dtype=torch.int64, device=dev)
+        call("eg_packed_count", ptr(means_c), ptr(quats_c), ptr(scales_c), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height,
+             near_plane, far_plane, eps2d, radius_clip, flags, ptr(block_base), ptr(indptr), stream())
+        indptr_host = indptr.tolist()  # the first of the call's two read-backs (the second: the M_c of the binning)
+        nnz = indptr_host[-1]
+        if nnz >= 2 ** 31:
+            raise RuntimeError(f"rasterization(packed=True): {nnz} visible (camera, Gaussian) pairs; the limit is 2^31 - 1")
+        i32 = dict(dtype=torch.int32, device=dev)
+        splat = torch.empty(nnz, 8, device=dev)
+        radii = torch.empty(nnz, **i32)
+        means2d = torch.empty(nnz, 2, device=dev)
+        depths = torch.empty(nnz, device=dev)
+        conics = torch.empty(nnz, 3, device=dev)
+        comps = torch.empty(nnz, device=dev)
+        tpg = torch.empty(nnz, **i32)
+        camera_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
+        gaussian_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
+        counts = torch.zeros(Cn, tw * th, **i32)
+        call("eg_packed_write", ptr(means_c), ptr(quats_c), ptr(scales_c), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height,
+             near_plane, far_plane, eps2d, radius_clip, flags, ptr(block_base), nnz, ptr(splat), ptr(radii), ptr(means2d),
+             ptr(depths), ptr(conics), ptr(comps), ptr(tpg), ptr(camera_ids), ptr(gaussian_ids), ptr(counts), stream())
+        holder["indptr"] = indptr_host
+        ctx.save_for_backward(means_c, quats_c, scales_c, opac_c, vm, Kc, indptr, camera_ids, gaussian_ids)
+        ctx.cfg = (width, height, eps2d, flags, bool(sparse_grad))
+        ctx.mark_non_differentiable(radii, tpg, counts, splat, camera_ids, gaussian_ids)
+        return radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids
+
+    @staticmethod
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, *_rest):
+        means, quats, scales, opac, vm, Kc, indptr, camera_ids, gaussian_ids = ctx.saved_tensors
+        width, height, eps2d, flags, sparse_grad = ctx.cfg
+        Cn, N, nnz = vm.shape[0], means.shape[0], gaussian_ids.shape[0]
+        dev = means.device
+        z2 = torch.zeros(nnz, 2, device=dev)
+        z1 = torch.zeros(nnz, 1, device=dev)
+        vm2d = v_means2d if v_means2d is not None else z2
+        vcon = v_conics if v_conics is not None else torch.zeros(nnz, 3, device=dev)
+        g2d = torch.cat([vm2d, z2, vcon, z1], dim=-1).contiguous()  # the [nnz, 8] record layout of the compositing backward
+        vcomp = (v_comps if v_comps is not None else torch.zeros(nnz, device=dev)).contiguous()
+        vdep = v_depths.contiguous() if v_depths is not None else None
+        rows = nnz if sparse_grad else N
+        v_means = torch.empty(rows, 3, device=dev)
+        v_quats = torch.empty(rows, 4, device=dev)
+        v_scales = torch.empty(rows, 3, device=dev)
+        if sparse_grad:
+            call("eg_packed_bwd_sparse", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width, height,
+                 eps2d, flags, nnz, ptr(camera_ids), ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means),
+                 ptr(v_quats), ptr(v_scales), stream())
+            idx = gaussian_ids[None]
+            v_means, v_quats, v_scales = (
+                torch.sparse_coo_tensor(idx, v, size=(N, v.shape[1]), is_coalesced=(Cn == 1))
+                for v in (v_means, v_quats, v_scales))
+            # (a second owner: torch's AccumulateGrad rebuilds a sparse gradient it owns alone from its indices and
+            # values and loses the coalesced mark on the way; one it shares is cloned, mark included)
+            ctx.sparse_grads = (v_means, v_quats, v_scales)
+        else:
+            call("eg_packed_bwd", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d,
+                 flags, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means), ptr(v_quats),
+                 ptr(v_scales), stream())
+        return (v_means, v_quats, v_scales) + (None,) * 12
+
+
 class _Compositing(torch.autograd.Function):
     """gsplat ``rasterize_to_pixels`` (packed=False, backgrounds=None) for C cameras."""
 
@@ -181,8 +278,11 @@ class _ModeCompositing(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, depths, backgrounds, width, height, offsets, flatten_ids,
-                absgrad, packed_splat, depth):
-        Cn, N = means2d.shape[0], means2d.shape[1]
+                absgrad, packed_splat, depth, packed_cams=None):
+        # (packed_cams = C: the per-Gaussian inputs are the packed [nnz, ...] lists of _PackedProjection, the colours
+        # already gathered per pair; the entries then take the record stride _lib.PACKED_STRIDE instead of N)
+        Cn, N = (packed_cams, _lib.PACKED_STRIDE) if packed_cams is not None else (means2d.shape[0], means2d.shape[1])
+        _ptr1 = _ptr_or_dummy if packed_cams is not None else ptr
         dev = means2d.device
         D = colors.shape[-1] if colors is not None else 0
         colors_c = colors.contiguous() if colors is not None else None
@@ -190,28 +290,30 @@ class _ModeCompositing(torch.autograd.Function):
         render = torch.empty(Cn, height, width, D + int(depth), device=dev)
         alphas = torch.empty(Cn, height, width, 1, device=dev)
         last_ids = torch.empty(Cn, height, width, dtype=torch.int32, device=dev)
-        per_cam = int(colors_c is not None and colors_c.dim() == 3)
-        call("eg_composite_fwd_modes_cams", Cn, ptr(packed_splat), N, ptr(colors_c), per_cam, D, int(depth), ptr(bg),
+        per_cam = int(colors_c is not None and (colors_c.dim() == 3 or packed_cams is not None))
+        call("eg_composite_fwd_modes_cams", Cn, _ptr1(packed_splat), N, _ptr1(colors_c), per_cam, D, int(depth), ptr(bg),
              ptr(offsets), ptr(flatten_ids), width, height, ptr(render), ptr(alphas), ptr(last_ids), stream())
         ctx.save_for_backward(means2d, packed_splat, colors_c, bg, alphas, last_ids, offsets, flatten_ids)
-        ctx.cfg = (width, height, absgrad, depth, D, per_cam)
+        ctx.cfg = (width, height, absgrad, depth, D, per_cam, packed_cams)
         ctx.mark_non_differentiable(last_ids)
         return render, alphas, last_ids
 
     @staticmethod
     def backward(ctx, v_render, v_alphas, _v_last):
-        width, height, absgrad, depth, D, per_cam = ctx.cfg
+        width, height, absgrad, depth, D, per_cam, packed_cams = ctx.cfg
         means2d, splat, colors, bg, alphas, last_ids, offsets, flatten_ids = ctx.saved_tensors
-        Cn, N = means2d.shape[0], means2d.shape[1]
+        Cn, N = (packed_cams, _lib.PACKED_STRIDE) if packed_cams is not None else (means2d.shape[0], means2d.shape[1])
+        lead = tuple(means2d.shape[:-1])  # (C, N), or (nnz,) on packed records
+        _ptr1 = _ptr_or_dummy if packed_cams is not None else ptr
         dev = means2d.device
         v_render = v_render.contiguous()
         v_alphas = v_alphas.contiguous()
-        g2d = torch.zeros(Cn, N, 8, device=dev)
-        v_colors = torch.zeros(Cn, N, D, device=dev) if (D > 0 and ctx.needs_input_grad[2]) else None
-        v_depths = torch.zeros(Cn, N, device=dev) if depth else None
-        call("eg_composite_bwd_modes_cams", Cn, ptr(splat), N, ptr(colors), per_cam, D, int(depth), ptr(bg), ptr(offsets),
-             ptr(flatten_ids), width, height, ptr(alphas), ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(g2d),
-             ptr(v_colors), ptr(v_depths), stream())
+        g2d = torch.zeros(*lead, 8, device=dev)
+        v_colors = torch.zeros(*lead, D, device=dev) if (D > 0 and ctx.needs_input_grad[2]) else None
+        v_depths = torch.zeros(*lead, device=dev) if depth else None
+        call("eg_composite_bwd_modes_cams", Cn, _ptr1(splat), N, _ptr1(colors), per_cam, D, int(depth), ptr(bg), ptr(offsets),
+             ptr(flatten_ids), width, height, ptr(alphas), ptr(last_ids), ptr(v_render), ptr(v_alphas), _ptr1(g2d),
+             _ptr1(v_colors), _ptr1(v_depths), stream())
         if v_colors is not None and not per_cam:
             v_colors = v_colors.sum(0)
         v_bg = None
@@ -220,7 +322,7 @@ class _ModeCompositing(torch.autograd.Function):
         if absgrad:
             means2d.absgrad = g2d[..., 2:4].contiguous()
         return (g2d[..., 0:2].contiguous(), g2d[..., 4:7].contiguous(), v_colors, g2d[..., 7].contiguous(), v_depths, v_bg,
-                None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None)
 
 
 class _WideCompositing(torch.autograd.Function):
@@ -232,8 +334,10 @@ class _WideCompositing(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, depths, backgrounds, width, height, offsets, flatten_ids,
-                absgrad, packed_splat, depth, chunk):
-        Cn, N = means2d.shape[0], means2d.shape[1]
+                absgrad, packed_splat, depth, chunk, packed_cams=None):
+        # (packed_cams: as in _ModeCompositing)
+        Cn, N = (packed_cams, _lib.PACKED_STRIDE) if packed_cams is not None else (means2d.shape[0], means2d.shape[1])
+        _ptr1 = _ptr_or_dummy if packed_cams is not None else ptr
         dev = means2d.device
         D = colors.shape[-1]
         colors_c = colors.contiguous()
@@ -242,39 +346,41 @@ class _WideCompositing(torch.autograd.Function):
         render = torch.empty(Cn, height, width, P, device=dev)
         alphas = torch.empty(Cn, height, width, 1, device=dev)
         last_ids = torch.empty(Cn, height, width, dtype=torch.int32, device=dev)
-        per_cam = int(colors_c.dim() == 3)
+        per_cam = int(colors_c.dim() == 3 or packed_cams is not None)
         for c0 in range(0, D, chunk):
             w = min(chunk, D - c0)
             first, final = c0 == 0, c0 + w == D
-            call("eg_composite_fwd_wide_cams", Cn, ptr(packed_splat), N, ptr(colors_c) + 4 * c0, per_cam, w,
+            call("eg_composite_fwd_wide_cams", Cn, _ptr1(packed_splat), N, _ptr1(colors_c) + 4 * c0, per_cam, w,
                  int(depth and final), ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width,
                  height, ptr(render) + 4 * c0, ptr(alphas) if first else None, ptr(last_ids) if first else None, w, D, P,
                  stream())
         ctx.save_for_backward(means2d, packed_splat, colors_c, bg, alphas, last_ids, offsets, flatten_ids)
-        ctx.cfg = (width, height, absgrad, depth, D, per_cam, chunk)
+        ctx.cfg = (width, height, absgrad, depth, D, per_cam, chunk, packed_cams)
         ctx.mark_non_differentiable(last_ids)
         return render, alphas, last_ids
 
     @staticmethod
     def backward(ctx, v_render, v_alphas, _v_last):
-        width, height, absgrad, depth, D, per_cam, chunk = ctx.cfg
+        width, height, absgrad, depth, D, per_cam, chunk, packed_cams = ctx.cfg
         means2d, splat, colors, bg, alphas, last_ids, offsets, flatten_ids = ctx.saved_tensors
-        Cn, N = means2d.shape[0], means2d.shape[1]
+        Cn, N = (packed_cams, _lib.PACKED_STRIDE) if packed_cams is not None else (means2d.shape[0], means2d.shape[1])
+        lead = tuple(means2d.shape[:-1])  # (C, N), or (nnz,) on packed records
+        _ptr1 = _ptr_or_dummy if packed_cams is not None else ptr
         dev = means2d.device
         P = D + int(depth)
         v_render = v_render.contiguous()
         v_alphas = v_alphas.contiguous()
-        g2d = torch.zeros(Cn, N, 8, device=dev)
-        v_colors = torch.zeros(Cn, N, D, device=dev) if ctx.needs_input_grad[2] else None
-        v_depths = torch.zeros(Cn, N, device=dev) if depth else None
+        g2d = torch.zeros(*lead, 8, device=dev)
+        v_colors = torch.zeros(*lead, D, device=dev) if ctx.needs_input_grad[2] else None
+        v_depths = torch.zeros(*lead, device=dev) if depth else None
         for c0 in range(0, D, chunk):
             w = min(chunk, D - c0)
             first, final = c0 == 0, c0 + w == D
-            call("eg_composite_bwd_wide_cams", Cn, ptr(splat), N, ptr(colors) + 4 * c0, per_cam, w, int(depth and final),
+            call("eg_composite_bwd_wide_cams", Cn, _ptr1(splat), N, _ptr1(colors) + 4 * c0, per_cam, w, int(depth and final),
                  ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width, height, ptr(alphas),
-                 ptr(last_ids), ptr(v_render) + 4 * c0, ptr(v_alphas) if first else None, ptr(g2d),
-                 ptr(v_colors) + 4 * c0 if v_colors is not None else None,
-                 ptr(v_depths) if (depth and final) else None, w, D, P, stream())
+                 ptr(last_ids), ptr(v_render) + 4 * c0, ptr(v_alphas) if first else None, _ptr1(g2d),
+                 _ptr1(v_colors) + 4 * c0 if v_colors is not None else None,
+                 _ptr1(v_depths) if (depth and final) else None, w, D, P, stream())
         if v_colors is not None and not per_cam:
             v_colors = v_colors.sum(0)
         v_bg = None
@@ -283,7 +389,7 @@ class _WideCompositing(torch.autograd.Function):
         if absgrad:
             means2d.absgrad = g2d[..., 2:4].contiguous()
         return (g2d[..., 0:2].contiguous(), g2d[..., 4:7].contiguous(), v_colors, g2d[..., 7].contiguous(), v_depths, v_bg,
-                None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -757,6 +863,84 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
     return render, alphas, info
 
 
+def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
+                          radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree, chunk,
+                          sparse_grad):
+    """`rasterization(packed=True)`: the packed projection (_PackedProjection), the colours / opacities gathered per pair
+    in torch (dense gradients of the caller's shapes, as in gsplat), every camera's range binned as a single-camera
+    problem (eg_packed_bin), and the mode / wide compositing kernels on the packed records (record stride
+    _lib.PACKED_STRIDE).  Never the unit-colour fast path.  Two host read-backs: indptr, then the M_c."""
+    N, Cn = means.shape[0], viewmats.shape[0]
+    dev = means.device
+    depth = render_mode != "RGB"
+    if render_mode in ("D", "ED"):
+        colors, backgrounds = None, None  # (gsplat: the depth is the only channel, its background is 0)
+    holder: Dict = {}
+    radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids = _PackedProjection.apply(
+        means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
+        float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder)
+    indptr = holder["indptr"]
+    nnz = indptr[-1]
+    if colors is not None:
+        if sh_degree is not None:
+            with torch.no_grad():
+                campos = torch.linalg.inv_ex(viewmats)[0][:, :3, 3]  # (torch.linalg.inv without its host read of `info`)
+            dirs = means[gaussian_ids] - campos[camera_ids]
+            coeffs = colors[gaussian_ids] if colors.dim() == 3 else colors[camera_ids, gaussian_ids]
+            if nnz > 0:  # (no mask: every pair is visible)
+                colors = torch.clamp_min(_sh.spherical_harmonics(sh_degree, dirs, coeffs) + 0.5, 0.0)
+            else:
+                colors = (dirs + coeffs.sum(-2)) * 0.0  # [0, 3], on the graph of `means` and the coefficients
+        else:
+            colors = colors[gaussian_ids] if colors.dim() == 2 else colors[camera_ids, gaussian_ids]
+    opac = opacities[gaussian_ids]
+    if antialiased:
+        opac = opac * comps
+    tw, th = math.ceil(width / TILE), math.ceil(height / TILE)
+    T = tw * th
+    with torch.no_grad():
+        offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
+        item_offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
+        total = torch.zeros(Cn, 4, dtype=torch.int32, device=dev)
+        call("eg_tile_offsets_cams", ptr(counts), T, Cn, 1 << 40, ptr(offsets), ptr(item_offsets), ptr(total), stream())
+        vals = total.reshape(-1).tolist()  # the second and last read-back of the call
+        Ms = [int(vals[4 * c]) for c in range(Cn)]
+        nmax = [int(vals[4 * c + 3]) for c in range(Cn)]
+        M = sum(Ms)
+        keys = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+        flat = torch.zeros(max(M, 1), dtype=torch.int32, device=dev)
+        ids = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+        call("eg_packed_bin", ptr(means2d), ptr(radii), ptr(depths), (C.c_int64 * (Cn + 1))(*indptr), Cn, width, height,
+             ptr(offsets), ptr(counts), (C.c_int64 * Cn)(*Ms), ptr(keys), ptr(flat), ptr(ids), (C.c_int32 * Cn)(*nmax),
+             stream())
+        bases = torch.tensor([sum(Ms[:c]) for c in range(Cn)], dtype=torch.int32, device=dev)
+        binfo = {"isect_ids": ids[:M], "flatten_ids": flat[:M],
+                 "isect_offsets": (offsets[:, :-1] + bases[:, None]).reshape(Cn, th, tw)}
+    if colors is not None and backgrounds is None and not depth and chunk is None:
+        # plain RGB with 1 or 3 channels: the mode kernels' <CH, no depth, background> instantiation under a zero
+        # background (T_final * 0 added to every channel), as `_mode_rasterization` runs RGB with real backgrounds
+        backgrounds = torch.zeros(Cn, colors.shape[-1], device=dev)
+    if chunk is not None and colors is not None:
+        render, alphas, last_ids = _WideCompositing.apply(
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            bool(absgrad), splat, depth, chunk, Cn)
+    else:
+        render, alphas, last_ids = _ModeCompositing.apply(
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            bool(absgrad), splat, depth, Cn)
+    if render_mode in ("ED", "RGB+ED"):
+        render = torch.cat([render[..., :-1], render[..., -1:] / alphas.clamp(min=1e-10)], dim=-1)
+    info = {
+        "camera_ids": camera_ids, "gaussian_ids": gaussian_ids,
+        "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
+        "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
+        **binfo,
+        "width": width, "height": height, "tile_size": TILE, "n_cameras": Cn,
+        "last_ids": last_ids,
+    }
+    return render, alphas, info
+
+
 def rasterization(
     means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor, colors: Tensor,
     viewmats: Tensor, Ks: Tensor, width: int, height: int,
@@ -765,9 +949,28 @@ def rasterization(
     backgrounds: Optional[Tensor] = None, render_mode: str = "RGB", sparse_grad: bool = False,
     absgrad: bool = False, rasterize_mode: str = "classic", channel_chunk: int = 32,
 ) -> Tuple[Tensor, Tensor, Dict]:
-    """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``, for packed=False,
-    tile_size=16 and colours of any channel count D >= 1 (the reference's call, edge_gs.py:250-268, is
-    render_mode='RGB' with three channels, without backgrounds and without sh_degree).
+    """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``, for tile_size=16 and colours of
+    any channel count D >= 1 (the reference's call, edge_gs.py:250-268, is packed=False, render_mode='RGB' with three
+    channels, without backgrounds and without sh_degree).
+
+    ``packed`` (default True, as in gsplat): the projection keeps only the pairs (camera c, Gaussian n) that survive
+    every cull -- exactly the set ``radii[c, n] > 0`` of the packed=False call -- in ascending order of ``c * N + n``
+    (csrc/packed.hip).  ``info["camera_ids"]`` / ``info["gaussian_ids"]`` are int64 [nnz] (None with packed=False);
+    ``radii``, ``depths``, ``opacities``, ``tiles_per_gauss`` are [nnz], ``means2d`` [nnz, 2] (non-leaf, ``retain_grad()``
+    works, ``.absgrad`` [nnz, 2] after backward with ``absgrad``), ``conics`` [nnz, 3]; ``flatten_ids`` index the packed
+    list; ``isect_ids``, ``isect_offsets``, ``last_ids`` and the scalars are as with packed=False.  The values are those of
+    the packed=False call at ``[camera_ids, gaussian_ids]``, bit for bit.  Colours and opacities are gathered per pair
+    in torch (dense gradients of the caller's shapes); with ``sh_degree`` the directions are
+    ``means[gaussian_ids] - campos[camera_ids]``.  Every render mode, ``backgrounds``, ``rasterize_mode``, the cull
+    arguments, ``absgrad`` and ``channel_chunk`` work as described below; a packed call never takes the unit-colour fast
+    path.  Nothing of size C * N is allocated: 4 bytes of scratch per 256 pairs, the outputs per visible pair.  Two
+    host read-backs per call (nnz, then the intersection counts), where packed=False has the second only.  A call in
+    which no pair is visible returns the backgrounds (or zeros), zero alphas, empty per-pair tensors and zero gradients.
+
+    ``sparse_grad`` (needs ``packed=True``, ValueError otherwise): the gradients of ``means``, ``quats`` and ``scales``
+    are ``torch.sparse_coo_tensor`` s of size [N, k] with indices ``gaussian_ids[None]`` and values [nnz, k], marked
+    coalesced exactly when there is one camera; ``opacities`` and ``colors`` keep dense gradients.  Without it the
+    three gradients are dense [N, k], summed over the cameras in camera order without atomics (the same bits every run).
 
     D = 1 or 3 takes the paths described below.  Any other D -- ``colors`` [N, D] or [C, N, D], every render mode, with
     or without ``backgrounds`` -- goes through projection, binning and the sort once and is then composited in
@@ -803,8 +1006,8 @@ def rasterization(
         raise ValueError(f"Unknown render_mode: {render_mode}")
     if sh_degree is not None:
         _sh.check_view_coeffs(colors, sh_degree, Cn, N)
-    if packed or sparse_grad:
-        raise NotImplementedError("packed / sparse_grad are outside the reference's path (edge_gs.py:261,265)")
+    if sparse_grad and not packed:
+        raise ValueError("sparse_grad=True requires packed=True")
     if tile_size != TILE:
         raise NotImplementedError("tile_size must be 16 (edge_gs.py:232)")
     if rasterize_mode not in ("classic", "antialiased"):
@@ -824,6 +1027,11 @@ def rasterization(
         _check(backgrounds, (Cn, D), "backgrounds")
     width, height = int(width), int(height)
     antialiased = rasterize_mode == "antialiased"
+    if packed:
+        wide = D not in (1, 3) and render_mode not in ("D", "ED") and sh_degree is None
+        return _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
+                                     far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
+                                     sh_degree, min(channel_chunk, 32) if wide else None, sparse_grad)
     if D not in (1, 3) and render_mode not in ("D", "ED"):  # (the depth-only modes do not read the colours)
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                    far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,

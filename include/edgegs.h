@@ -677,6 +677,62 @@ int eg_composite_bwd_wide_cams(int32_t C, const float *splat /*[C,N,8]*/, int32_
                                float *g2d /*[C,N,8]*/, float *v_colors /*or NULL*/, float *v_depths /*[C,N], with depth*/,
                                int32_t n_real, int32_t color_stride, int32_t pixel_stride, eg_stream_t stream);
 
+/* ---- N as the RECORD STRIDE of the four entries above, and packed records (N == EG_PACKED_STRIDE).
+ * The mode and wide kernels use N for one thing only: camera c's block of splat, g2d, v_colors, v_depths (and of colors
+ * with colors_per_camera != 0) starts c * N rows into the array, and flatten_ids index inside that block.  With
+ * N == EG_PACKED_STRIDE (zero) every camera addresses the SAME arrays from row 0: splat / g2d [nnz, 8], colors / v_colors
+ * [nnz, ...] (already gathered per pair, so colors_per_camera makes no difference), v_depths [nnz], and flatten_ids are
+ * indices into the whole packed list of eg_packed_write (eg_packed_bin leaves them so).  offsets, the images and
+ * backgrounds are per camera as before.  Nothing else in the entries reads N. */
+#define EG_PACKED_STRIDE 0
+
+/* ---- packed projection (rasterization(packed=True)), csrc/packed.hip: only the pairs (camera c, Gaussian n) whose
+ * radius is positive after every cull -- exactly the set radii[c, n] > 0 of eg_project_fwd_cams with the same arguments,
+ * with the same values bit for bit -- in ascending order of c * N + n.  nnz = number of pairs.
+ * eg_packed_count: the culls of every pair, counted per workgroup of 256 Gaussians of one camera; block_base
+ *   [C * ceil(N / 256)] int32 (the only scratch) receives the exclusive scan, indptr [C + 1] int64 the cameras' ranges
+ *   (indptr[C] = nnz).  The caller reads indptr back (the one host synchronisation gsplat has for nnz, too).
+ * eg_packed_write: recomputes the projection and writes pair p = its rank: splat [nnz, 8] (the record of the
+ *   compositing kernels: x y a b c opacity*compensation depth radius), radii / depths / compensations /
+ *   tiles_per_gauss [nnz], means2d [nnz, 2], conics [nnz, 3], camera_ids / gaussian_ids [nnz] int64, and adds the
+ *   tile hits to tile_counts [C, T] (zeroed by the caller).  All outputs are required.  nnz == 0: nothing to do.
+ * eg_packed_bin: eg_tile_emit + eg_sort_pairs on every camera's range; indptr_host [C + 1], M_host [C] and
+ *   max_tile_host [C] (or NULL) are HOST arrays, offsets [C, T + 1] from eg_tile_offsets_cams; keys / flatten_ids /
+ *   isect_ids (NULL ok) hold sum(M_host) entries, camera c's from sum(M_host[:c]).  flatten_ids index the whole packed
+ *   list; isect_ids carry the camera above the tile bits (camera << (32 + floor(log2(T)) + 1)).
+ * eg_packed_bwd: v_means [N, 3], v_quats [N, 4], v_scales [N, 3] from g2d [nnz, 8] (layout of eg_composite_bwd_*'s
+ *   g2d: words 0-1 v_means2d, 4-6 v_conics), v_comps [nnz] and v_depths [nnz] (or NULL).  One thread per Gaussian sums
+ *   its pairs in camera order in registers and writes every row (zeros where no camera sees it): no atomics, the same
+ *   bits on every run.  indptr: the DEVICE array eg_packed_count wrote.
+ * eg_packed_bwd_sparse: the same VJP per pair without the sum: v_means [nnz, 3], v_quats [nnz, 4], v_scales [nnz, 3]
+ *   (the values of sparse gradients whose indices are gaussian_ids). */
+int eg_packed_count(const float *means, const float *quats, const float *scales, const float *opacities,
+                    const float *viewmats /*[C,4,4]*/, const float *Ks /*[C,3,3]*/, int32_t N, int32_t C, int32_t width,
+                    int32_t height, float near_plane, float far_plane, float eps2d, float radius_clip, uint32_t flags,
+                    int32_t *block_base /*[C*ceil(N/256)]*/, int64_t *indptr /*[C+1]*/, eg_stream_t stream);
+int eg_packed_write(const float *means, const float *quats, const float *scales, const float *opacities,
+                    const float *viewmats, const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height,
+                    float near_plane, float far_plane, float eps2d, float radius_clip, uint32_t flags,
+                    const int32_t *block_base, int64_t nnz, float *splat /*[nnz,8]*/, int32_t *radii, float *means2d,
+                    float *depths, float *conics, float *compensations, int32_t *tiles_per_gauss, int64_t *camera_ids,
+                    int64_t *gaussian_ids, int32_t *tile_counts /*[C,T]*/, eg_stream_t stream);
+int eg_packed_bin(const float *means2d /*[nnz,2]*/, const int32_t *radii /*[nnz]*/, const float *depths /*[nnz]*/,
+                  const int64_t *indptr_host /*[C+1]*/, int32_t C, int32_t width, int32_t height,
+                  const int32_t *offsets /*[C,T+1]*/, int32_t *tile_counts /*[C,T], returned to zero*/,
+                  const int64_t *M_host /*[C]*/, uint64_t *keys, int32_t *flatten_ids, int64_t *isect_ids /*NULL ok*/,
+                  const int32_t *max_tile_host /*[C] or NULL*/, eg_stream_t stream);
+int eg_packed_bwd(const float *means, const float *quats, const float *scales, const float *opacities,
+                  const float *viewmats, const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height, float eps2d,
+                  uint32_t flags, const int64_t *indptr /*[C+1], device*/, int64_t nnz, const int64_t *gaussian_ids,
+                  const float *g2d /*[nnz,8]*/, const float *v_comps /*[nnz]*/, const float *v_depths /*[nnz] or NULL*/,
+                  float *v_means, float *v_quats, float *v_scales, eg_stream_t stream);
+int eg_packed_bwd_sparse(const float *means, const float *quats, const float *scales, const float *opacities,
+                         const float *viewmats, const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height,
+                         float eps2d, uint32_t flags, int64_t nnz, const int64_t *camera_ids, const int64_t *gaussian_ids,
+                         const float *g2d /*[nnz,8]*/, const float *v_comps /*[nnz]*/, const float *v_depths /*[nnz] or NULL*/,
+                         float *v_means /*[nnz,3]*/, float *v_quats /*[nnz,4]*/, float *v_scales /*[nnz,3]*/,
+                         eg_stream_t stream);
+
 /* ---- the drop-in operator's fast path in two calls (edgegaussians_amd/rasterizer.py: the reference's own call of
  * gsplat.rasterization -- one camera, colours == 1 without grad, edge_gs.py:247-279 -- and its autograd backward).
  * eg_operator_fwd: projection + exact tile binning -> per-tile sort -> the training step's wave-autonomous forward in its
