@@ -1,4 +1,6 @@
 """Comparison helpers shared by the parity tests."""
+import math
+
 import numpy as np
 import torch
 
@@ -736,3 +738,570 @@ def projection_reference(case):
                outs=outs, grads=grads, kappa=kappa, border=border, vis=vis, comp_rows=comp_rows)
     _proj_cache[key] = ref
     return ref
+
+
+# ---------------------------------------------------------------------------------------------------
+# The orientation regularisers (csrc/knn.hip) and the densify / cull kernels (csrc/densify.hip), row by row
+# (tests/test_regularizers_host.py, tests/test_gpu_regularizers.py, tests/test_densify_host.py, tests/test_gpu_densify.py).
+REG_ROW_TOL = 1e-4            # per row: |got - ref64|_rowmax <= REG_ROW_TOL * (row maximum of the float64 reference)
+REG_LOSS_TOL = 1e-6           # the loss value, relative
+REG_FP32_SHARE = 0.25         # the fp32 torch evaluation of the reference stays within this share of the row bound
+REG_MIN_MARGIN = 1e-5         # smallest |dot| and smallest top_k selection gap a scene may contain (float64), see reg_conditions
+ADAM_SKIP_BELOW = 100 * 1e-8  # Adam deltas: elements with 0 < |g64| < 100 eps are left out ...
+ADAM_SKIP_CAP = 1e-3          # ... and are at most this share
+
+
+def _quat_rotmats(q):
+    w, x, y, z = (q / q.norm(dim=1, keepdim=True)).unbind(-1)
+    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                        2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                        2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1).view(-1, 3, 3)
+
+
+def ref_direction_terms(means, quats, log_scales, nn, top_k, dtype=torch.float64):
+    """The pieces of ref_direction_loss with the graph attached: dict of loss, leaves (means, quats), and detached major
+    axes [N,3], unit directions u [N,K,3], squared distances n2, dot [N,K], valid [N,K], selection key [N,K], chosen
+    [N,K] and `used`."""
+    m = means.detach().to(dtype).clone().requires_grad_(True)
+    q = quats.detach().to(dtype).clone().requires_grad_(True)
+    ls = log_scales.detach().to(dtype)
+    nn = torch.as_tensor(to_np(nn)).long()
+    N, K = nn.shape
+    used = top_k if 0 < top_k < K else K
+    major = _quat_rotmats(q)[torch.arange(N), :, torch.argmax(ls, dim=-1)]       # first maximum
+    d = m[:, None, :] - m[nn.clamp(min=0)]
+    n2 = (d * d).sum(-1)
+    valid = (nn >= 0) & (n2.detach() > 0)
+    u = d / torch.sqrt(torch.where(valid, n2, torch.ones_like(n2)))[..., None]
+    dot = (major[:, None, :] * u).sum(-1)
+    align = torch.where(valid, dot.abs(), torch.zeros_like(dot))
+    key = torch.where(valid, align.detach(), torch.full_like(align, -1.0))       # listed-but-invalid ranks last
+    chosen = torch.ones(N, K, dtype=torch.bool)
+    if used < K:
+        first = torch.sort(key, dim=-1, descending=True, stable=True).indices[:, :used]
+        chosen = torch.zeros(N, K, dtype=torch.bool).scatter_(1, first, True)
+        align = torch.where(chosen, align, torch.zeros_like(align))
+    loss = 1.0 - align.sum() / (N * used)
+    return dict(loss=loss, leaves=(m, q), major=major.detach(), u=u.detach(), n2=n2.detach(), dot=dot.detach(), valid=valid,
+                key=key, chosen=chosen, used=used, nn=nn)
+
+
+def ref_direction_loss(means, quats, log_scales, nn, top_k, dtype=torch.float64):
+    """compute_direction_loss (edge_gs.py:346-373) under torch autograd, written from its formulas: major axis = the
+    column argmax(scale) of R(q / |q|), unit directions to the listed neighbours, loss = 1 - mean_i mean_k |m_i . u_ik|,
+    with 0 < top_k < K the mean over the top_k largest alignments of the row ('enforce_half').  Returns
+    (loss, dmeans [N,3], dquats [N,4]) in `dtype`.
+
+    Where the reference's expression is NaN (0 / 0) or indexes from the end (-1), this function implements THIS
+    PROJECT's documented conventions explicitly instead:
+      * a table entry < 0 and a neighbour at distance exactly 0 contribute alignment 0 and no gradient;
+      * the divisor stays N * used, used = top_k if 0 < top_k < K else K, however many entries contributed;
+      * for the top_k choice such entries rank below every valid one (stable descending sort: ties go to the lower slot);
+      * the major axis is torch.argmax of the log-scales, which takes the FIRST maximum."""
+    t = ref_direction_terms(means, quats, log_scales, nn, top_k, dtype)
+    gm, gq = torch.autograd.grad(t["loss"], t["leaves"])
+    return t["loss"].detach(), gm, gq
+
+
+def ref_ratio_loss(log_scales, dtype=torch.float64):
+    """compute_ratio_loss (edge_gs.py:375-380) under autograd with torch.sort(..., descending=True, stable=True): on
+    ties the gradient goes -r to the first maximum and +r to the first of the rest.  Returns (loss, dlog_scales [N,3])."""
+    s = log_scales.detach().to(dtype).clone().requires_grad_(True)
+    srt, _ = torch.sort(torch.exp(s), dim=-1, descending=True, stable=True)
+    loss = (srt[:, 1] / srt[:, 0]).mean()
+    (g,) = torch.autograd.grad(loss, (s,))
+    return loss.detach(), g
+
+
+def ref_regulariser_step(kind, means, quats, log_scales, nn, top_k, avg_loss_sum, factor, dtype=torch.float64):
+    """One regulariser iteration of train_gaussians.py:108-131 up to the optimizer: lambda = avg_loss_sum * factor / loss,
+    returns (loss, {"means", "quats", "scales": lambda * dloss/dparam}) -- zeros for the blocks outside the loss."""
+    N = means.shape[0]
+    g = {"means": torch.zeros(N, 3, dtype=dtype), "quats": torch.zeros(N, 4, dtype=dtype), "scales": torch.zeros(N, 3, dtype=dtype)}
+    if kind == "direction":
+        loss, gm, gq = ref_direction_loss(means, quats, log_scales, nn, top_k, dtype)
+        lam = avg_loss_sum * factor / loss
+        g["means"], g["quats"] = gm * lam, gq * lam
+    elif kind == "ratio":
+        loss, gs = ref_ratio_loss(log_scales, dtype)
+        lam = avg_loss_sum * factor / loss
+        g["scales"] = gs * lam
+    else:
+        raise ValueError(kind)
+    return loss, g
+
+
+def row_rel_ratio(got, ref64, tol=REG_ROW_TOL):
+    """(largest |got - ref64|_rowmax / (tol * row maximum of ref64) over the rows with a non-zero reference, number of rows
+    over 1, number of all-zero reference rows on which `got` is not exactly zero, per-row ratios)."""
+    ref = to_np(ref64).astype(np.float64).reshape(ref64.shape[0], -1)
+    g = to_np(got).astype(np.float64).reshape(ref.shape)
+    sigma = np.abs(ref).max(axis=1) if ref.size else np.zeros(0)
+    live = sigma > 0
+    ratio = np.zeros_like(sigma)
+    ratio[live] = np.abs(g - ref).max(axis=1)[live] / (tol * sigma[live])
+    nonzero = int((g[~live] != 0).any(axis=1).sum()) if ref.size else 0
+    return float(ratio.max(initial=0.0)), int((ratio > 1.0).sum()), nonzero, ratio
+
+
+def row_rel_check(got, ref64, name, tol=REG_ROW_TOL):
+    """Every row of `got` within tol of its own maximum in the float64 reference; exactly zero where the reference row is."""
+    worst, over, nonzero, _ = row_rel_ratio(got, ref64, tol)
+    assert nonzero == 0, f"{name}: {nonzero} rows are not exactly zero where the float64 reference is"
+    assert worst <= 1.0, f"{name}: {over} rows over {tol} of their own maximum, the worst by {worst:.2f} x"
+    return worst
+
+
+def cpu_knn(points, k, targets=None):
+    """[N,k] int32 nearest `targets` (default: the points themselves, self excluded) in float64, ascending (distance,
+    index); -1 where fewer than k exist -- the layout of regularizers.knn."""
+    p = points.double()
+    t = p if targets is None else targets.double()
+    d2 = ((p[:, None, :] - t[None, :, :]) ** 2).sum(-1)
+    if targets is None:
+        d2.fill_diagonal_(float("inf"))
+    avail = t.shape[0] - (1 if targets is None else 0)
+    order = torch.sort(d2, dim=1, stable=True).indices[:, :k]
+    out = torch.full((p.shape[0], k), -1, dtype=torch.int32)
+    out[:, :min(k, avail)] = order[:, :min(k, avail)].int()
+    return out
+
+
+def reg_curve_scene(n, seed, shuffle=False):
+    """fp32 (means, quats, log_scales): n points in order along four 3-D polylines (six random vertices each) with
+    0.003 noise, quaternions randn * U(0.5, 1.5) (un-normalised), log-scales of 0.004 U(0.7, 1.4) times a permutation of
+    SCALE_RATIOS (one clear major axis).  shuffle: the same rows under a random permutation."""
+    gen = torch.Generator().manual_seed(seed)
+    lines, pts = 4, []
+    for li in range(lines):
+        cnt = n // lines + (1 if li < n % lines else 0)
+        verts = torch.rand(6, 3, generator=gen, dtype=torch.float64)
+        t = torch.linspace(0.0, 5.0, cnt + 2, dtype=torch.float64)[1:-1]
+        seg = t.floor().clamp(max=4).long()
+        f = (t - seg.double())[:, None]
+        pts.append(verts[seg] * (1 - f) + verts[seg + 1] * f)
+    means = torch.cat(pts) + 0.003 * torch.randn(n, 3, generator=gen, dtype=torch.float64)
+    quats = torch.randn(n, 4, generator=gen, dtype=torch.float64) * (0.5 + torch.rand(n, 1, generator=gen, dtype=torch.float64))
+    size = 0.004 * (0.7 + 0.7 * torch.rand(n, 1, generator=gen, dtype=torch.float64))
+    perm = torch.argsort(torch.rand(n, 3, generator=gen), dim=1)
+    ls = torch.log(size * torch.tensor(SCALE_RATIOS, dtype=torch.float64)[perm])
+    if shuffle:
+        p = torch.randperm(n, generator=gen)
+        means, quats, ls = means[p], quats[p], ls[p]
+    return means.float().contiguous(), quats.float().contiguous(), ls.float().contiguous()
+
+
+EDGE_CLASSES = ("duplicate", "ulp", "dot_zero", "dot_zero_partner", "quat_tiny", "quat_huge", "two_equal_major",
+                "two_equal_minor", "three_equal")
+EDGE_PER_CLASS = 4
+EDGES_K = 6
+
+
+def reg_edges_scene(seed=41, n_curve=1024):
+    """`curve` plus EDGE_PER_CLASS rows of every EDGE_CLASSES entry appended behind it.  The curve rows keep the neighbour
+    table of the curve alone (nobody lists an appended row unless stated); an appended row lists its nearest curve rows,
+    with these slots overridden:
+      duplicate        sits exactly on curve row b, which its slot 0 lists (distance 0: no contribution);
+      ulp              pairs A = (0.5, y, z), B = (nextafter(0.5), y, z) that list each other in slot 0 (|gradient| ~ 1e7);
+      dot_zero         identity quaternion, major axis x, its ONLY neighbour (dot_zero_partner) displaced exactly along y;
+      quat_tiny/huge   quaternion norm 1e-3 / 1e3;
+      two_equal_major  log-scales (a, a, b) or (b, a, a), a > b; two_equal_minor (a, b, b); three_equal (a, a, a).
+    Returns (means, quats, log_scales, nn [N, EDGES_K] int32, {class: row indices})."""
+    gen = torch.Generator().manual_seed(seed + 1)
+    means, quats, ls = reg_curve_scene(n_curve, seed)
+    nn_curve = cpu_knn(means, EDGES_K)
+    G = EDGE_PER_CLASS
+    n_new = G * len(EDGE_CLASSES)
+    base = torch.randperm(n_curve, generator=gen)[:n_new]
+    new_m = means[base] + 0.004 * torch.randn(n_new, 3, generator=gen)
+    new_q = torch.randn(n_new, 4, generator=gen) * (0.5 + torch.rand(n_new, 1, generator=gen))
+    new_ls = ls[base].clone()
+    rows = {c: list(range(n_curve + i * G, n_curve + (i + 1) * G)) for i, c in enumerate(EDGE_CLASSES)}
+    loc = {c: slice(i * G, (i + 1) * G) for i, c in enumerate(EDGE_CLASSES)}
+    new_m[loc["duplicate"]] = means[base[loc["duplicate"]]]
+    a = new_m[loc["ulp"]].clone()
+    a[:, 0] = 0.5
+    a[G // 2:] = a[:G // 2]
+    a[G // 2:, 0] = torch.nextafter(torch.tensor(0.5), torch.tensor(1.0))
+    new_m[loc["ulp"]] = a
+    new_q[loc["dot_zero"]] = torch.tensor([1.0, 0.0, 0.0, 0.0])
+    new_ls[loc["dot_zero"]] = torch.log(torch.tensor([0.016, 0.005, 0.004]))
+    p = new_m[loc["dot_zero"]].clone()
+    p[:, 1] += 0.003 * (1.0 + torch.rand(G, generator=gen))
+    new_m[loc["dot_zero_partner"]] = p
+    for c, s in (("quat_tiny", 1e-3), ("quat_huge", 1e3)):
+        q = new_q[loc[c]]
+        new_q[loc[c]] = q / q.norm(dim=1, keepdim=True) * s
+    hi, lo = math.log(0.012), math.log(0.004)
+    new_ls[loc["two_equal_major"]] = torch.tensor([[hi, hi, lo], [lo, hi, hi]] * (G // 2))
+    new_ls[loc["two_equal_minor"]] = torch.tensor([[hi, lo, lo], [lo, hi, lo]] * (G // 2))
+    new_ls[loc["three_equal"]] = torch.full((G, 3), lo)
+    nn_new = cpu_knn(new_m, EDGES_K, targets=means)
+    for k, r in enumerate(range(loc["ulp"].start, loc["ulp"].stop)):
+        nn_new[r, 0] = n_curve + loc["ulp"].start + (k + G // 2) % G
+    for k, r in enumerate(range(loc["dot_zero"].start, loc["dot_zero"].stop)):
+        nn_new[r] = -1
+        nn_new[r, 0] = rows["dot_zero_partner"][k]
+    out = (torch.cat([means, new_m]).contiguous(), torch.cat([quats, new_q]).contiguous(), torch.cat([ls, new_ls]).contiguous(),
+           torch.cat([nn_curve, nn_new]).contiguous(), rows)
+    return out
+
+
+REG_SIZES = (1, 2, 255, 256, 257, 1000)
+REG_SIZE_SEEDS = {1: 201, 2: 202, 255: 459, 256: 458, 257: 462, 1000: 1202}   # seeds whose scenes meet reg_conditions
+REG_SIZE_KS = (1, 5, 20)
+REG_BLOCK_N, REG_BLOCK_K = 2048, 10
+REG_K32_N = 600
+_reg_cache = {}
+
+
+def reg_scene(name):
+    """(means, quats, log_scales, nn or None, edge rows or None) of a named scene, built once per process: "curve",
+    "shuffled" (REG_BLOCK_N rows, REG_BLOCK_K neighbours), "edges", "k32" (synthetic table: the row itself in slot 0, a
+    repeated index in slots 1-2, random rows elsewhere) and "size<N>" (no table: the caller searches the K it needs)."""
+    if name in _reg_cache:
+        return _reg_cache[name]
+    if name in ("curve", "shuffled"):
+        m, q, s = reg_curve_scene(REG_BLOCK_N, 33, shuffle=name == "shuffled")
+        out = (m, q, s, cpu_knn(m, REG_BLOCK_K), None)
+    elif name == "edges":
+        out = reg_edges_scene()
+    elif name == "k32":
+        m, q, s = reg_curve_scene(REG_K32_N, 37)
+        nn = torch.randint(0, REG_K32_N, (REG_K32_N, 32), generator=torch.Generator().manual_seed(38), dtype=torch.int32)
+        nn[:, 0] = torch.arange(REG_K32_N, dtype=torch.int32)
+        nn[:, 2] = nn[:, 1]
+        out = (m, q, s, nn.contiguous(), None)
+    elif name.startswith("size"):
+        n = int(name[4:])
+        out = reg_curve_scene(n, REG_SIZE_SEEDS[n]) + (None, None)
+    else:
+        raise KeyError(name)
+    _reg_cache[name] = out
+    return out
+
+
+def reg_top_ks(K):
+    """0, K/2, K and K + 1 (the last two must equal the full method)"""
+    return sorted({0, K // 2, K, K + 1})
+
+
+def reg_reference(name, nn=None, top_k=0, tag="cpu"):
+    """float64 (loss, dmeans, dquats) of a named scene, computed once per (scene, table tag, top_k) and never modified.
+    `nn`: the table to use where the scene has none of its own ("size<N>": `tag` names it)."""
+    m, q, s, nn_own, _ = reg_scene(name)
+    nn = nn_own if nn is None else nn
+    key = ("ref", name, tag, tuple(nn.shape), top_k)
+    if key not in _reg_cache:
+        _reg_cache[key] = ref_direction_loss(m, q, s, nn, top_k)
+    return _reg_cache[key]
+
+
+def reg_conditions(means, quats, log_scales, nn, top_k):
+    """What a direction-loss comparison rests on, from the float64 reference: (smallest non-zero |dot| over the valid
+    entries, smallest top_k selection gap -- key of the last chosen minus key of the first entry left out, over the rows
+    where the two are not interchangeable (both invalid, or the same neighbour) --, number of valid entries with dot
+    exactly 0).  A |dot| or a gap below fp32 rounding would let two correct evaluations differ by a whole term."""
+    t = ref_direction_terms(means, quats, log_scales, nn, top_k)
+    dot, valid, key, used, nn = t["dot"], t["valid"], t["key"], t["used"], t["nn"]
+    K = nn.shape[1]
+    a = dot.abs()[valid]
+    min_dot = float(a[a > 0].min()) if (a > 0).any() else float("inf")
+    gap = float("inf")
+    if used < K:
+        srt = torch.sort(key, dim=-1, descending=True, stable=True)
+        k_in, k_out = srt.values[:, used - 1], srt.values[:, used]
+        j_in, j_out = nn.gather(1, srt.indices[:, used - 1:used])[:, 0], nn.gather(1, srt.indices[:, used:used + 1])[:, 0]
+        same = ((k_in < 0) & (k_out < 0)) | ((j_in == j_out) & (k_in == k_out))
+        if (~same).any():
+            gap = float((k_in - k_out)[~same].min())
+    return min_dot, gap, int(((dot == 0) & valid).sum())
+
+
+def reg_survival(means, quats, log_scales, nn, top_k, grads64):
+    """How much of each gradient row is left of what was summed into it, from the float64 reference: (s_means [N],
+    s_quats [N]).  dmeans row i sums one term of size <= w / |d| per contributing (row, neighbour) pair that involves i
+    (its own and those of the rows that list it); s_means = |row| / that sum of bounds.  dquats row i is the tangent
+    part of a sum of unit directions pulled back through R(q / |q|) (factor 2 / |q|): s_quats = |row| |q| / (2 w n_i), n_i
+    the number of contributing neighbours.  w = 1 / (N used).  1 where a row has no term.  Every term is computed to
+    ~1e-7 of its bound in fp32, so relative to the row itself the rounding is ~1e-7 / s: small s = the row is a small
+    remainder (an aligned Gaussian: sin of a small angle, neighbours on both sides cancelling, the radial part of the
+    quaternion gradient projected out)."""
+    t = ref_direction_terms(means, quats, log_scales, nn, top_k)
+    on = (t["valid"] & t["chosen"]).double()
+    N = on.shape[0]
+    w = 1.0 / (N * t["used"])
+    inv_d = on / torch.sqrt(torch.where(t["valid"], t["n2"], torch.ones_like(t["n2"])))
+    mag = inv_d.sum(1).index_add(0, t["nn"].clamp(min=0).reshape(-1), inv_d.reshape(-1)) * w
+    gm, gq = grads64
+    one = torch.ones(N, dtype=torch.float64)
+    sm = torch.where(mag > 0, gm.double().norm(dim=1) / mag.clamp(min=1e-300), one)
+    cnt = on.sum(1)
+    sq = torch.where(cnt > 0, gq.double().norm(dim=1) * quats.double().norm(dim=1) / (2.0 * w * cnt.clamp(min=1)), one)
+    return sm.numpy(), sq.numpy()
+
+
+# The `edges` scene only: a row of which less than REG_SMALL_REMAINDER is left (reg_survival) is a SMALL-REMAINDER row:
+# fp32 rounding of its terms, ~1e-7 of their bound each, is then more than ~1e-5 of the row, which a quarter of 1e-4
+# cannot be promised to hold.  Such rows are named, counted, at most REG_REMAINDER_CAP of the rows, and held to 1e-4 of
+# the TENSOR's maximum instead.  A row that is exactly zero in the reference is never in the class.
+REG_SMALL_REMAINDER = 1.0 / 128
+REG_REMAINDER_CAP = 0.01
+
+
+def same_block_share(nn, block=256):
+    """share of the listed (>= 0) table entries that lie in the row's own block of `block` rows"""
+    nn = torch.as_tensor(to_np(nn)).long()
+    row = torch.arange(nn.shape[0])[:, None].expand_as(nn)
+    listed = nn >= 0
+    return float(((nn // block == row // block) & listed).sum() / max(int(listed.sum()), 1))
+
+
+def adam_first_step_deltas(params, grads64, lrs, betas=(0.9, 0.999), eps=1e-8, dtype=torch.float64):
+    """{name: parameter delta} of ONE torch.optim.Adam step from zero moments, run in `dtype` on the float64 gradients"""
+    out = {}
+    for k, p in params.items():
+        P = torch.nn.Parameter(p.detach().to(dtype).clone())
+        P.grad = grads64[k].to(dtype).reshape(P.shape).clone()
+        torch.optim.Adam([P], lr=lrs[k], betas=betas, eps=eps).step()
+        out[k] = (P.detach().double() - p.detach().double())
+    return out
+
+
+def adam_delta_ratio(delta, delta64, g64, lr):
+    """(largest |delta - delta64| / (1e-4 lr) over the compared elements, share of elements left out: 0 < |g64| < 100 eps)"""
+    g = to_np(g64).astype(np.float64).reshape(-1)
+    skip = (np.abs(g) > 0) & (np.abs(g) < ADAM_SKIP_BELOW)
+    err = np.abs(to_np(delta).astype(np.float64).reshape(-1) - to_np(delta64).astype(np.float64).reshape(-1))
+    return float((err[~skip] / (1e-4 * lr)).max(initial=0.0)), float(skip.mean()) if skip.size else 0.0
+
+
+# The trainer-level regulariser cases: a fresh trainer (zero moments), one step with a host avg_loss_sum.  The learning rates
+# are chosen so that 1e-4 lr exceeds half an ulp of the stored fp32 parameter (|mean| < 1: 3e-8, |log-scale| < 8: 2.4e-7,
+# |quat| < 8: 2.4e-7) -- below that no fp32 parameter can meet the delta bound, whatever computed it -- and pairwise
+# distinct, so that a learning rate applied to the wrong block shows.
+REG_STEP_LRS = dict(means_lr=2e-3, scales_lr=2e-2, quats_lr=1e-2, opacities_lr=3e-2)
+REG_STEP_AVG_LOSS_SUM = 400.0
+REG_STEP_FACTOR = 0.01
+REG_STEP_NN = 5
+REG_STEP_SEED = 3             # (a seed whose scene meets reg_conditions for both neighbour methods)
+REG_STEP_CASES = (("direction", "enforce_full"), ("direction", "enforce_half"), ("ratio", "enforce_full"))
+
+
+def reg_step_scene():
+    if "step_scene" not in _reg_cache:
+        from edgegaussians_amd import synth
+        _reg_cache["step_scene"] = synth.make_scene(1500, 2, 96, 80, seed=REG_STEP_SEED, spread_opacity=True, scale=0.02, anisotropy=5.0)
+    return _reg_cache["step_scene"]
+
+
+def reg_step_table(method):
+    """the trainer's table for `method` on the CPU: [N, K + 1] nearest others, of which columns 1 .. K are used"""
+    sc = reg_step_scene()
+    key = ("step_table", method)
+    if key not in _reg_cache:
+        n = 2 * REG_STEP_NN + 1 if method == "enforce_half" else REG_STEP_NN + 1
+        _reg_cache[key] = cpu_knn(sc.means, n)
+    return _reg_cache[key]
+
+
+# ---------------------------------------------------------------------------------------------------
+# densify / cull
+VOTE_SIZE = (40, 24)          # W != H
+VOTE_HALF_MARGIN = 1e-4       # px: a projected coordinate this close to a half-integer is borderline
+VOTE_C_MARGIN = 1e-6          # |c| below this is borderline
+VOTE_MAX_BORDER = 0.01
+SCAN_SIZES = (0, 1, 63, 64, 65, 1023, 1024, 1025, 2047, 2048, 2049, 5000)
+
+
+def scan_masks(n, seed=5):
+    """{name: uint8 [n]} the mask cases of the scan / row-mover tests"""
+    gen = torch.Generator().manual_seed(seed + n)
+    out = {"zeros": torch.zeros(n, dtype=torch.uint8), "ones": torch.ones(n, dtype=torch.uint8),
+           "half": (torch.rand(n, generator=gen) < 0.5).to(torch.uint8), "sparse": (torch.rand(n, generator=gen) < 0.01).to(torch.uint8),
+           "last": torch.zeros(n, dtype=torch.uint8), "byte1024": torch.zeros(n, dtype=torch.uint8),
+           "values": torch.tensor([0, 2, 255, 0, 1], dtype=torch.uint8)[torch.randint(0, 5, (n,), generator=gen)]}
+    if n:
+        out["last"][-1] = 1
+    if n > 1024:
+        out["byte1024"][1024] = 1
+    return out
+
+
+def ref_mask_scan(mask):
+    """(exclusive prefix count of the non-zero bytes [n] int32, their number)"""
+    nz = (torch.as_tensor(mask) != 0).long()
+    c = torch.cumsum(nz, 0)
+    return (c - nz).int(), int(nz.sum())
+
+
+def _rint_votes(a, b, c, W, H):
+    """float64: (pixel x, pixel y, inside, borderline) of u = a / c, v = b / c rounded half to even"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u, v = a / c, b / c
+    ru, rv = np.rint(u), np.rint(v)
+    inside = (ru >= 0) & (ru < W) & (rv >= 0) & (rv < H)      # NaN / inf compare false
+    with np.errstate(invalid="ignore"):
+        near = lambda t: np.abs(np.abs(t - np.floor(t)) - 0.5) < VOTE_HALF_MARGIN  # noqa: E731
+        border = np.where(np.isfinite(u) & np.isfinite(v), near(u) | near(v), False) | (np.abs(c) < VOTE_C_MARGIN)
+    x = np.where(inside, ru, 0).astype(np.int64)
+    y = np.where(inside, rv, 0).astype(np.int64)
+    return x, y, inside, border
+
+
+def ref_project_hits(means, P, masks, W, H, per_view=False):
+    """cull_gaussians_not_projecting's vote (edge_gs.py:587-596) in float64: P [V,3,4] = K @ viewmat[:3,:4], [x y z 1] P^T,
+    divide, round half to even, inside the image, edge mask non-zero there -- no depth test: c < 0 votes where it lands.
+    Returns (votes [N] int64, borderline [N] bool: some view's coordinate within VOTE_HALF_MARGIN px of a half-integer
+    or |c| < VOTE_C_MARGIN); per_view: both as [N,V]."""
+    X = to_np(means).astype(np.float64)
+    P, masks = to_np(P).astype(np.float64).reshape(-1, 3, 4), to_np(masks)
+    votes, border = np.zeros((X.shape[0], P.shape[0]), np.int64), np.zeros((X.shape[0], P.shape[0]), bool)
+    for v in range(P.shape[0]):
+        h = X @ P[v, :, :3].T + P[v, :, 3]
+        x, y, inside, b = _rint_votes(h[:, 0], h[:, 1], h[:, 2], W, H)
+        votes[:, v] = inside & (masks[v][y, x] != 0)
+        border[:, v] = b
+    return (votes, border) if per_view else (votes.sum(axis=1), border.any(axis=1))
+
+
+def ref_project_visibility(means, cams, maps, W, H, visib_in=None):
+    """filter_by_projection's sum (filtering.py:80-123) in float64: x = K (R X + t), divide, np.round, the float32 edge
+    strengths of the views the point lands in summed in view order into float64.  cams [V,21] = K | R | t.
+    Returns (visib [N] float64, borderline [N] bool)."""
+    X = to_np(means).astype(np.float64)
+    cams, maps = to_np(cams).astype(np.float64), to_np(maps)
+    vis = np.zeros(X.shape[0], np.float64)
+    border = np.zeros(X.shape[0], bool)
+    for v in range(cams.shape[0]):
+        K, R, t = cams[v, :9].reshape(3, 3), cams[v, 9:18].reshape(3, 3), cams[v, 18:21]
+        h = (X @ R.T + t) @ K.T
+        x, y, inside, b = _rint_votes(h[:, 0], h[:, 1], h[:, 2], W, H)
+        vis += np.where(inside, maps[v][y, x].astype(np.float64), 0.0)
+        border |= b
+    return (vis if visib_in is None else to_np(visib_in).astype(np.float64) + vis), border
+
+
+def vote_scene(n, V, seed=61):
+    """(means [n,3], P [V,3,4], cams [V,21], byte masks [V,H,W] with values 0 / 1 / 255, float maps [V,H,W]) on VOTE_SIZE:
+    look-at cameras; half of the rows in the unit box (inside every image), half in a box of edge 9 round it (outside
+    the image in most views, behind the camera in some), a sixteenth behind camera 0 where they still land inside."""
+    from edgegaussians_amd import synth
+    W, H = VOTE_SIZE
+    gen = torch.Generator().manual_seed(seed + 7 * n + V)
+    vms, Ks = synth.lookat_cameras(V, W, H, gen)
+    means = torch.rand(n, 3, generator=gen)
+    wide = torch.rand(n, generator=gen) < 0.5
+    means[wide] = (means[wide] - 0.5) * 9.0 + 0.5
+    nb = n // 16                                   # ... and a sixteenth BEHIND camera 0 near its axis: c < 0, inside the image
+    R0, t0 = vms[0, :3, :3], vms[0, :3, 3]
+    back = torch.rand(nb, 3, generator=gen) * torch.tensor([0.3, 0.2, 2.0]) + torch.tensor([-0.15, -0.1, -3.0])
+    means[:nb] = (back - t0) @ R0                  # camera space -> world: R^T (p - t)
+    P = torch.bmm(Ks, vms[:, :3, :4]).contiguous()
+    cams = torch.cat([Ks.reshape(V, 9), vms[:, :3, :3].reshape(V, 9), vms[:, :3, 3]], dim=1).contiguous()
+    masks = torch.tensor([0, 1, 255], dtype=torch.uint8)[torch.randint(0, 3, (V, H, W), generator=gen)]
+    maps = torch.rand(V, H, W, generator=gen)
+    return means.contiguous(), P, cams, masks.contiguous(), maps.contiguous()
+
+
+def exact_vote_block():
+    """Rows whose projection is exact in fp32 (identity view matrix, focal length 8, principal point (4, 2), z = +-1 or 0):
+    (means [n,3], P [1,3,4], cams [1,21], mask [1,H,W] -- non-zero where x + y is even --, expected votes [n] int64,
+    expected pixel (x, y) or (-1, -1) [n,2]).  u = 0.5 -> 0, 1.5 -> 2, 2.5 -> 2, -0.5 -> -0 (pixel 0, inside),
+    W - 0.5 -> W (outside for even W), likewise in v; c < 0 votes where it lands; c == 0 with a != 0 does not vote."""
+    W, H = VOTE_SIZE
+    f, cx, cy = 8.0, 4.0, 2.0
+    K = torch.tensor([[f, 0.0, cx], [0.0, f, cy], [0.0, 0.0, 1.0]])
+    vm = torch.eye(4)
+    rows = []   # (u, v, z, expected pixel or None)
+    halves = ((0.5, 0), (1.5, 2), (2.5, 2), (-0.5, 0))
+    for u, px in halves:
+        for v, py in halves:
+            rows.append((u, v, 1.0, (px, py)))
+        rows.append((u, 3.0, 1.0, (px, 3)))
+        rows.append((5.0, u, 1.0, (5, px)))
+    rows += [(W - 0.5, 3.0, 1.0, None), (3.0, H - 0.5, 1.0, None), (W - 1.5, H - 1.5, 1.0, (W - 2, H - 2)),
+             (-1.5, 3.0, 1.0, None), (3.0, -1.5, 1.0, None)]
+    rows += [(6.5, 3.5, -1.0, (6, 4)), (7.0, 2.0, -1.0, (7, 2)), (8.0, 5.0, -1.0, (8, 5))]       # c < 0: votes
+    rows += [(6.0, 6.0, 0.0, None), (-3.0, 2.0, 0.0, None)]                                        # c == 0, a != 0
+    means, want = [], []
+    for u, v, z, pix in rows:
+        if z == 0.0:
+            means.append((u / f, v / f, 0.0))           # a = f x = u != 0, c = 0
+        else:
+            means.append(((u - cx) * z / f, (v - cy) * z / f, z))   # a = f x + cx z = u z, c = z
+        want.append(pix if pix is not None else (-1, -1))
+    means = torch.tensor(means, dtype=torch.float32)
+    want = torch.tensor(want, dtype=torch.int64)
+    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    mask = (((xx + yy) % 2) == 0).to(torch.uint8)[None].contiguous()
+    votes = torch.where(want[:, 0] >= 0, ((want[:, 0] + want[:, 1]) % 2 == 0).long(), torch.zeros(len(rows), dtype=torch.int64))
+    P = (K @ vm[:3, :4])[None].contiguous()
+    cams = torch.cat([K.reshape(1, 9), vm[:3, :3].reshape(1, 9), vm[:3, 3].reshape(1, 3)], dim=1).contiguous()
+    return means.contiguous(), P, cams, mask, votes, want
+
+
+DENSIFY_NAMES = ("means", "scales", "quats", "opacities")
+DENSIFY_DIMS = dict(means=3, scales=3, quats=4, opacities=1)
+
+
+def densify_case(seed=75, n=2500):
+    """Everything the trainer-level densify test needs, in the REFERENCE's row order: the scene, live moments and absgrads,
+    a cull mask, a duplication mask (over the survivors) with its noise, and byte edge masks."""
+    from edgegaussians_amd import synth
+    key = ("densify", seed, n)
+    if key in _reg_cache:
+        return _reg_cache[key]
+    W, H = VOTE_SIZE
+    sc = synth.make_scene(n, 4, W, H, seed=seed, spread_opacity=True, scale=0.02)
+    gen = torch.Generator().manual_seed(seed + 1)
+    state = {"means": sc.means.clone(), "scales": sc.log_scales.clone(), "quats": sc.quats.clone(),
+             "opacities": sc.logit_opacities.reshape(-1, 1).clone()}
+    for k in DENSIFY_NAMES:
+        state["m_" + k] = torch.randn(n, DENSIFY_DIMS[k], generator=gen) * 1e-2
+        state["v_" + k] = torch.rand(n, DENSIFY_DIMS[k], generator=gen) * 1e-3
+    state["absgrads"] = torch.rand(n, generator=gen) + 0.1
+    cull_mask = torch.rand(n, generator=gen) < 0.3
+    n1 = int((~cull_mask).sum())
+    dup_mask = torch.rand(n1, generator=gen) < 0.2
+    noise = torch.randn(2 * int(dup_mask.sum()), 3, generator=gen)
+    masks = torch.tensor([0, 1, 255], dtype=torch.uint8)[torch.multinomial(torch.tensor([0.7, 0.15, 0.15]), 4 * H * W, True,
+                                                                           generator=gen)].view(4, H, W).contiguous()
+    out = dict(scene=sc, state=state, cull_mask=cull_mask, dup_mask=dup_mask, noise=noise, masks=masks)
+    _reg_cache[key] = out
+    return out
+
+
+def emulate_densify(case, reset_opacity_value=0.08, dup_factor=3, noise_scale=0.05, min_fraction=0.1):
+    """cull -> duplicate -> cull_not_projecting with torch boolean indexing / cat on the CPU (edge_gs.py:384-474,578-601):
+    returns (the 13 per-Gaussian arrays after each of the three events, the rows whose LAST cull decision hinges on a
+    borderline view of the vote: the decision differs between that view voting and not voting)."""
+    sc, W, H = case["scene"], *VOTE_SIZE
+    st = {k: v.clone() for k, v in case["state"].items()}
+
+    def cull(st, mask):
+        st = {k: v[~mask].clone() for k, v in st.items()}
+        st["opacities"] = st["opacities"].clamp(max=reset_opacity_value)
+        return st
+
+    after = []
+    st = cull(st, case["cull_mask"])
+    after.append({k: v.clone() for k, v in st.items()})
+    sel, copies = case["dup_mask"], dup_factor - 1
+    for k in DENSIFY_NAMES:
+        new = torch.cat([st[k][sel]] * copies)
+        if k == "means":
+            new = new + case["noise"] * noise_scale
+        st[k] = torch.cat([st[k], new])
+        for mv in ("m_", "v_"):
+            st[mv + k] = torch.cat([st[mv + k], torch.zeros(new.shape)])
+    st["absgrads"] = torch.zeros(st["means"].shape[0])
+    after.append({k: v.clone() for k, v in st.items()})
+    P = torch.bmm(sc.Ks, sc.viewmats[:, :3, :4])
+    votes, border = ref_project_hits(st["means"], P, case["masks"], W, H, per_view=True)
+    V = float(sc.viewmats.shape[0])
+    frac = torch.from_numpy(votes.sum(axis=1)).float() / V
+    lo, hi = (votes & ~border).sum(axis=1) / V, (votes | border).sum(axis=1) / V
+    st = cull(st, frac < min_fraction)
+    after.append(st)
+    return after, (lo < min_fraction) != (hi < min_fraction)
