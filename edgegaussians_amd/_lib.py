@@ -147,6 +147,8 @@ _SIGS = {
                       C.POINTER(_i32), _vp],
     "eg_packed_bwd": [_vp] * 6 + [_i32, _i32, _i32, _i32, _f, _u32, _vp, _i64] + [_vp] * 7 + [_vp],
     "eg_packed_bwd_sparse": [_vp] * 6 + [_i32, _i32, _i32, _i32, _f, _u32, _i64] + [_vp] * 8 + [_vp],
+    "eg_project_bwd_viewmats": [_vp] * 6 + [_i32, _i32, _i32, _i32, _f, _u32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32,
+                                _vp, _vp],
     "eg_sh_fwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp],
     "eg_sh_bwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "eg_train_step_batched": [C.POINTER(StepArgs), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp],

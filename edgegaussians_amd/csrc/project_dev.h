@@ -182,9 +182,15 @@ struct Grads {
   float mean[3], quat[4], scale[3], opac;
 };
 
+// CAM (csrc/viewmat_grad.hip): the same sweep stops at the camera-space cotangents and leaves the CAMERA's share in
+// v_cam[12] -- rows of [v_R | v_tr], v_R[i][j] = v_t[i] mean[j] + sum_k vW[3 i + k] M[j][k] with M = Rq diag(s) (the
+// transpose-side product of W = Rv M), v_tr = v_t -- from the world mean `mean`; `o` is not touched.  The default
+// instantiation is the function every other kernel inlines, instruction for instruction.
+template <bool CAM = false>
 __device__ __forceinline__ void backward_geom(const Cam &cam, const Fwd &f, float eps2d, uint32_t flags,
                                               const float4 ga, const float4 gb, bool ext, float v_comp_ext,
-                                              float v_depth_ext, Grads &o) {
+                                              float v_depth_ext, Grads &o, float *v_cam = nullptr,
+                                              const float *mean = nullptr) {
 #pragma clang fp contract(off)  // (one rounding sequence in every kernel: see forward_geom)
   const float vx = ga.x, vy = ga.y;
   const float va = gb.x, vb = gb.y, vc = gb.z, vo_eff = gb.w;
@@ -241,6 +247,18 @@ __device__ __forceinline__ void backward_geom(const Cam &cam, const Fwd &f, floa
   else        { vtz += cam.fx * f.tx * rz3 * vJ02; }
   if (f.in_y) { vty += -cam.fy * f.rz2 * vJ12; vtz += 2.f * cam.fy * f.ty * rz3 * vJ12; }
   else        { vtz += cam.fy * f.ty * rz3 * vJ12; }
+  if constexpr (CAM) {
+    const float vt[3] = {vtx, vty, vtz};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        v_cam[4 * i + j] = vt[i] * mean[j] + (vW[3 * i] * (f.Rq[3 * j] * f.s[0]) + vW[3 * i + 1] * (f.Rq[3 * j + 1] * f.s[1]) +
+                                              vW[3 * i + 2] * (f.Rq[3 * j + 2] * f.s[2]));
+      v_cam[4 * i + 3] = vt[i];
+    }
+    return;
+  }
   o.mean[0] = cam.R[0] * vtx + cam.R[3] * vty + cam.R[6] * vtz;
   o.mean[1] = cam.R[1] * vtx + cam.R[4] * vty + cam.R[7] * vtz;
   o.mean[2] = cam.R[2] * vtx + cam.R[5] * vty + cam.R[8] * vtz;

@@ -98,7 +98,16 @@ class _Projection(torch.autograd.Function):
         call("eg_project_bwd_cams", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d,
              flags, ptr(splat), ptr(g2d), ptr(vcomp), ptr(vdep) if vdep is not None else None, ptr(v_means), ptr(v_quats),
              ptr(v_scales), stream())
-        return (v_means, v_quats, v_scales) + (None,) * 10
+        v_viewmats = None
+        if ctx.needs_input_grad[4]:  # (a pose optimiser: nobody else pays for these two kernels)
+            v_viewmats = torch.zeros(Cn, 4, 4, device=dev)
+            if N > 0:  # (the entry tells the dense layout by its record, and without Gaussians there is none: zeros)
+                blocks = math.ceil(N / 256)
+                scratch = torch.empty(Cn, blocks, 12, device=dev)
+                call("eg_project_bwd_viewmats", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width,
+                     height, eps2d, flags, ptr(splat), None, 0, None, ptr(g2d), ptr(vcomp), ptr(vdep), ptr(scratch), blocks,
+                     ptr(v_viewmats), stream())
+        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 8
 
 
 _DUMMY: Dict = {}
@@ -195,7 +204,15 @@ class _PackedProjection(torch.autograd.Function):
             call("eg_packed_bwd", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d,
                  flags, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means), ptr(v_quats),
                  ptr(v_scales), stream())
-        return (v_means, v_quats, v_scales) + (None,) * 12
+        v_viewmats = None
+        if ctx.needs_input_grad[4]:  # (always dense [C, 4, 4], with `sparse_grad` as well)
+            blocks = math.ceil(min(nnz, N) / 256)
+            scratch = torch.empty(Cn, blocks, 12, device=dev)
+            v_viewmats = torch.empty(Cn, 4, 4, device=dev)
+            call("eg_project_bwd_viewmats", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width,
+                 height, eps2d, flags, None, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d),
+                 ptr(vcomp), ptr(vdep), ptr(scratch), blocks, ptr(v_viewmats), stream())
+        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 10
 
 
 class _Compositing(torch.autograd.Function):
@@ -883,7 +900,7 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
     nnz = indptr[-1]
     if colors is not None:
         if sh_degree is not None:
-            with torch.no_grad():
+            with torch.set_grad_enabled(torch.is_grad_enabled() and viewmats.requires_grad):  # (the poses' gradient, if asked for)
                 campos = torch.linalg.inv_ex(viewmats)[0][:, :3, 3]  # (torch.linalg.inv without its host read of `info`)
             dirs = means[gaussian_ids] - campos[camera_ids]
             coeffs = colors[gaussian_ids] if colors.dim() == 3 else colors[camera_ids, gaussian_ids]
@@ -980,12 +997,20 @@ def rasterization(
     several it is the sum of the chunks' abs-gradients (each chunk's share of dL/dmeans2d enters with its own absolute
     value).  What gsplat 1.0.0 itself leaves there for D > channel_chunk could not be checked against gsplat.
 
+    ``viewmats`` is a differentiable input, as in gsplat: when it requires grad it receives ``[C, 4, 4]`` -- the
+    projection's share, with an exactly zero bottom row, summed over the visible pairs of each camera by two kernels of
+    their own (csrc/viewmat_grad.hip: no atomics, the same bits every run, dense also with ``sparse_grad``), plus, with
+    ``sh_degree``, the view directions' share through ``inverse(viewmats)`` (torch's backward of the inverse, which
+    fills the bottom row too).  Such a call never takes the unit-colour fast path; the projection backward gives
+    ``means``, ``quats`` and ``scales`` the bits it gives without it.  ``Ks`` receives none.
+
     ``sh_degree`` = L (0..4): ``colors`` holds spherical-harmonics coefficients, [N, K, 3] shared by the cameras or
     [C, N, K, 3], fp32 on the device, ``(L + 1) ** 2 <= K`` (the rows above are ignored and get zero gradient); anything
     else is a ValueError.  The colour of Gaussian n in camera c is ``clamp_min(SH(means[n] - campos[c]) + 0.5, 0)``
     with ``campos = inverse(viewmats)[:, :3, 3]`` where ``radii[c, n] > 0`` and 0 elsewhere (csrc/sh.hip); the
     coefficients receive their gradient (summed over the cameras when shared), ``means`` receives the direction's on
-    top of the projection's, ``viewmats`` none.  These 3-channel colours take the general path (never the fast one),
+    top of the projection's, and so does ``viewmats`` (through ``campos``) when it requires grad.  These 3-channel
+    colours take the general path (never the fast one),
     so every render mode and ``backgrounds`` work with it; "D" / "ED" do not evaluate the harmonics.
 
     ``render_mode``: "RGB", "D", "ED", "RGB+D" or "RGB+ED", as in gsplat: the "+D" modes append the projection depth
@@ -1041,8 +1066,9 @@ def rasterization(
                                    far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree)
 
     if (sh_degree is None and Cn == 1 and colors.dim() == 2 and not colors.requires_grad and float(eps2d) == 0.3 and float(near_plane) == 0.01
-            and float(far_plane) == 1e10 and float(radius_clip) == 0.0 and N > 0 and _FAST_ENABLED):
-        # the reference's own call (edge_gs.py:247-268): colours torch.ones(N, 3) without grad, one camera
+            and float(far_plane) == 1e10 and float(radius_clip) == 0.0 and N > 0 and _FAST_ENABLED and not viewmats.requires_grad):
+        # the reference's own call (edge_gs.py:247-268): colours torch.ones(N, 3) without grad, one camera (and a fixed
+        # one: the fast path's single node has no pose gradient, a camera that requires grad takes the general path)
         out = _fast_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, absgrad, antialiased)
         if out is not None:
             return out

@@ -101,11 +101,33 @@ def check_view_coeffs(coeffs: Tensor, sh_degree, Cn: int, N: int) -> int:
     return check_degree(sh_degree, coeffs.shape[-2])
 
 
+class _CameraDirs(torch.autograd.Function):
+    """dirs [C, N, 3] = means[n] - campos[c], for the call whose `campos` needs a gradient.  Backward: `means` receives
+    the sum over the cameras in camera order -- the order, hence the bits, of eg_sh_bwd's own sum in its means / campos
+    form -- and `campos` minus the sum over the Gaussians."""
+
+    @staticmethod
+    def forward(ctx, means, campos):
+        return means[None] - campos[:, None]
+
+    @staticmethod
+    def backward(ctx, v_dirs):
+        v_means = v_dirs[0].clone()
+        for c in range(1, v_dirs.shape[0]):
+            v_means += v_dirs[c]
+        return v_means, -v_dirs.sum(1)
+
+
 def view_colors(means: Tensor, viewmats: Tensor, coeffs: Tensor, radii: Tensor, sh_degree: int) -> Tensor:
     """The colours ``rasterization`` composites with ``sh_degree``: [C, N, 3] =
     clamp_min(SH(means - campos[c]) + 0.5, 0) where radii [C, N] > 0, else 0.  campos = inverse(viewmats)[:, :3, 3],
-    on the device without a host sync; ``viewmats`` receives no gradient."""
-    with torch.no_grad():
+    on the device without a host sync.  ``viewmats`` that require grad receive the directions' gradient through
+    ``campos`` (the `dirs` form of `_SH` behind `_CameraDirs`); otherwise the kernels form the directions themselves."""
+    pose_grad = torch.is_grad_enabled() and viewmats.requires_grad
+    with torch.set_grad_enabled(pose_grad):
         campos = torch.linalg.inv_ex(viewmats)[0][:, :3, 3]  # (torch.linalg.inv without its host read of `info`)
+    with torch.no_grad():
         masks = radii > 0
+    if pose_grad:
+        return _SH.apply(sh_degree, _CameraDirs.apply(means, campos), None, None, coeffs, masks, True)
     return _SH.apply(sh_degree, None, means, campos, coeffs, masks, True)

@@ -4,7 +4,8 @@ resolves to the MI355X-native implementation, so the reference's model class run
 The reference imports ``rasterization`` alone; ``spherical_harmonics`` is there for the other callers of gsplat, whose
 ``rasterization(..., sh_degree=L)`` calls it serves as well.  ``rasterization`` takes gsplat's defaults, ``packed=True``
 included (only the visible (camera, Gaussian) pairs are kept; ``info["camera_ids"]`` / ``info["gaussian_ids"]`` name
-them), and ``sparse_grad=True`` on top of it; ``tile_size`` other than 16 is the one argument it refuses."""
+them), and ``sparse_grad=True`` on top of it; ``viewmats`` that require grad receive their ``[C, 4, 4]`` gradient (pose
+optimisation); ``tile_size`` other than 16 is the one argument it refuses."""
 from edgegaussians_amd.rasterizer import rasterization  # noqa: F401
 from edgegaussians_amd.sh import spherical_harmonics  # noqa: F401
 

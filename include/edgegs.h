@@ -733,6 +733,29 @@ int eg_packed_bwd_sparse(const float *means, const float *quats, const float *sc
                          float *v_means /*[nnz,3]*/, float *v_quats /*[nnz,4]*/, float *v_scales /*[nnz,3]*/,
                          eg_stream_t stream);
 
+/* ---- camera-pose gradient of the projection (gsplat's v_viewmats), csrc/viewmat_grad.hip: for every visible pair
+ * (c, n), with v_t the cotangent of its camera-space mean (the v_depths term included), vW the cotangent of
+ * W = R_c Rq diag(s) and M = Rq diag(s):  v_R[c][i][j] += v_t[i] mean[j] + sum_k vW[3i+k] M[j][k],  v_tr[c][i] += v_t[i];
+ * v_viewmats [C, 4, 4] = [[v_R | v_tr], [0 0 0 0]] is written whole (a camera that sees nothing gets sixteen zeros).  Ks
+ * gets no gradient.  Serves both layouts of the projection:
+ *   dense   splat [C, N, 8] (eg_project_fwd_cams's record: the pair is visible when its radius word is positive),
+ *           g2d [C, N, 8], v_comps [C, N], v_depths [C, N] or NULL as eg_project_bwd_cams takes them; indptr and
+ *           gaussian_ids NULL, nnz 0;
+ *   packed  splat NULL; indptr [C + 1] (the DEVICE array of eg_packed_count), nnz, gaussian_ids [nnz], g2d [nnz, 8],
+ *           v_comps [nnz], v_depths [nnz] or NULL as eg_packed_bwd takes them.
+ * scratch: scratch_blocks * C * 12 floats from the caller, scratch_blocks >= ceil(N / 256) (dense) or
+ * ceil(min(nnz, N) / 256) (packed); with zero blocks it may be NULL.  One lane per pair, one 12-float partial per
+ * workgroup, then one workgroup per camera folds the partials in a fixed order: no atomics, no host read-back, the same
+ * bits on every run.  Null pointers and sizes (N < 0, C outside 1..65535, nnz < 0 or > N * C, a scratch too small) are
+ * refused with EG_ERR_ARG before any device call. */
+int eg_project_bwd_viewmats(const float *means, const float *quats, const float *scales, const float *opacities,
+                            const float *viewmats, const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height,
+                            float eps2d, uint32_t flags, const float *splat /*[C,N,8] or NULL = packed*/,
+                            const int64_t *indptr /*[C+1], device*/, int64_t nnz, const int64_t *gaussian_ids,
+                            const float *g2d, const float *v_comps, const float *v_depths /*NULL ok*/,
+                            float *scratch /*[C,scratch_blocks,12]*/, int32_t scratch_blocks,
+                            float *v_viewmats /*[C,4,4]*/, eg_stream_t stream);
+
 /* ---- the drop-in operator's fast path in two calls (edgegaussians_amd/rasterizer.py: the reference's own call of
  * gsplat.rasterization -- one camera, colours == 1 without grad, edge_gs.py:247-279 -- and its autograd backward).
  * eg_operator_fwd: projection + exact tile binning -> per-tile sort -> the training step's wave-autonomous forward in its
