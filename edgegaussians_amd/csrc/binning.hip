@@ -361,8 +361,31 @@ constexpr int kXcdMinTiles = 512;  // XCD-aware placement on grids of 512 .. 204
 constexpr int kXcdShiftDefault = 1;  // XCD-aware record placement: tiles per block side = 2^shift
 constexpr int kFrontDefault = 4;  // class boundary of the dispatch order (slices); SegTable::slice_major carries it
 
+// SegTable::skip_empty: the background's loss term of a tile, sum_p w_p |gt_p| over its pixels -- thread t of the first four
+// waves takes pixel (t >> 4, t & 15) of the tile: four half lines per wave and array ...
+__device__ __forceinline__ float bg_loss_term(const SegTable &seg, int tile, int tid) {
+  float l = 0.f;
+  if (tid < kTilePix) {
+    const int ty_ = (int)(((float)tile + 0.5f) * seg.inv_tw), tx_ = tile - __mul24(ty_, seg.tw);
+    const int pi = ty_ * kTile + (tid >> 4), pj = tx_ * kTile + (tid & 15);
+    if (pi < seg.height && pj < seg.width) {
+      const int pp = pi * seg.width + pj;
+      l = seg.wmap[pp] * fabsf(seg.gt[pp]);  // w_p |clamp(1 - T_final) - gt_p| with T_final = 1
+    }
+  }
+  return l;
+}
+// ... and its way into the forward's 64 partial loss sums
+__device__ __forceinline__ void add_bg_loss(const SegTable &seg, int tile, int tid, float l_bg) {
+  if (tid < kTilePix) {
+    l_bg = wave_sum_dpp_f(l_bg);  // (total in lane 63)
+    if ((tid & 63) == 63 && l_bg != 0.f) unsafeAtomicAdd(&seg.loss_part[(tile * 4 + (tid >> 6)) & 63], l_bg);
+  }
+}
+
 // THREADS = number of buckets; CAP = keys per buffer (two buffers).  n_lo < n handled here.
-template <int THREADS, int CAP, bool LARGE, bool PREFIX3 = false>
+template <int THREADS, int CAP, bool LARGE, bool PREFIX3 = false, bool PAIR = false>
+// (PAIR: TWO tiles per workgroup of the small variant on the "prefix here" path, see the prologue in front of the tile loop)
 // (PREFIX3, round 6: "prefix here" on grids of 2049 .. 2560 tiles -- the reference's native 800 x 800 is 2500 -- takes a third batch
 // of cursor loads; an instantiation of its own: the branch alone cost the 1024-tile launches of configs 1 / 2 0.3-0.4 us)
 // (512-thread variant: two workgroups per CU need 4 waves per SIMD, i.e. at most 128 VGPRs; the 256-thread variant at
@@ -422,9 +445,27 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
       r_[10] = (unsigned long long)(__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 15); r_[11] = blockIdx.x; /* XCC_ID, workgroup */ \
     }                                                                            \
   } while (0)
+// (PAIR: a workgroup leaves one record per TILE, both with the workgroup's start; the second tile's phases start clean)
+#define EG_SP_NEXT()                                                             \
+  do {                                                                           \
+    if (PAIR && pass > 0) {                                                      \
+      for (int k_ = 0; k_ < 7; ++k_) prof_t[k_] = 0u;                            \
+      prof_prev = (long long)__builtin_readcyclecounter();                       \
+    }                                                                            \
+  } while (0)
+// (PAIR: the record of an empty tile -- phase 0 is the time since the workgroup's start, i.e. the round trip it shared
+// with its partner; the clock the partner's phases count from is left alone)
+#define EG_SP_EMPTY()                                                            \
+  do {                                                                           \
+    prof_t[0] = (unsigned)((long long)__builtin_readcyclecounter() - prof_prev); \
+    EG_SP_DONE(0);                                                               \
+    prof_t[0] = 0u;                                                              \
+  } while (0)
 #else
 #define EG_SP_TICK(k_) do {} while (0)
 #define EG_SP_DONE(n_) do {} while (0)
+#define EG_SP_NEXT() do {} while (0)
+#define EG_SP_EMPTY() do {} while (0)
 #endif
   // The large variant runs a small grid (<= 256 workgroups of 136 KiB LDS) over the tiles that outgrew the small one.
   // Round 4: every workgroup first FINDS them -- all its threads look at the T ranges at once and collect the oversized
@@ -462,16 +503,131 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
       n_loop = nb;
     }
   }
-  for (int it = blockIdx.x; it < n_loop; it += gridDim.x) {
+  // [5] per tile of the workgroup: the waves' partial sums of the tile prefix (finish_prefix)
+  __shared__ int s_pre[PAIR ? 10 : 5][THREADS / 64];
+  // PAIR.  One 512-thread workgroup per tile is twice what the chip holds at 1024 tiles: the launch ran in two rounds, the
+  // second one made of near-empty border tiles whose workgroups became resident only to wait 3 us for their loads behind
+  // everybody else's (profiles/r05_sort_phases_config2_final.txt).  Workgroup b owns tile A = middle-out rank b and tile
+  // B = rank T - 1 - b (with odd T the middle rank has no partner): the innermost, heaviest tiles get the outermost
+  // partners, the ones most likely to be empty.  EVERYTHING both tiles need from memory is requested here, before
+  // anything is waited for -- both cursors, the one batch of populations that serves both prefixes, every thread's first
+  // key of A and of B, the background-loss inputs of both -- and one pass over the populations forms both tiles' sums.  An
+  // empty tile then adds its loss term and is done, without a barrier; the others are sorted one after the other by the
+  // loop below, whose per-tile loads have all been made.  Across A's sort only B's first key (two VGPRs) stays live: the
+  // waves' partial sums of B wait in LDS (s_pre[5..9]) and its population is wave-uniform.
+  int tileA = 0, tileB = 0, popA = 0, popB = 0, n_pass = 0;
+  bool goA = false;
+  unsigned long long specA = ~0ull, specB = ~0ull;
+  if (PAIR) {
+    const int rA = blockIdx.x, rB = T - 1 - rA;
+    const bool hasB = rB != rA;
+    auto tile_of_rank = [&](int r) { return seg.middle_out ? ((r & 1) ? T / 2 - (r + 1) / 2 : T / 2 + r / 2) : r; };
+    tileA = tile_of_rank(rA);
+    tileB = hasB ? tile_of_rank(rB) : tileA;
+    if (tid < seg.seg_cap) {
+      specA = keys[(size_t)tileA * seg.seg_cap + tid];
+      if (hasB) specB = keys[(size_t)tileB * seg.seg_cap + tid];
+    }
+    popA = seg.cursor[tileA];
+    popB = seg.cursor[tileB];
+    const __amdgpu_buffer_rsrc_t cur_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)seg.cursor, 0, T * 4, 0x00020000);
+    constexpr int NE = kPrefixBatchTiles / THREADS;
+    static_assert(!(PAIR && PREFIX3), "pairs are launched on grids of <= 2 prefix batches (launch_tile_sort)");
+    int pv0[NE], pv1[NE];
+#pragma unroll
+    for (int j = 0; j < NE; ++j) {
+      pv0[j] = (int)__builtin_amdgcn_raw_buffer_load_b32(cur_rsrc, (tid + j * THREADS) * 4, 0, 0);
+      pv1[j] = 0;
+    }
+    if (T > kPrefixBatchTiles) {  // (uniform)
+#pragma unroll
+      for (int j = 0; j < NE; ++j)
+        pv1[j] = (int)__builtin_amdgcn_raw_buffer_load_b32(cur_rsrc, (tid + (NE + j) * THREADS) * 4, 0, 0);
+    }
+    float lA = 0.f, lB = 0.f;
+    if (seg.skip_empty) {
+      lA = bg_loss_term(seg, tileA, tid);
+      if (hasB) lB = bg_loss_term(seg, tileB, tid);
+    }
+    // (uniform) nothing to sort, no record, no table entry: as in the one-tile form below
+    const bool emptyA = seg.skip_empty && popA == 0 && tileA != T - 1;
+    const bool emptyB = hasB && seg.skip_empty && popB == 0 && tileB != T - 1;
+    goA = !emptyA;
+    const bool goB = hasB && !emptyB;
+    n_pass = (goA ? 1 : 0) + (goB ? 1 : 0);
+    if (n_pass > 0) {
+      int isA = 0, frA = 0, dpA = 0, isB = 0, frB = 0, dpB = 0, msum = 0, cmax = 0;
+      const bool any_last = tileA == T - 1 || tileB == T - 1;  // (uniform; the totals do not depend on the tile)
+      const int xA = seg.xcd_shift > 0 ? xcd_of_tile(tileA, seg.tw, seg.inv_tw, seg.xcd_shift) : 0;
+      const int xB = seg.xcd_shift > 0 ? xcd_of_tile(tileB, seg.tw, seg.inv_tw, seg.xcd_shift) : 0;
+      auto sums2 = [&](const int (&pv)[NE], int j0) {
+#pragma unroll
+        for (int j = 0; j < NE; ++j) {
+          const int tj = tid + (j0 + j) * THREADS;
+          const bool ok = tj < T, beforeA = tj < tileA, beforeB = tj < tileB;
+          const int kk = min(pv[j], seg.seg_cap), it = ok ? max(1, (kk + 127) >> 7) : 0;
+          // (the terms are those of `sums` in the one-tile form, once per tile: its XCD and its bound are its own)
+          const bool rec = !(seg.skip_empty && kk == 0 && tj != T - 1);
+          const int xj = seg.xcd_shift > 0 ? xcd_of_tile(tj, seg.tw, seg.inv_tw, seg.xcd_shift) : 0;
+          const int itf = rec ? min(it, seg.slice_major) : 0, itd = rec ? it - itf : 0;
+          const int itfA = xj == xA ? itf : 0, itfB = xj == xB ? itf : 0;
+          isA += beforeA ? it : 0;
+          frA += beforeA ? itfA : 0;
+          dpA += itfA + ((xj == xA && beforeA) ? itd : 0);
+          isB += beforeB ? it : 0;
+          frB += beforeB ? itfB : 0;
+          dpB += itfB + ((xj == xB && beforeB) ? itd : 0);
+          if (any_last) { msum += kk; cmax = max(cmax, pv[j]); }
+        }
+      };
+      sums2(pv0, 0);
+      if (T > kPrefixBatchTiles) sums2(pv1, NE);
+      // (DPP scans: the totals land in lane 63; only for the tiles that go on -- a scan costs ~240 cycles with four waves
+      // per SIMD doing the same)
+      const bool top = (tid & 63) == 63;
+      if (goA) {
+        isA = wave_scan_dpp(isA, 0, OpAdd());
+        frA = wave_scan_dpp(frA, 0, OpAdd());
+        dpA = wave_scan_dpp(dpA, 0, OpAdd());
+        if (top) { s_pre[0][tid >> 6] = isA; s_pre[1][tid >> 6] = frA; s_pre[4][tid >> 6] = dpA; }
+      }
+      if (goB) {
+        isB = wave_scan_dpp(isB, 0, OpAdd());
+        frB = wave_scan_dpp(frB, 0, OpAdd());
+        dpB = wave_scan_dpp(dpB, 0, OpAdd());
+        if (top) { s_pre[5][tid >> 6] = isB; s_pre[6][tid >> 6] = frB; s_pre[9][tid >> 6] = dpB; }
+      }
+      if (any_last) {
+        msum = wave_scan_dpp(msum, 0, OpAdd());
+        cmax = wave_scan_dpp(cmax, 0, OpMaxI());
+        const int lb = tileA == T - 1 ? 0 : 5;
+        if (top) { s_pre[lb + 2][tid >> 6] = msum; s_pre[lb + 3][tid >> 6] = cmax; }
+      }
+    }
+    if (emptyA) {
+      add_bg_loss(seg, tileA, tid, lA);
+      { const int tile = tileA; (void)tile; EG_SP_EMPTY(); }
+    }
+    if (emptyB) {
+      add_bg_loss(seg, tileB, tid, lB);
+      { const int tile = tileB; (void)tile; EG_SP_EMPTY(); }
+    }
+  }
+  for (int it = blockIdx.x, pass = 0; PAIR ? pass < n_pass : it < n_loop; it += gridDim.x, ++pass) {
+  const bool useB = PAIR && (pass > 0 || !goA);  // (uniform) which of the workgroup's two tiles this pass sorts
   const int wg = by_list ? s_big_sorted[it] : it;
   // Workgroup -> tile, MIDDLE OUT over the row-major tile index (the small variant: one tile per workgroup, dispatched in
   // index order, two or three rounds of them): the tiles of the image's middle rows -- where a centred object puts its
   // thousands of keys -- start in the first round and the near-empty border tiles make up the last one, instead of the
   // image's lower half with its share of heavy tiles.  Any assignment is correct.
-  const int tile = (!LARGE && seg.middle_out) ? ((wg & 1) ? T / 2 - (wg + 1) / 2 : T / 2 + wg / 2) : wg;
-  __syncthreads();
+  const int tile = PAIR ? (useB ? tileB : tileA)
+                        : (!LARGE && seg.middle_out) ? ((wg & 1) ? T / 2 - (wg + 1) / 2 : T / 2 + wg / 2) : wg;
+  // (PAIR: the barrier separates the two tiles' uses of LDS -- kout, hist, cursor, wave_tmp, wave_tmp2; s_pre is written
+  // once, in the prologue, and each tile reads its own half behind its first barrier.  The first pass needs none.)
+  if (!PAIR || pass > 0) __syncthreads();
+  EG_SP_NEXT();
   long long start, end;
-  __shared__ int s_pre[5][THREADS / 64];
+  const int pb = (PAIR && useB) ? 5 : 0;  // this tile's rows of s_pre
   bool prefix_pending = false;  // (uniform) the tile prefix still has to be finished: see SegTable::total
   int pop_here = 0;
   // after a barrier: every thread sums the waves' partials; thread 0 writes the tile's table entries (and the
@@ -481,7 +637,7 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
     if (tid >= 64) return;  // (the first wave writes the tables and the records: a tile has a few dozen items at most)
     int isum = 0, k0 = 0, l0k1 = 0;
 #pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) { isum += s_pre[0][w]; k0 += s_pre[1][w]; l0k1 += s_pre[4][w]; }
+    for (int w = 0; w < THREADS / 64; ++w) { isum += s_pre[pb + 0][w]; k0 += s_pre[pb + 1][w]; l0k1 += s_pre[pb + 4][w]; }
     // of the tiles of THIS tile's XCD (all tiles without the XCD-aware placement): k0 = front-class items in front of this
     // tile; l0k1 = front-class items in all + deep-class items in front of this tile.  (Two full ints: round 5 packed them
     // into 16-bit halves of one, and a list of >= 32768 items turned `l0k1` negative -- a negative dispatch index still
@@ -512,7 +668,7 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
       if (tile == T - 1) {  // (the last tile's workgroup has summed the view's totals as well)
         int msum = 0, cmax = 0;
 #pragma unroll
-        for (int w = 0; w < THREADS / 64; ++w) { msum += s_pre[2][w]; cmax = max(cmax, s_pre[3][w]); }
+        for (int w = 0; w < THREADS / 64; ++w) { msum += s_pre[pb + 2][w]; cmax = max(cmax, s_pre[pb + 3][w]); }
         const int itot = isum + max(1, (kept_ + 127) >> 7);  // (the tiles in front + this one: all of them)
         seg.total[0] = msum;
         if (cmax > seg.seg_cap || itot > seg.max_items) seg.total[1] = 1;  // sticky: only the host clears it
@@ -526,11 +682,17 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
   // the population is known (one round trip to memory instead of two: most tiles hold fewer keys than the workgroup
   // has threads); a slot beyond the population holds a stale key of an earlier step and is dropped below
   unsigned long long spec0 = ~0ull;
-  if (!LARGE && seg.cursor && tid < seg.seg_cap) spec0 = keys[(size_t)tile * seg.seg_cap + tid];
+  if (PAIR) spec0 = useB ? specB : specA;  // (requested in the prologue)
+  else if (!LARGE && seg.cursor && tid < seg.seg_cap) spec0 = keys[(size_t)tile * seg.seg_cap + tid];
   if (seg.cursor) {
     if (!LARGE) {
       int kept, first, items;
-      if (seg.total) {
+      if (PAIR) {  // (the prologue has loaded the population and left the waves' partial sums in s_pre)
+        pop_here = useB ? popB : popA;
+        kept = min(pop_here, seg.seg_cap);
+        prefix_pending = true;
+        first = items = 0;
+      } else if (seg.total) {
         // The populations of the tiles before this one are REQUESTED by all threads before anything is waited for
         // (they travel with the tile's own cursor and first keys); per-wave partial sums go to LDS and the prefix
         // is finished right after the FIRST barrier the sort takes anyway (finish_prefix below): no barrier of its own
@@ -556,26 +718,12 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
         // 256-thread variant, whose workgroups all start together, asks once it knows: requested by every tile's
         // workgroup the term cost that launch 0.6 us at config 1, profiles/r05_skip_empty_ab.txt)
         constexpr bool kBgEarly = THREADS >= 512;
-        auto bg_term = [&]() -> float {
-          float l = 0.f;
-          if (tid < kTilePix) {
-            const int ty_ = (int)(((float)tile + 0.5f) * seg.inv_tw), tx_ = tile - __mul24(ty_, seg.tw);
-            const int pi = ty_ * kTile + (tid >> 4), pj = tx_ * kTile + (tid & 15);
-            if (pi < seg.height && pj < seg.width) {
-              const int pp = pi * seg.width + pj;
-              l = seg.wmap[pp] * fabsf(seg.gt[pp]);  // w_p |clamp(1 - T_final) - gt_p| with T_final = 1
-            }
-          }
-          return l;
-        };
+        auto bg_term = [&]() -> float { return bg_loss_term(seg, tile, tid); };
         float l_bg = 0.f;
         if (kBgEarly && seg.skip_empty) l_bg = bg_term();
         if (seg.skip_empty && pop_here == 0 && tile != T - 1) {  // (uniform) nothing to sort, no record, no table entry
           if (!kBgEarly) l_bg = bg_term();
-          if (tid < kTilePix) {
-            l_bg = wave_sum_dpp_f(l_bg);  // (total in lane 63)
-            if ((tid & 63) == 63 && l_bg != 0.f) unsafeAtomicAdd(&seg.loss_part[(tile * 4 + (tid >> 6)) & 63], l_bg);
-          }
+          add_bg_loss(seg, tile, tid, l_bg);
           EG_SP_TICK(0); EG_SP_DONE(0);
           continue;
         }
@@ -895,6 +1043,13 @@ extern "C" int eg_tile_emit(const float *means2d, const int32_t *radii, const fl
 
 static bool g_sort_attr_set = false;
 
+// 1 when the training step's tile sort (one view, segmented layout, n_tiles <= kPrefixHereMaxTiles) gives every workgroup
+// TWO tiles for this grid and population hint (launch_tile_sort), else 0
+extern "C" int eg_sort_two_tiles_per_workgroup(int32_t n_tiles, int32_t max_tile_hint) {
+  constexpr int kResident = 512;  // 512-thread workgroups the chip holds: two per CU (<= 128 VGPRs), 256 CUs
+  return (max_tile_hint > 1536 && n_tiles > kResident && n_tiles <= 2 * kPrefixBatchTiles) ? 1 : 0;
+}
+
 #ifdef EG_SORT_PROF
 static unsigned long long *g_sort_prof = nullptr;
 static int g_sort_prof_tiles = 0;
@@ -931,15 +1086,27 @@ static int launch_tile_sort(uint64_t *keys, const int32_t *offsets, int32_t T, i
   // LDS that would all find nothing to do: ~3 us) is skipped and the small variant owns EVERY tile -- a
   // tile that outgrew the hint is then still sorted correctly, by the slower paths of the small variant.
   const bool small_only = max_tile_hint > 0 && (int64_t)max_tile_hint * 5 / 4 <= kSmall;
-  // workgroups of the small variant: one per tile (two tiles per workgroup measured 7.7 -> 10.1 us at config 1, 11.8 -> 12.4
-  // at config 2, profiles/r06_misc_ab.txt: the second tile's round trip to memory starts after the first tile's sort)
-#define EG_SORT_SMALL(TH_, P3_)                                                                                          \
-  tile_sort_kernel<TH_, kSmall, false, P3_><<<dim3(T, C), TH_, kSmall * 8 + 2 * TH_ * 4 * kSortBM, as_stream(stream)>>>( \
+  // workgroups of the small variant: one per tile -- except where sort_two_tiles_per_workgroup says so: the 512-thread
+  // variant on the "prefix here" path, one view, 513 .. 2048 tiles.  Two 512-thread workgroups fit a CU, 512 the chip: above
+  // that the launch ran in rounds, the last one made of near-empty border tiles.  There a workgroup takes TWO tiles,
+  // middle-out rank b and rank T - 1 - b, and asks for both tiles' data in one round trip to memory (tile_sort_kernel,
+  // PAIR).  Config 2 (1024 tiles), parent and paired legs alternating on one chip: 11.35 / 11.19 -> 10.15 / 10.15 us,
+  // step 77.8 / 78.5 -> 76.5 / 76.5 us (profiles/sort_pairs_ab.txt); 95 VGPRs, no scratch.  (A grid-stride loop over two tiles, whose second tile's round trip
+  // starts after the first tile's sort, had measured 7.7 -> 10.1 us at config 1 and 11.8 -> 12.4 at config 2,
+  // profiles/r06_misc_ab.txt.)  Everything else keeps one tile per workgroup: grids of <= 512 tiles and the 256-thread
+  // variant at 1024 (all workgroups resident: pairing would only serialise two tiles); grids of 2049 .. 2560 tiles (three
+  // prefix batches: pairs not measured there); batched launches (C > 1: not measured in pairs); and the grids above
+  // kPrefixHereMaxTiles, whose workgroups read their prefix instead of forming it.
+  const bool pair = seg.total != nullptr && C == 1 && eg_sort_two_tiles_per_workgroup(T, max_tile_hint) != 0;
+#define EG_SORT_SMALL(TH_, P3_, PR_)                                                                                     \
+  tile_sort_kernel<TH_, kSmall, false, P3_, PR_><<<dim3(PR_ ? (T + 1) / 2 : T, C), TH_, kSmall * 8 + 2 * TH_ * 4 * kSortBM, \
+                                                   as_stream(stream)>>>(                                                 \
       (unsigned long long *)keys, offsets, T, (long long)capacity, small_only ? 0x7fffffff : kSmall, flatten_ids,            \
       (long long *)isect_ids, seg, bt)
   const bool prefix3 = seg.total != nullptr && T > 2 * kPrefixBatchTiles;
-  if (wide) { if (prefix3) EG_SORT_SMALL(512, true); else EG_SORT_SMALL(512, false); }
-  else      { if (prefix3) EG_SORT_SMALL(256, true); else EG_SORT_SMALL(256, false); }
+  if (pair)      { EG_SORT_SMALL(512, false, true); }
+  else if (wide) { if (prefix3) EG_SORT_SMALL(512, true, false); else EG_SORT_SMALL(512, false, false); }
+  else           { if (prefix3) EG_SORT_SMALL(256, true, false); else EG_SORT_SMALL(256, false, false); }
 #undef EG_SORT_SMALL
   if (!small_only)
     tile_sort_kernel<1024, kLarge, true><<<dim3(min(T, 256), C), 1024, kLargeLds, as_stream(stream)>>>(

@@ -552,6 +552,11 @@ int eg_train_step(const eg_step_args *args_host, eg_stream_t stream);
  * what a caller labels its measurements with (bench.py). */
 int eg_backward_is_fused(int32_t n_gaussians, int32_t n_tiles);
 
+/* 1 when the tile sort of a step (one view, segmented layout, "prefix here" grid) on a grid of n_tiles tiles with the
+ * population hint max_tile_hint runs its 512-thread variant with TWO tiles per workgroup (grids of 513 .. 2048 tiles, hint
+ * above 1536), else 0: a launch shape, never a result. */
+int eg_sort_two_tiles_per_workgroup(int32_t n_tiles, int32_t max_tile_hint);
+
 /* The XCD-aware placement of the item records (eg_step_args::item_rec) on a grid of n_tiles tiles with one view per launch:
  * tiles per block side = 2^result, 0 = dense records.  A caller sizes max_items for 8 x the longest of the eight lists. */
 int eg_record_xcd_shift(int32_t n_tiles);

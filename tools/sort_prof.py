@@ -64,3 +64,20 @@ for lo, hi in ((0, 0), (1, 64), (65, 512), (513, 1536), (1537, 4096)):
 xcc, wg = rec[:, 10].astype(int), rec[:, 11].astype(int)
 print(f"  XCC_ID of workgroup b: == b % 8 for {int((xcc == wg % 8).sum())} of {len(wg)} workgroups; per-XCC counts {np.bincount(xcc, minlength=8).tolist()}")
 
+# two tiles per workgroup (the 512-thread variant on the "prefix here" path: both records carry the workgroup's start)
+n_wg = len(np.unique(wg))
+if n_wg < len(wg):
+    print(f"  {len(wg)} tile records of {n_wg} workgroups: workgroup wall time (start -> its last tile's end) by what the pair holds")
+    by = {}
+    for i, b in enumerate(wg):
+        by.setdefault(b, []).append(i)
+    kinds = {"single tile": [], "both empty": [], "one empty": [], "both populated": []}
+    for b, ii in by.items():
+        life_us = max(en[i] for i in ii) - min(st[i] for i in ii)
+        pops = [pop[i] for i in ii]
+        k = "single tile" if len(ii) == 1 else "both empty" if max(pops) <= 0 else "one empty" if min(pops) <= 0 else "both populated"
+        kinds[k].append((life_us, sum(pops)))
+    for k, v in kinds.items():
+        if v:
+            a = np.array(v)
+            print(f"    {k:15s} {len(v):5d} workgroups, wall mean {a[:, 0].mean():.2f} us p95 {np.percentile(a[:, 0], 95):.2f} max {a[:, 0].max():.2f}; keys mean {a[:, 1].mean():.0f}")
