@@ -30,6 +30,7 @@ FLAG_FRONT_PREFIX = 32   # EG_FLAG_FRONT_PREFIX (tile grids above PREFIX_HERE_MA
 PREFIX_HERE_MAX_TILES = 2560  # kPrefixHereMaxTiles (csrc/common.h)
 REWALK_SPECULATE = -2  # EG_REWALK_SPECULATE
 MAX_WS_TAG = 0xfffe      # EG_MAX_WS_TAG
+TS_STAGE_BATCH = {8: 128, 32: 256}  # kStage8 / kStage32 (csrc/tiles.hip): Gaussians per staging batch of the 8- / 32-pixel compositing
 PACKED_STRIDE = 0        # EG_PACKED_STRIDE: the record stride N of the mode / wide compositing entries on packed records
 
 
@@ -145,6 +146,13 @@ _SIGS = {
     "eg_packed_write": [_vp] * 6 + [_i32, _i32, _i32, _i32, _f, _f, _f, _f, _u32, _vp, _i64] + [_vp] * 10 + [_vp],
     "eg_packed_bin": [_vp, _vp, _vp, C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, C.POINTER(_i64), _vp, _vp, _vp,
                       C.POINTER(_i32), _vp],
+    "eg_tile_count_ts": [_vp, _vp, C.POINTER(_i64), _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "eg_tile_emit_sort_ts": [_vp, _vp, _vp, C.POINTER(_i64), _i32, _i32, _i32, _i32, _vp, _vp, C.POINTER(_i64), _vp, _vp, _vp,
+                             C.POINTER(_i32), _i32, _vp],
+    "eg_composite_fwd_ts_cams": [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32,
+                                 _i32, _i32, _vp],
+    "eg_composite_bwd_ts_cams": [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _i32, _i32, _i32, _vp],
     "eg_packed_bwd": [_vp] * 6 + [_i32, _i32, _i32, _i32, _f, _u32, _vp, _i64] + [_vp] * 7 + [_vp],
     "eg_packed_bwd_sparse": [_vp] * 6 + [_i32, _i32, _i32, _i32, _f, _u32, _i64] + [_vp] * 8 + [_vp],
     "eg_project_bwd_viewmats": [_vp] * 6 + [_i32, _i32, _i32, _i32, _f, _u32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32,

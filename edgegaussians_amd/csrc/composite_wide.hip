@@ -16,55 +16,15 @@
 // Backward: the walk of composite_bwd_colors_kernel.  Its reduction -- one six-step butterfly per partial, then lane 0
 // issuing every atomic -- costs 6 (8 + CH + 1) cross-lane operations and 8 + CH + 1 serial atomics per (wave,
 // Gaussian).  Here the CH colour partials and the 8 splat-side partials are reduced by a HALVING EXCHANGE
-// (lane_transpose_sum below): in a step over lane bit b a lane keeps one half of its values, hands the other half to
+// (lane_transpose_sum, wide_dev.h): in a step over lane bit b a lane keeps one half of its values, hands the other half to
 // lane ^ (1 << b) and adds what it receives, so n values cost n/2 + n/4 + ... + 1 = n - 1 exchanges and finish with
 // component k in lane k.  Lanes 0 .. CH-1 then hold the colour sums, lanes 32 .. 39 the splat-side sums and lane 63
 // the depth sum, and ONE atomic instruction adds them all: consecutive lanes to consecutive addresses.  Measured
 // against the plain scheme instantiated at the same widths (profiles/channels_bwd_reduction_ab.jsonl).
 #include "common.h"
+#include "wide_dev.h"
 
 namespace eg {
-
-struct WideArgs {
-  const float *bg;    // backgrounds of the chunk: camera c's row at bg + c * cs (BG)
-  float *v_depths;    // [C, N] (backward, DEPTH), accumulated
-  int N;              // record stride between the cameras' blocks; EG_PACKED_STRIDE (0) = packed records (see ModeArgs)
-  int colors_per_camera;
-  int n_real;         // real channels of the chunk, 1 .. CH
-  int cs;             // row stride (floats) of colors, v_colors and backgrounds
-  int ps;             // row stride (floats) of render and v_render
-  int vec;            // every colour row of the chunk starts on a 16-byte (CH = 2: 8-byte) boundary
-};
-
-// flatten_ids: the C cameras' lists one after the other, offsets [C, T+1] local to each list
-__device__ __forceinline__ int wide_list_base(const int *__restrict__ offsets, int T, int c) {
-  int base = 0;
-  for (int k = 0; k < c; ++k) base += offsets[(size_t)k * (T + 1) + T];
-  return base;
-}
-
-// Colour rows of the n Gaussians flat[first + step * r], r = 0 .. n-1, into sC[r * CH ..]: unit e = (row, 4 channels)
-// is fetched by thread e % 256 with one 16-byte load where the rows are aligned and the unit holds real channels only.
-template <int CH>
-__device__ __forceinline__ void stage_colors(float *__restrict__ sC, const float *__restrict__ colors,
-                                             const int *__restrict__ flat, int first, int step, int n,
-                                             const WideArgs &wa) {
-  constexpr int VW = CH < 4 ? CH : 4;  // floats per unit
-  constexpr int UPR = CH / VW;         // units per row
-  typedef float vecw __attribute__((ext_vector_type(VW)));
-  for (int e = threadIdx.x; e < n * UPR; e += kTilePix) {
-    const int r = e / UPR, c0 = (e % UPR) * VW;
-    const float *row = colors + (size_t)flat[first + step * r] * wa.cs + c0;
-    vecw v;
-    if (wa.vec && c0 + VW <= wa.n_real) {
-      v = *(const vecw *)row;
-    } else {
-#pragma unroll
-      for (int k = 0; k < VW; ++k) v[k] = (c0 + k < wa.n_real) ? row[k] : 0.f;
-    }
-    *(vecw *)(sC + (size_t)e * VW) = v;
-  }
-}
 
 template <int CH, bool DEPTH, bool BG>
 __global__ void __launch_bounds__(256)
@@ -148,36 +108,6 @@ composite_fwd_wide_kernel(const float4 *__restrict__ splat, const float *__restr
     }
     if constexpr (DEPTH) out[wa.n_real] = pix_d;  // (the depth channel's background is 0)
   }
-}
-
-// One step of the halving exchange over lane bit H, and the steps below it.
-// (the step width H is a template argument: with a run-time H the indices v[k + H] are dynamic and the array leaves
-// the registers)
-template <int H, int K>
-__device__ __forceinline__ void halving_step(float (&v)[K], int lane) {
-  if constexpr (H >= 1) {
-    const bool upper = (lane & H) != 0;  // this lane keeps the components whose bit H is set
-#pragma unroll
-    for (int k = 0; k < H; ++k) {
-      const float send = upper ? v[k] : v[k + H];
-      const float keep = upper ? v[k + H] : v[k];
-      v[k] = keep + __shfl_xor(send, H, 64);
-    }
-    halving_step<H / 2, K>(v, lane);
-  }
-}
-
-// Sum over the wave of each of the K values of every lane (K a power of two, 2 .. 32); returns, in every lane, the sum
-// of component lane & (K - 1).  Halving exchange over the lane bits K/2, ..., 1 (K - 1 exchanges), then plain
-// butterflies over the lane bits K, ..., 32.  v is clobbered.
-template <int K>
-__device__ __forceinline__ float lane_transpose_sum(float (&v)[K], int lane) {
-  static_assert(K >= 2 && K <= 32 && (K & (K - 1)) == 0, "power of two");
-  halving_step<K / 2, K>(v, lane);
-  float s = v[0];
-#pragma unroll
-  for (int d = K; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
-  return s;
 }
 
 template <int CH, bool DEPTH, bool BG>

@@ -1,0 +1,582 @@
+// Tile sizes 8 and 32 (rasterization(tile_size=8 | 32)): binning with a run-time tile size and the compositing kernels
+// templated on it.  tile_size = 16 never comes here: it keeps binning.hip, composite.hip and composite_wide.hip.
+//
+// Binning.  tile_count_kernel / tile_emit_kernel of binning.hip with the tile size as an argument: the same tile box
+// ((x / ts) -+ (r / ts) in fp32, floor / ceil, clamp), the same LDS-privatised histogram (grids of up to 16 384 tiles for
+// the counting, 8 192 for the emission, which keeps two words per tile) and the same direct-atomic fallback beyond -- at
+// ts = 8 a 1024 x 1032 image has 16 512 tiles.  The scan (eg_tile_offsets_cams) and the per-tile sort (eg_sort_pairs)
+// know the tile size only through T and are used as they are.  The cameras' Gaussians are addressed through a host
+// array of C + 1 range bounds, which serves both layouts of the projection: [c N, (c + 1) N) for the dense [C, N, ...]
+// arrays, indptr for the packed lists.
+//
+// Compositing: one kernel family <TS, CH, DEPTH, BG> for chunks of CH = 2 .. 32 channels (n_real of them real) and the
+// depth-only form CH = 0, which stages no colours; the walk, its source expressions, the staging through LDS, the halving
+// exchange and the single-atomic write-out are those of composite_wide.hip.
+//   ts = 8   a tile is 64 pixels = one wave: ONE 64-LANE WORKGROUP PER TILE.  The wave stages kStage8 = 128 Gaussians per
+//            batch (two per lane) and walks them; a barrier of a one-wave workgroup costs nothing, and no wave ever waits
+//            for the list of another tile (four tiles per 256-thread workgroup would hold the three short lists' waves --
+//            and their LDS -- until the longest is done, or need wave-private staging without workgroup barriers).
+//   ts = 32  a tile is 1024 pixels: ONE 256-THREAD WORKGROUP PER 16 x 16 QUADRANT, four workgroups walking the parent
+//            tile's list (kStage32 = 256 per batch).  A 1024-thread workgroup would run 4 waves per SIMD and cap the
+//            kernel at 128 VGPRs, below what the backward needs at CH = 32 (three 32-float arrays per lane); the
+//            quadrant form keeps the register budget and the code shape of the 16-pixel kernels, its quadrants leave
+//            independently (a quadrant whose pixels all stopped does not wait for the other three), and a quadrant that
+//            lies outside the image leaves at once.  The price: the list is staged four times (the four workgroups
+//            of a tile are neighbours in the XCD remap, so the repeats can come from one L2).
+#include "common.h"
+#include "wide_dev.h"
+
+namespace eg {
+
+constexpr int kTsBinThreads = 512;
+constexpr int kTsMaxLdsWords = 16384;  // 64 KiB of LDS counters; larger grids use the direct-atomic path
+
+inline bool tile_size_ok(int ts) { return ts == 8 || ts == 32; }  // (16: binning.hip, composite*.hip)
+
+// common.h tile_box with `ts` in place of 16
+__device__ __forceinline__ void tile_box_ts(float x, float y, int radius, float ts, int tw, int th, int &x0, int &y0,
+                                            int &x1, int &y1) {
+  const float tr = (float)radius / ts;
+  const float tx = x / ts, ty = y / ts;
+  x0 = min(max((int)floorf(tx - tr), 0), tw);
+  y0 = min(max((int)floorf(ty - tr), 0), th);
+  x1 = min(max((int)ceilf(tx + tr), 0), tw);
+  y1 = min(max((int)ceilf(ty + tr), 0), th);
+}
+
+// one camera's n Gaussians: tiles_per_gauss [n] (NULL ok), tile_counts [T] accumulated
+template <bool LDS>
+__global__ void __launch_bounds__(kTsBinThreads)
+ts_count_kernel(const float2 *__restrict__ means2d, const int *__restrict__ radii, int n, float ts, int tw, int th,
+                int *__restrict__ tiles_per_gauss, int *__restrict__ tile_counts) {
+  extern __shared__ __attribute__((aligned(16))) int s_hist[];
+  const int T = tw * th;
+  if (LDS) {
+    for (int t = threadIdx.x; t < T; t += kTsBinThreads) s_hist[t] = 0;
+    __syncthreads();
+  }
+  const int g = blockIdx.x * kTsBinThreads + threadIdx.x;
+  if (g < n) {
+    const int radius = radii[g];
+    int cnt = 0;
+    if (radius > 0) {
+      const float2 m = means2d[g];
+      int x0, y0, x1, y1;
+      tile_box_ts(m.x, m.y, radius, ts, tw, th, x0, y0, x1, y1);
+      cnt = (y1 - y0) * (x1 - x0);
+      for (int ty = y0; ty < y1; ++ty)
+        for (int tx = x0; tx < x1; ++tx) atomicAdd(LDS ? &s_hist[ty * tw + tx] : &tile_counts[ty * tw + tx], 1);
+    }
+    if (tiles_per_gauss) tiles_per_gauss[g] = cnt;
+  }
+  if (LDS) {
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += kTsBinThreads) {
+      const int c = s_hist[t];
+      if (c) atomicAdd(&tile_counts[t], c);
+    }
+  }
+}
+
+// one camera's n Gaussians: key = depth bits << 32 | index inside the camera's range; the slots are claimed as in
+// tile_emit_kernel (the cursors -- the tile counts -- are counted back down to zero)
+template <bool LDS>
+__global__ void __launch_bounds__(kTsBinThreads)
+ts_emit_kernel(const float2 *__restrict__ means2d, const int *__restrict__ radii, const float *__restrict__ depths,
+               int n, float ts, int tw, int th, const int *__restrict__ offsets, int *__restrict__ cursor,
+               long long capacity, unsigned long long *__restrict__ keys) {
+  extern __shared__ __attribute__((aligned(16))) int s_mem[];
+  const int T = tw * th;
+  int *s_hist = s_mem, *s_base = s_mem + T;
+  if (LDS) {
+    for (int t = threadIdx.x; t < T; t += kTsBinThreads) s_hist[t] = 0;
+    __syncthreads();
+  }
+  const int g = blockIdx.x * kTsBinThreads + threadIdx.x;
+  int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+  float depth = 0.f;
+  if (g < n) {
+    const int radius = radii[g];
+    if (radius > 0) {
+      const float2 m = means2d[g];
+      depth = depths[g];
+      tile_box_ts(m.x, m.y, radius, ts, tw, th, x0, y0, x1, y1);
+    }
+  }
+  const unsigned long long key = ((unsigned long long)(unsigned)__float_as_int(depth) << 32) | (unsigned)g;
+  if (!LDS) {
+    for (int ty = y0; ty < y1; ++ty)
+      for (int tx = x0; tx < x1; ++tx) {
+        const int t = ty * tw + tx;
+        const long long idx = (long long)offsets[t] + (atomicSub(&cursor[t], 1) - 1);
+        if (idx >= 0 && idx < capacity) keys[idx] = key;
+      }
+    return;
+  }
+  for (int ty = y0; ty < y1; ++ty)
+    for (int tx = x0; tx < x1; ++tx) atomicAdd(&s_hist[ty * tw + tx], 1);
+  __syncthreads();
+  for (int t = threadIdx.x; t < T; t += kTsBinThreads) {
+    const int c = s_hist[t];
+    if (c) {
+      s_base[t] = offsets[t] + (atomicSub(&cursor[t], c) - c);  // slots [base, base + c)
+      s_hist[t] = 0;
+    }
+  }
+  __syncthreads();
+  for (int ty = y0; ty < y1; ++ty)
+    for (int tx = x0; tx < x1; ++tx) {
+      const int t = ty * tw + tx;
+      const long long idx = (long long)s_base[t] + atomicAdd(&s_hist[t], 1);
+      if (idx >= 0 && idx < capacity) keys[idx] = key;
+    }
+}
+
+// sorted ids of one camera's range -> indices into the whole list (id_base != 0); the camera into the isect ids
+__global__ void __launch_bounds__(256)
+ts_rebase_kernel(int *__restrict__ flatten_ids, long long *__restrict__ isect_ids, long long M, int id_base,
+                 long long camera_bits) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= M) return;
+  if (id_base) flatten_ids[i] += id_base;
+  if (isect_ids) isect_ids[i] |= camera_bits;
+}
+
+// ---------------------------------------------------------------------------------------------
+// compositing
+constexpr int kStage8 = 128;   // Gaussians per staging batch, ts = 8 (64 lanes: two per lane)
+constexpr int kStage32 = 256;  // ... ts = 32 (256 threads: one per thread)
+constexpr int ts_threads(int ts) { return ts == 8 ? 64 : 256; }
+constexpr int ts_stage(int ts) { return ts == 8 ? kStage8 : kStage32; }
+constexpr int ts_sub(int ts) { return ts == 32 ? 4 : 1; }  // workgroups per tile
+
+// workgroup -> (tile, pixel of this thread); false: the workgroup's pixels all lie outside the image (uniform)
+template <int TS>
+__device__ __forceinline__ bool ts_pixel(int tw, int th, int width, int height, int &tile, int &i, int &j) {
+  constexpr int SUB = ts_sub(TS);
+  const int unit = xcd_tile(blockIdx.x, tw * th * SUB);  // (the quadrants of a tile are neighbours: one XCD, mostly)
+  tile = unit / SUB;
+  const int q = unit % SUB, tid = threadIdx.x;
+  const int ty = tile / tw, tx = tile - ty * tw;
+  int i0, j0;
+  if constexpr (TS == 8) {
+    i0 = ty * 8; j0 = tx * 8;
+    i = i0 + (tid >> 3); j = j0 + (tid & 7);
+  } else {
+    i0 = ty * 32 + (q >> 1) * 16; j0 = tx * 32 + (q & 1) * 16;
+    i = i0 + (tid >> 4); j = j0 + (tid & 15);
+  }
+  return i0 < height && j0 < width;
+}
+
+template <int TS, int CH, bool DEPTH, bool BG>
+__global__ void __launch_bounds__(ts_threads(TS))
+ts_composite_fwd_kernel(const float4 *__restrict__ splat, const float *__restrict__ colors,
+                        const int *__restrict__ offsets, const int *__restrict__ flat, int width, int height, int tw,
+                        int th, float *__restrict__ render, float *__restrict__ alphas, int *__restrict__ last_ids,
+                        const WideArgs wa) {
+  static_assert(CH > 0 || (DEPTH && !BG), "the depth-only form has a depth channel and no background");
+  constexpr int THREADS = ts_threads(TS), STAGE = ts_stage(TS), CHA = CH > 0 ? CH : 1;
+  __shared__ float4 sA[STAGE];  // x, y, a, b
+  __shared__ float4 sB[STAGE];  // c, o, sigma threshold, depth (DEPTH)
+  __shared__ __attribute__((aligned(16))) float sC[CH > 0 ? STAGE * CH : 4];
+
+  {
+    const int c = blockIdx.y, T = tw * th;
+    const size_t hw = (size_t)width * height;
+    flat += wide_list_base(offsets, T, c);
+    offsets += (size_t)c * (T + 1);
+    splat += 2 * (size_t)wa.N * c;
+    if (CH > 0 && wa.colors_per_camera) colors += (size_t)wa.N * wa.cs * c;
+    render += hw * wa.ps * c;
+    if (alphas) alphas += hw * c;
+    if (last_ids) last_ids += hw * c;
+  }
+  int tile, i, j;
+  if (!ts_pixel<TS>(tw, th, width, height, tile, i, j)) return;
+  const int tid = threadIdx.x;
+  const bool inside = (i < height) && (j < width);
+  const float px = (float)j + 0.5f, py = (float)i + 0.5f;
+  const int start = offsets[tile], end = offsets[tile + 1];
+
+  float T = 1.f;
+  float pix[CHA];
+#pragma unroll
+  for (int k = 0; k < CHA; ++k) pix[k] = 0.f;
+  float pix_d = 0.f;
+  int last = 0;
+  bool done = !inside;
+
+  for (int base = start; base < end; base += STAGE) {
+    if (__syncthreads_and(done)) break;
+    const int n = min(STAGE, end - base);
+    for (int e = tid; e < n; e += THREADS) {
+      const int g = flat[base + e];
+      const float4 s0 = splat[2 * g], s1 = splat[2 * g + 1];
+      sA[e] = s0;
+      sB[e] = make_float4(s1.x, s1.y, __logf(255.f * s1.y) + kThrMargin, DEPTH ? s1.z : 0.f);
+    }
+    if constexpr (CH > 0) stage_colors<CH, THREADS>(sC, colors, flat, base, 1, n, wa);
+    __syncthreads();
+    for (int t = 0; t < n && !done; ++t) {
+      const float4 A = sA[t], B = sB[t];
+      const float dx = A.x - px, dy = A.y - py;
+      const float sigma = 0.5f * (A.z * dx * dx + B.x * dy * dy) + A.w * dx * dy;
+      if (sigma < 0.f || sigma > B.z) continue;
+      const float alpha = fminf(kAlphaMax, B.y * __expf(-sigma));
+      if (alpha < kAlphaMin) continue;
+      const float next_T = T * (1.f - alpha);
+      if (next_T <= kTStop) { done = true; break; }
+      const float w = alpha * T;
+      if constexpr (CH > 0) {
+#pragma unroll
+        for (int k = 0; k < CH; ++k) pix[k] += sC[t * CH + k] * w;
+      }
+      if constexpr (DEPTH) pix_d += B.w * w;
+      last = base + t;
+      T = next_T;
+    }
+  }
+
+  if (inside) {
+    const int p = i * width + j;
+    if (alphas) alphas[p] = 1.f - T;
+    if (last_ids) last_ids[p] = last;
+    float *out = render + (size_t)p * wa.ps;
+    if constexpr (CH > 0) {
+#pragma unroll
+      for (int k = 0; k < CH; ++k) {
+        if (k < wa.n_real) {
+          float v = pix[k];
+          if constexpr (BG) v += T * wa.bg[(size_t)blockIdx.y * wa.cs + k];
+          out[k] = v;
+        }
+      }
+    }
+    if constexpr (DEPTH) out[wa.n_real] = pix_d;  // (the depth channel's background is 0)
+  }
+}
+
+template <int TS, int CH, bool DEPTH, bool BG>
+__global__ void __launch_bounds__(ts_threads(TS))
+ts_composite_bwd_kernel(const float4 *__restrict__ splat, const float *__restrict__ colors,
+                        const int *__restrict__ offsets, const int *__restrict__ flat, int width, int height, int tw,
+                        int th, const float *__restrict__ alphas, const int *__restrict__ last_ids,
+                        const float *__restrict__ v_render, const float *__restrict__ v_alphas,
+                        float *__restrict__ g2d, float *__restrict__ v_colors, const WideArgs wa) {
+  static_assert(CH > 0 || (DEPTH && !BG), "the depth-only form has a depth channel and no background");
+  constexpr int THREADS = ts_threads(TS), STAGE = ts_stage(TS), CHA = CH > 0 ? CH : 1;
+  __shared__ float4 sA[STAGE];
+  __shared__ float4 sB[STAGE];  // c, o, depth (DEPTH), Gaussian id (int bits)
+  __shared__ __attribute__((aligned(16))) float sC[CH > 0 ? STAGE * CH : 4];
+
+  {
+    const int c = blockIdx.y, T = tw * th;
+    const size_t hw = (size_t)width * height, n = (size_t)wa.N;
+    flat += wide_list_base(offsets, T, c);
+    offsets += (size_t)c * (T + 1);
+    splat += 2 * n * c;
+    if (CH > 0 && wa.colors_per_camera) colors += n * wa.cs * c;
+    alphas += hw * c;
+    last_ids += hw * c;
+    v_render += hw * wa.ps * c;
+    if (v_alphas) v_alphas += hw * c;
+    g2d += 8 * n * c;
+    if (v_colors) v_colors += n * wa.cs * c;
+  }
+  int tile, i, j;
+  if (!ts_pixel<TS>(tw, th, width, height, tile, i, j)) return;
+  const int start = offsets[tile], end = offsets[tile + 1];
+  if (end <= start) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const bool inside = (i < height) && (j < width);
+  const float px = (float)j + 0.5f, py = (float)i + 0.5f;
+  const int p = inside ? i * width + j : 0;
+
+  const float T_final = inside ? 1.f - alphas[p] : 1.f;
+  float T = T_final;
+  float buffer[CHA], vr[CHA];
+#pragma unroll
+  for (int k = 0; k < CHA; ++k) {
+    buffer[k] = 0.f;
+    vr[k] = (CH > 0 && inside && k < wa.n_real) ? v_render[(size_t)p * wa.ps + k] : 0.f;
+  }
+  float buffer_d = 0.f, vr_d = 0.f;  // the depth channel (DEPTH)
+  if constexpr (DEPTH) vr_d = inside ? v_render[(size_t)p * wa.ps + wa.n_real] : 0.f;
+  float bg_vr = 0.f;  // sum_k bg[k] v_render[k] (BG)
+  if constexpr (BG) {
+#pragma unroll
+    for (int k = 0; k < CH; ++k)
+      if (k < wa.n_real) bg_vr += wa.bg[(size_t)blockIdx.y * wa.cs + k] * vr[k];
+  }
+  const float va_pix = (inside && v_alphas) ? v_alphas[p] : 0.f;
+  // a pixel nothing contributed to has alpha == 0 exactly; mark it with last = -1
+  const int bin_final = (inside && alphas[p] > 0.f) ? last_ids[p] : -1;
+  int wave_last = bin_final;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) wave_last = max(wave_last, __shfl_xor(wave_last, d, 64));
+
+  const int n_batches = (end - start + STAGE - 1) / STAGE;
+  for (int b = 0; b < n_batches; ++b) {
+    __syncthreads();
+    const int batch_end = end - 1 - STAGE * b;
+    const int size = min(STAGE, batch_end + 1 - start);
+    for (int e = tid; e < size; e += THREADS) {
+      const int g = flat[batch_end - e];
+      const float4 s0 = splat[2 * g], s1 = splat[2 * g + 1];
+      sA[e] = s0;
+      sB[e] = make_float4(s1.x, s1.y, DEPTH ? s1.z : 0.f, __int_as_float(g));
+    }
+    if constexpr (CH > 0) stage_colors<CH, THREADS>(sC, colors, flat, batch_end, -1, size, wa);
+    __syncthreads();
+    for (int t = max(0, batch_end - wave_last); t < size; ++t) {
+      bool valid = inside && (batch_end - t <= bin_final);
+      const float4 A = sA[t], B = sB[t];
+      const float dx = A.x - px, dy = A.y - py;
+      float vis = 0.f, alpha = 0.f;
+      if (valid) {
+        const float sigma = 0.5f * (A.z * dx * dx + B.x * dy * dy) + A.w * dx * dy;
+        vis = __expf(-sigma);
+        alpha = fminf(kAlphaMax, B.y * vis);
+        if (sigma < 0.f || alpha < kAlphaMin) valid = false;
+      }
+      if (!__any(valid)) continue;
+      float r_rgb[CHA];
+#pragma unroll
+      for (int k = 0; k < CHA; ++k) r_rgb[k] = 0.f;
+      float r_d = 0.f;
+      float gv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // g2d record: gx gy |gx| |gy| ga gb gc go
+      if (valid) {
+        const float ra = 1.f / (1.f - alpha);
+        T *= ra;
+        const float fac = alpha * T;
+        float v_alpha = 0.f;
+        if constexpr (CH > 0) {
+#pragma unroll
+          for (int k = 0; k < CH; ++k) {
+            r_rgb[k] = fac * vr[k];
+            v_alpha += (sC[t * CH + k] * T - buffer[k] * ra) * vr[k];
+          }
+        }
+        if constexpr (DEPTH) {
+          r_d = fac * vr_d;
+          v_alpha += (B.z * T - buffer_d * ra) * vr_d;
+        }
+        v_alpha += T_final * ra * va_pix;
+        if constexpr (BG) v_alpha += -T_final * ra * bg_vr;
+        if (B.y * vis <= kAlphaMax) {
+          const float v_sigma = -B.y * vis * v_alpha;
+          gv[0] = v_sigma * (A.z * dx + A.w * dy);
+          gv[1] = v_sigma * (A.w * dx + B.x * dy);
+          gv[2] = fabsf(gv[0]);
+          gv[3] = fabsf(gv[1]);
+          gv[4] = 0.5f * v_sigma * dx * dx;
+          gv[5] = v_sigma * dx * dy;
+          gv[6] = 0.5f * v_sigma * dy * dy;
+          gv[7] = vis * v_alpha;
+        }
+        if constexpr (CH > 0) {
+#pragma unroll
+          for (int k = 0; k < CH; ++k) buffer[k] += sC[t * CH + k] * fac;
+        }
+        if constexpr (DEPTH) buffer_d += B.z * fac;
+      }
+      const int g = __float_as_int(B.w);
+      // component k of the colour sums in lane k (k < CH), of the splat-side sums in lane 32 + k
+      float c_sum = 0.f;
+      if constexpr (CH > 0) c_sum = lane_transpose_sum<CH>(r_rgb, lane);
+      const float g_sum = lane_transpose_sum<8>(gv, lane);
+      float *dst = nullptr;
+      float val = 0.f;
+      if (lane < 32) {
+        if (CH > 0 && v_colors && lane < wa.n_real) { dst = v_colors + (size_t)g * wa.cs + lane; val = c_sum; }
+      } else if (lane < 40) {
+        dst = g2d + (size_t)g * 8 + (lane - 32);
+        val = g_sum;
+      }
+      if constexpr (DEPTH) {
+        r_d = wave_sum_dpp_f(r_d);  // (the sum lands in lane 63)
+        if (lane == 63) { dst = wa.v_depths + (size_t)blockIdx.y * wa.N + g; val = r_d; }
+      }
+      if (dst) unsafeAtomicAdd(dst, val);
+    }
+  }
+}
+
+}  // namespace eg
+
+using namespace eg;
+
+// ---------------------------------------------------------------------------------------------
+// (macros, not functions: the error message names the entry point)
+#define EG_TS_RANGES(C, ranges_host, width, height, tile_size)                                         \
+  EG_REQUIRE(tile_size_ok(tile_size), "tile_size must be 8 or 32 (16: eg_tile_count, eg_tile_emit)");   \
+  EG_REQUIRE(C >= 1 && C <= 65535 && width > 0 && height > 0, "bad sizes");                            \
+  EG_REQUIRE(ranges_host, "null pointer");                                                             \
+  EG_REQUIRE(ranges_host[0] >= 0, "bad ranges");                                                       \
+  for (int c_ = 0; c_ < C; ++c_)                                                                       \
+    EG_REQUIRE(ranges_host[c_ + 1] >= ranges_host[c_] && ranges_host[c_ + 1] - ranges_host[c_] < (1ll << 31), "bad ranges")
+
+extern "C" int eg_tile_count_ts(const float *means2d, const int32_t *radii, const int64_t *ranges_host, int32_t C,
+                                int32_t width, int32_t height, int32_t tile_size, int32_t *tiles_per_gauss,
+                                int32_t *tile_counts, eg_stream_t stream) {
+  EG_TS_RANGES(C, ranges_host, width, height, tile_size);
+  if (ranges_host[C] == ranges_host[0]) return EG_OK;
+  EG_REQUIRE(means2d && radii && tile_counts, "null pointer");
+  const int tw = cdiv(width, tile_size), th = cdiv(height, tile_size);
+  const int64_t T = (int64_t)tw * th;
+  EG_REQUIRE(T < (1ll << 31), "bad sizes");
+  for (int c = 0; c < C; ++c) {
+    const int64_t b = ranges_host[c];
+    const int n = (int)(ranges_host[c + 1] - b);
+    if (n == 0) continue;
+    int32_t *tpg = tiles_per_gauss ? tiles_per_gauss + b : nullptr;
+    if (T <= kTsMaxLdsWords)
+      ts_count_kernel<true><<<cdiv(n, kTsBinThreads), kTsBinThreads, sizeof(int) * T, as_stream(stream)>>>(
+          (const float2 *)means2d + b, radii + b, n, (float)tile_size, tw, th, tpg, tile_counts + T * c);
+    else
+      ts_count_kernel<false><<<cdiv(n, kTsBinThreads), kTsBinThreads, 0, as_stream(stream)>>>(
+          (const float2 *)means2d + b, radii + b, n, (float)tile_size, tw, th, tpg, tile_counts + T * c);
+  }
+  return check_launch("tile_count_ts");
+}
+
+extern "C" int eg_tile_emit_sort_ts(const float *means2d, const int32_t *radii, const float *depths,
+                                    const int64_t *ranges_host, int32_t C, int32_t width, int32_t height,
+                                    int32_t tile_size, const int32_t *offsets, int32_t *tile_counts,
+                                    const int64_t *M_host, uint64_t *keys, int32_t *flatten_ids, int64_t *isect_ids,
+                                    const int32_t *max_tile_host, int32_t rebase, eg_stream_t stream) {
+  EG_TS_RANGES(C, ranges_host, width, height, tile_size);
+  EG_REQUIRE(offsets && tile_counts && M_host, "null pointer");
+  const int tw = cdiv(width, tile_size), th = cdiv(height, tile_size);
+  const int64_t T64 = (int64_t)tw * th;
+  EG_REQUIRE(T64 < (1ll << 30), "bad sizes");
+  const int T = (int)T64;
+  int tile_bits = 0;
+  while ((1 << tile_bits) <= T) ++tile_bits;  // floor(log2(T)) + 1
+  for (int c = 0; c < C; ++c) {  // (everything is checked before the first launch)
+    const int64_t n = ranges_host[c + 1] - ranges_host[c], M = M_host[c];
+    EG_REQUIRE(M >= 0 && (!rebase || ranges_host[c] < (1ll << 31)), "bad sizes");
+    EG_REQUIRE(M == 0 || (n > 0 && means2d && radii && depths && keys && flatten_ids), "null pointer");
+  }
+  int64_t m_base = 0;
+  for (int c = 0; c < C; ++c) {
+    const int64_t b = ranges_host[c], M = M_host[c];
+    const int n = (int)(ranges_host[c + 1] - b);
+    if (M > 0) {
+      const int32_t *offs = offsets + (size_t)(T + 1) * c;
+      if (2 * T <= kTsMaxLdsWords)
+        ts_emit_kernel<true><<<cdiv(n, kTsBinThreads), kTsBinThreads, sizeof(int) * 2 * T, as_stream(stream)>>>(
+            (const float2 *)means2d + b, radii + b, depths + b, n, (float)tile_size, tw, th, offs,
+            tile_counts + (size_t)T * c, (long long)M, (unsigned long long *)keys + m_base);
+      else
+        ts_emit_kernel<false><<<cdiv(n, kTsBinThreads), kTsBinThreads, 0, as_stream(stream)>>>(
+            (const float2 *)means2d + b, radii + b, depths + b, n, (float)tile_size, tw, th, offs,
+            tile_counts + (size_t)T * c, (long long)M, (unsigned long long *)keys + m_base);
+      int rc = check_launch("tile_emit_sort_ts");
+      if (rc) return rc;
+      int64_t *ids = isect_ids ? isect_ids + m_base : nullptr;
+      rc = eg_sort_pairs(keys + m_base, offs, T, M, flatten_ids + m_base, ids, max_tile_host ? max_tile_host[c] : 0, stream);
+      if (rc) return rc;
+      const int id_base = rebase ? (int)b : 0;
+      if (id_base != 0 || (ids && c > 0)) {
+        ts_rebase_kernel<<<cdiv(M, 256), 256, 0, as_stream(stream)>>>(flatten_ids + m_base, (long long *)ids, (long long)M,
+                                                                     id_base, (long long)c << (32 + tile_bits));
+        rc = check_launch("tile_emit_sort_ts");
+        if (rc) return rc;
+      }
+    }
+    m_base += M;
+  }
+  return EG_OK;
+}
+
+#define EG_TS_CHECK(C, N, channels, n_real, depth, width, height, tile_size, cs, ps)                          \
+  EG_REQUIRE(tile_size_ok(tile_size), "tile_size must be 8 or 32 (16: eg_composite_*_wide_cams)");            \
+  EG_REQUIRE(C >= 1 && C <= 65535 && N >= 0 && width > 0 && height > 0, "bad sizes");                         \
+  EG_REQUIRE(channels >= 0 && channels <= 32, "channels (the chunk width) must be 0 .. 32");                  \
+  EG_REQUIRE(channels > 0 || depth, "channels == 0 (depth only) needs the depth channel");                    \
+  EG_REQUIRE(channels > 0 ? (n_real >= 1 && n_real <= channels) : n_real == 0, "n_real must be 1 .. channels"); \
+  EG_REQUIRE(channels == 0 || cs >= n_real, "color_stride is smaller than the channel count");                \
+  EG_REQUIRE(ps >= n_real + (depth ? 1 : 0), "pixel_stride is smaller than the channel count");               \
+  EG_REQUIRE((int64_t)cdiv(width, tile_size) * cdiv(height, tile_size) * 4 < (1ll << 31), "bad sizes")
+
+#define EG_TS_DB(LAUNCH, TS, CH)                                                        \
+  do {                                                                                  \
+    if (depth) { if (bg) LAUNCH(TS, CH, true, true); else LAUNCH(TS, CH, true, false); } \
+    else { if (bg) LAUNCH(TS, CH, false, true); else LAUNCH(TS, CH, false, false); }     \
+  } while (0)
+
+#define EG_TS_CH(LAUNCH, TS)                            \
+  do {                                                  \
+    if (channels == 0) LAUNCH(TS, 0, true, false);      \
+    else if (channels <= 2) EG_TS_DB(LAUNCH, TS, 2);    \
+    else if (channels <= 4) EG_TS_DB(LAUNCH, TS, 4);    \
+    else if (channels <= 8) EG_TS_DB(LAUNCH, TS, 8);    \
+    else if (channels <= 16) EG_TS_DB(LAUNCH, TS, 16);  \
+    else EG_TS_DB(LAUNCH, TS, 32);                      \
+  } while (0)
+
+#define EG_TS_DISPATCH(LAUNCH)                                                   \
+  do {                                                                           \
+    if (tile_size == 8) EG_TS_CH(LAUNCH, 8); else EG_TS_CH(LAUNCH, 32);          \
+  } while (0)
+
+// the colour rows can be fetched in 16-byte (CH = 2: 8-byte) units
+static int ts_rows_aligned(const float *colors, int channels, int cs) {
+  if (channels == 0) return 0;
+  const int vw = channels <= 2 ? 2 : 4;
+  return ((uintptr_t)colors % (vw * sizeof(float)) == 0) && (cs % vw == 0);
+}
+
+extern "C" int eg_composite_fwd_ts_cams(int32_t C, const float *splat, int32_t N, const float *colors,
+                                        int32_t colors_per_camera, int32_t channels, int32_t depth,
+                                        const float *backgrounds, const int32_t *offsets, const int32_t *flatten_ids,
+                                        int32_t width, int32_t height, int32_t tile_size, float *render, float *alphas,
+                                        int32_t *last_ids, int32_t n_real, int32_t color_stride, int32_t pixel_stride,
+                                        eg_stream_t stream) {
+  EG_TS_CHECK(C, N, channels, n_real, depth, width, height, tile_size, color_stride, pixel_stride);
+  EG_REQUIRE(channels == 0 || colors, "null colors (channels > 0)");
+  EG_REQUIRE(splat && offsets && flatten_ids && render, "null pointer");
+  const int tw = cdiv(width, tile_size), th = cdiv(height, tile_size);
+  const float *bg = channels > 0 ? backgrounds : nullptr;
+  const WideArgs wa = {bg, nullptr, N, colors_per_camera != 0, n_real, color_stride, pixel_stride,
+                       ts_rows_aligned(colors, channels, color_stride)};
+  hipStream_t s = as_stream(stream);
+#define EG_LAUNCH_FWD_TS(TS, CH, DEPTH, BG)                                                                     \
+  ts_composite_fwd_kernel<TS, CH, DEPTH, BG><<<dim3(tw * th * ts_sub(TS), C), ts_threads(TS), 0, s>>>(          \
+      (const float4 *)splat, colors, offsets, flatten_ids, width, height, tw, th, render, alphas, last_ids, wa)
+  EG_TS_DISPATCH(EG_LAUNCH_FWD_TS);
+#undef EG_LAUNCH_FWD_TS
+  return check_launch("composite_fwd_ts_cams");
+}
+
+extern "C" int eg_composite_bwd_ts_cams(int32_t C, const float *splat, int32_t N, const float *colors,
+                                        int32_t colors_per_camera, int32_t channels, int32_t depth,
+                                        const float *backgrounds, const int32_t *offsets, const int32_t *flatten_ids,
+                                        int32_t width, int32_t height, int32_t tile_size, const float *alphas,
+                                        const int32_t *last_ids, const float *v_render, const float *v_alphas,
+                                        float *g2d, float *v_colors, float *v_depths, int32_t n_real,
+                                        int32_t color_stride, int32_t pixel_stride, eg_stream_t stream) {
+  EG_TS_CHECK(C, N, channels, n_real, depth, width, height, tile_size, color_stride, pixel_stride);
+  EG_REQUIRE(channels == 0 || colors, "null colors (channels > 0)");
+  EG_REQUIRE(splat && offsets && flatten_ids && alphas && last_ids && v_render && g2d, "null pointer");
+  EG_REQUIRE(!depth || v_depths, "null v_depths (depth channel)");
+  const int tw = cdiv(width, tile_size), th = cdiv(height, tile_size);
+  const float *bg = channels > 0 ? backgrounds : nullptr;
+  const WideArgs wa = {bg, v_depths, N, colors_per_camera != 0, n_real, color_stride, pixel_stride,
+                       ts_rows_aligned(colors, channels, color_stride)};
+  hipStream_t s = as_stream(stream);
+#define EG_LAUNCH_BWD_TS(TS, CH, DEPTH, BG)                                                                     \
+  ts_composite_bwd_kernel<TS, CH, DEPTH, BG><<<dim3(tw * th * ts_sub(TS), C), ts_threads(TS), 0, s>>>(          \
+      (const float4 *)splat, colors, offsets, flatten_ids, width, height, tw, th, alphas, last_ids, v_render,      \
+      v_alphas, g2d, v_colors, wa)
+  EG_TS_DISPATCH(EG_LAUNCH_BWD_TS);
+#undef EG_LAUNCH_BWD_TS
+  return check_launch("composite_bwd_ts_cams");
+}
+#undef EG_TS_DISPATCH
+#undef EG_TS_CH
+#undef EG_TS_DB
+#undef EG_TS_CHECK
+#undef EG_TS_RANGES

@@ -28,6 +28,7 @@ from . import sh as _sh
 from ._lib import call, ptr, stream
 
 TILE = 16
+TILE_SIZES = (8, 16, 32)  # 8 and 32: csrc/tiles.hip (counting, emission and compositing of their own)
 import os as _os
 _FAST_ENABLED = bool(int(_os.environ.get("EG_OPERATOR_FAST", "1")))
 
@@ -42,14 +43,15 @@ def _check(t: Tensor, shape, name: str, dtype=torch.float32):
 
 
 class _Projection(torch.autograd.Function):
-    """gsplat ``fully_fused_projection`` (packed=False) for C cameras, tile counting fused in."""
+    """gsplat ``fully_fused_projection`` (packed=False) for C cameras, tile counting fused in (tile_size 16; any other
+    tile size: the projection without its counting, then eg_tile_count_ts)."""
 
     @staticmethod
     def forward(ctx, means, quats, scales, opac_for_splat, viewmats, Ks, width, height, eps2d,
-                near_plane, far_plane, radius_clip, antialiased):
+                near_plane, far_plane, radius_clip, antialiased, tile_size=TILE):
         Cn, N = viewmats.shape[0], means.shape[0]
         dev = means.device
-        tw, th = math.ceil(width / TILE), math.ceil(height / TILE)
+        tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
         means_c, quats_c, scales_c = means.contiguous(), quats.contiguous(), scales.contiguous()
         opac_c = opac_for_splat.contiguous()
         vm, Kc = viewmats.contiguous(), Ks.contiguous()
@@ -63,9 +65,13 @@ class _Projection(torch.autograd.Function):
         counts = torch.zeros(Cn, tw * th, dtype=torch.int32, device=dev)
         flags = _lib.FLAG_ANTIALIASED if antialiased else 0
         # (round 6: the C cameras by ONE native call -- csrc/cams.hip loops over the per-camera launcher)
+        fused = tile_size == TILE  # (the counting fused into the projection kernel is the 16-pixel one)
         call("eg_project_fwd_cams", ptr(means_c), ptr(quats_c), ptr(scales_c), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height,
              near_plane, far_plane, eps2d, radius_clip, flags, ptr(splat), ptr(radii), ptr(means2d), ptr(depths), ptr(conics),
-             ptr(comps), ptr(tpg), ptr(counts), stream())
+             ptr(comps), ptr(tpg) if fused else None, ptr(counts) if fused else None, stream())
+        if not fused:
+            call("eg_tile_count_ts", ptr(means2d), ptr(radii), (C.c_int64 * (Cn + 1))(*[c * N for c in range(Cn + 1)]), Cn,
+                 width, height, tile_size, ptr(tpg), ptr(counts), stream())
         ctx.save_for_backward(means_c, quats_c, scales_c, opac_c, vm, Kc, splat)
         ctx.cfg = (width, height, eps2d, flags)
         ctx.mark_non_differentiable(radii, tpg, counts, splat)
@@ -107,7 +113,7 @@ class _Projection(torch.autograd.Function):
                 call("eg_project_bwd_viewmats", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width,
                      height, eps2d, flags, ptr(splat), None, 0, None, ptr(g2d), ptr(vcomp), ptr(vdep), ptr(scratch), blocks,
                      ptr(v_viewmats), stream())
-        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 8
+        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 9
 
 
 _DUMMY: Dict = {}
@@ -131,14 +137,15 @@ class _PackedProjection(torch.autograd.Function):
     (indptr, hence nnz: the synchronisation gsplat has there too), eg_packed_write.  Backward: eg_packed_bwd (dense
     [N, k] gradients, summed over the cameras in camera order, no atomics) or, with `sparse_grad`, eg_packed_bwd_sparse
     (sparse COO gradients of size [N, k] with indices gaussian_ids[None] and values [nnz, k], coalesced iff C == 1).
-    `holder` receives the host copy of indptr."""
+    `holder` receives the host copy of indptr.  A `tile_size` other than 16: eg_packed_write counts 16-pixel tiles into
+    a throw-away buffer, and eg_tile_count_ts counts the pairs' tiles of the asked size."""
 
     @staticmethod
     def forward(ctx, means, quats, scales, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-                radius_clip, antialiased, sparse_grad, holder):
+                radius_clip, antialiased, sparse_grad, holder, tile_size=TILE):
         Cn, N = viewmats.shape[0], means.shape[0]
         dev = means.device
-        tw, th = math.ceil(width / TILE), math.ceil(height / TILE)
+        tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
         means_c, quats_c, scales_c = means.contiguous(), quats.contiguous(), scales.contiguous()
         opac_c = opac_for_splat.contiguous()
         vm, Kc = viewmats.contiguous(), Ks.contiguous()
@@ -163,9 +170,13 @@ class _PackedProjection(torch.autograd.Function):
         camera_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
         gaussian_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
         counts = torch.zeros(Cn, tw * th, **i32)
+        counts16 = counts if tile_size == TILE else torch.zeros(Cn, math.ceil(width / TILE) * math.ceil(height / TILE), **i32)
         call("eg_packed_write", ptr(means_c), ptr(quats_c), ptr(scales_c), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height,
              near_plane, far_plane, eps2d, radius_clip, flags, ptr(block_base), nnz, ptr(splat), ptr(radii), ptr(means2d),
-             ptr(depths), ptr(conics), ptr(comps), ptr(tpg), ptr(camera_ids), ptr(gaussian_ids), ptr(counts), stream())
+             ptr(depths), ptr(conics), ptr(comps), ptr(tpg), ptr(camera_ids), ptr(gaussian_ids), ptr(counts16), stream())
+        if tile_size != TILE:  # (tiles_per_gauss is written again, for this tile size)
+            call("eg_tile_count_ts", ptr(means2d), ptr(radii), (C.c_int64 * (Cn + 1))(*indptr_host), Cn, width, height,
+                 tile_size, ptr(tpg), ptr(counts), stream())
         holder["indptr"] = indptr_host
         ctx.save_for_backward(means_c, quats_c, scales_c, opac_c, vm, Kc, indptr, camera_ids, gaussian_ids)
         ctx.cfg = (width, height, eps2d, flags, bool(sparse_grad))
@@ -212,7 +223,7 @@ class _PackedProjection(torch.autograd.Function):
             call("eg_project_bwd_viewmats", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width,
                  height, eps2d, flags, None, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d),
                  ptr(vcomp), ptr(vdep), ptr(scratch), blocks, ptr(v_viewmats), stream())
-        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 10
+        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 11
 
 
 class _Compositing(torch.autograd.Function):
@@ -407,6 +418,78 @@ class _WideCompositing(torch.autograd.Function):
             means2d.absgrad = g2d[..., 2:4].contiguous()
         return (g2d[..., 0:2].contiguous(), g2d[..., 4:7].contiguous(), v_colors, g2d[..., 7].contiguous(), v_depths, v_bg,
                 None, None, None, None, None, None, None, None, None)
+
+
+class _TileCompositing(torch.autograd.Function):
+    """`_WideCompositing` on tiles of 8 or 32 pixels (csrc/tiles.hip, eg_composite_{fwd,bwd}_ts_cams): every channel
+    count goes through the one kernel family, D = 1 and 3 included, in chunks of `chunk` channels; `colors` None (the
+    depth-only modes) is one launch each way of the form that stages no colours."""
+
+    @staticmethod
+    def forward(ctx, means2d, conics, colors, opacities, depths, backgrounds, width, height, offsets, flatten_ids,
+                absgrad, packed_splat, depth, chunk, tile_size, packed_cams=None):
+        # (packed_cams: as in _ModeCompositing)
+        Cn, N = (packed_cams, _lib.PACKED_STRIDE) if packed_cams is not None else (means2d.shape[0], means2d.shape[1])
+        _ptr1 = _ptr_or_dummy if packed_cams is not None else ptr
+        dev = means2d.device
+        D = colors.shape[-1] if colors is not None else 0
+        colors_c = colors.contiguous() if colors is not None else None
+        bg = backgrounds.contiguous() if (backgrounds is not None and D > 0) else None
+        P = D + int(depth)
+        render = torch.empty(Cn, height, width, P, device=dev)
+        alphas = torch.empty(Cn, height, width, 1, device=dev)
+        last_ids = torch.empty(Cn, height, width, dtype=torch.int32, device=dev)
+        per_cam = int(colors_c is not None and (colors_c.dim() == 3 or packed_cams is not None))
+        if D == 0:
+            call("eg_composite_fwd_ts_cams", Cn, _ptr1(packed_splat), N, None, 0, 0, 1, None, ptr(offsets), ptr(flatten_ids),
+                 width, height, tile_size, ptr(render), ptr(alphas), ptr(last_ids), 0, 0, P, stream())
+        for c0 in range(0, D, chunk):
+            w = min(chunk, D - c0)
+            first, final = c0 == 0, c0 + w == D
+            call("eg_composite_fwd_ts_cams", Cn, _ptr1(packed_splat), N, _ptr1(colors_c) + 4 * c0, per_cam, w,
+                 int(depth and final), ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width,
+                 height, tile_size, ptr(render) + 4 * c0, ptr(alphas) if first else None, ptr(last_ids) if first else None,
+                 w, D, P, stream())
+        ctx.save_for_backward(means2d, packed_splat, colors_c, bg, alphas, last_ids, offsets, flatten_ids)
+        ctx.cfg = (width, height, absgrad, depth, D, per_cam, chunk, tile_size, packed_cams)
+        ctx.mark_non_differentiable(last_ids)
+        return render, alphas, last_ids
+
+    @staticmethod
+    def backward(ctx, v_render, v_alphas, _v_last):
+        width, height, absgrad, depth, D, per_cam, chunk, tile_size, packed_cams = ctx.cfg
+        means2d, splat, colors, bg, alphas, last_ids, offsets, flatten_ids = ctx.saved_tensors
+        Cn, N = (packed_cams, _lib.PACKED_STRIDE) if packed_cams is not None else (means2d.shape[0], means2d.shape[1])
+        lead = tuple(means2d.shape[:-1])  # (C, N), or (nnz,) on packed records
+        _ptr1 = _ptr_or_dummy if packed_cams is not None else ptr
+        dev = means2d.device
+        P = D + int(depth)
+        v_render = v_render.contiguous()
+        v_alphas = v_alphas.contiguous()
+        g2d = torch.zeros(*lead, 8, device=dev)
+        v_colors = torch.zeros(*lead, D, device=dev) if (D > 0 and ctx.needs_input_grad[2]) else None
+        v_depths = torch.zeros(*lead, device=dev) if depth else None
+        if D == 0:
+            call("eg_composite_bwd_ts_cams", Cn, _ptr1(splat), N, None, 0, 0, 1, None, ptr(offsets), ptr(flatten_ids), width,
+                 height, tile_size, ptr(alphas), ptr(last_ids), ptr(v_render), ptr(v_alphas), _ptr1(g2d), None,
+                 _ptr1(v_depths), 0, 0, P, stream())
+        for c0 in range(0, D, chunk):
+            w = min(chunk, D - c0)
+            first, final = c0 == 0, c0 + w == D
+            call("eg_composite_bwd_ts_cams", Cn, _ptr1(splat), N, _ptr1(colors) + 4 * c0, per_cam, w, int(depth and final),
+                 ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width, height, tile_size,
+                 ptr(alphas), ptr(last_ids), ptr(v_render) + 4 * c0, ptr(v_alphas) if first else None, _ptr1(g2d),
+                 _ptr1(v_colors) + 4 * c0 if v_colors is not None else None,
+                 _ptr1(v_depths) if (depth and final) else None, w, D, P, stream())
+        if v_colors is not None and not per_cam:
+            v_colors = v_colors.sum(0)
+        v_bg = None
+        if bg is not None and ctx.needs_input_grad[5]:  # (gsplat computes it in torch the same way)
+            v_bg = (v_render[..., :D] * (1.0 - alphas)).sum((1, 2))
+        if absgrad:
+            means2d.absgrad = g2d[..., 2:4].contiguous()
+        return (g2d[..., 0:2].contiguous(), g2d[..., 4:7].contiguous(), v_colors, g2d[..., 7].contiguous(), v_depths, v_bg,
+                None, None, None, None, None, None, None, None, None, None)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -826,40 +909,84 @@ def isect_tiles_and_sort_cams(means2d: Tensor, radii: Tensor, depths: Tensor, co
             [item_offsets[c] for c in range(Cn)], [total[c] for c in range(Cn)], n_items, extra)
 
 
+def isect_tiles_and_sort_ts(means2d: Tensor, radii: Tensor, depths: Tensor, ranges, counts: Tensor, width: int, height: int,
+                            tile_size: int, rebase: bool):
+    """Binning on tiles of `tile_size` pixels (csrc/tiles.hip) for C cameras by TWO native calls and one host read-back:
+    the C tile scans, then -- the M_c known -- eg_tile_emit_sort_ts.  Camera c owns entries [ranges[c], ranges[c + 1]) of
+    the flat inputs; `counts` [C, T] holds eg_tile_count_ts's counts and is returned to zero.  Returns offsets [C, T + 1]
+    (each row local to its camera's list), the cameras' flatten_ids and isect_ids one after the other (max(M, 1)
+    entries; the ids index the camera's own range, or with `rebase` the whole list; the isect ids carry the camera)
+    and the M_c."""
+    dev = means2d.device
+    Cn, T = counts.shape
+    offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
+    item_offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
+    total = torch.zeros(Cn, 4, dtype=torch.int32, device=dev)  # total[:, 1] (overflow) is sticky: start from zero
+    call("eg_tile_offsets_cams", ptr(counts), T, Cn, 1 << 40, ptr(offsets), ptr(item_offsets), ptr(total), stream())
+    vals = total.reshape(-1).tolist()  # the read-back of the M_c
+    Ms = [int(vals[4 * c]) for c in range(Cn)]
+    nmax = [int(vals[4 * c + 3]) for c in range(Cn)]
+    M = sum(Ms)
+    keys = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+    flat = torch.zeros(max(M, 1), dtype=torch.int32, device=dev)
+    ids = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+    call("eg_tile_emit_sort_ts", ptr(means2d), ptr(radii), ptr(depths), (C.c_int64 * (Cn + 1))(*ranges), Cn, width, height,
+         tile_size, ptr(offsets), ptr(counts), (C.c_int64 * Cn)(*Ms), ptr(keys), ptr(flat), ptr(ids), (C.c_int32 * Cn)(*nmax),
+         int(rebase), stream())
+    return offsets, flat, ids, Ms
+
+
 RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
 
 
 def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
-                        radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree=None, chunk=None):
+                        radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree=None, chunk=None,
+                        tile_size=TILE):
     """`rasterization` with a depth channel and / or backgrounds: the general two-node path (projection -> compositing)
     with the compositing of eg_composite_{fwd,bwd}_modes_cams, which takes `depths` as an input.  With `sh_degree`,
     `colors` holds the coefficients and the colours are evaluated behind the projection (its radii are their mask).
     With `chunk` (colours of a channel count other than 1 or 3, in any mode that renders them): the same projection,
-    binning and sort, then the compositing of eg_composite_{fwd,bwd}_wide_cams in chunks of `chunk` channels."""
+    binning and sort, then the compositing of eg_composite_{fwd,bwd}_wide_cams in chunks of `chunk` channels.
+    With a `tile_size` of 8 or 32 (always with `chunk`): counting, emission and compositing by csrc/tiles.hip."""
     N, Cn = means.shape[0], viewmats.shape[0]
     depth = render_mode != "RGB"
     if render_mode in ("D", "ED"):
         colors, backgrounds = None, None  # (gsplat: the depth is the only channel, its background is 0)
     radii, means2d, depths, conics, comps, tpg, counts, _splat = _Projection.apply(
         means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
-        float(near_plane), float(far_plane), float(radius_clip), antialiased)
+        float(near_plane), float(far_plane), float(radius_clip), antialiased, tile_size)
     if sh_degree is not None and colors is not None:
         colors = _sh.view_colors(means, viewmats, colors, radii, sh_degree)
     opac = opacities[None, :].expand(Cn, N)
     if antialiased:
         opac = opac * comps
-    tw, th = math.ceil(width / TILE), math.ceil(height / TILE)
+    tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
     tile_bits = int(math.floor(math.log2(tw * th))) + 1
     with torch.no_grad():
-        o_l, f_l, i_l, Ms = isect_tiles_and_sort_cams(means2d.contiguous(), radii, depths.contiguous(), counts, width,
-                                                      height)[:4]
-        offsets = torch.stack(o_l)  # [C, T+1], each row local to its camera's list
-        flat = torch.cat(f_l) if sum(Ms) > 0 else torch.zeros(1, dtype=torch.int32, device=means.device)
-        bases = [sum(Ms[:c]) for c in range(Cn)]
-        binfo = {"isect_ids": torch.cat([i_l[c] | (c << (32 + tile_bits)) for c in range(Cn)]),
-                 "flatten_ids": torch.cat([f_l[c] + c * N for c in range(Cn)]),
-                 "isect_offsets": torch.stack([(o_l[c][:-1] + bases[c]).reshape(th, tw) for c in range(Cn)])}
-    if chunk is not None and colors is not None:
+        if tile_size != TILE:
+            offsets, flat, ids, Ms = isect_tiles_and_sort_ts(
+                means2d.contiguous(), radii, depths.contiguous(), [c * N for c in range(Cn + 1)], counts, width, height,
+                tile_size, rebase=False)
+            M = sum(Ms)
+            bases = torch.tensor([sum(Ms[:c]) for c in range(Cn)], dtype=torch.int32, device=means.device)
+            cam_base = torch.repeat_interleave(torch.arange(Cn, dtype=torch.int32, device=means.device) * N,
+                                               torch.tensor(Ms, device=means.device), output_size=M)
+            binfo = {"isect_ids": ids[:M], "flatten_ids": flat[:M] + cam_base,
+                     "isect_offsets": (offsets[:, :-1] + bases[:, None]).reshape(Cn, th, tw)}
+        else:
+            o_l, f_l, i_l, Ms = isect_tiles_and_sort_cams(means2d.contiguous(), radii, depths.contiguous(), counts, width,
+                                                          height)[:4]
+            offsets = torch.stack(o_l)  # [C, T+1], each row local to its camera's list
+            flat = torch.cat(f_l) if sum(Ms) > 0 else torch.zeros(1, dtype=torch.int32, device=means.device)
+            bases = [sum(Ms[:c]) for c in range(Cn)]
+            binfo = {"isect_ids": torch.cat([i_l[c] | (c << (32 + tile_bits)) for c in range(Cn)]),
+                     "flatten_ids": torch.cat([f_l[c] + c * N for c in range(Cn)]),
+                     "isect_offsets": torch.stack([(o_l[c][:-1] + bases[c]).reshape(th, tw) for c in range(Cn)])}
+    if tile_size != TILE:
+        render, alphas, last_ids = _TileCompositing.apply(
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            bool(absgrad), _splat, depth, chunk, tile_size)
+    elif chunk is not None and colors is not None:
         render, alphas, last_ids = _WideCompositing.apply(
             means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
             bool(absgrad), _splat, depth, chunk)
@@ -874,7 +1001,7 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
         "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
         "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
         **binfo,
-        "width": width, "height": height, "tile_size": TILE, "n_cameras": Cn,
+        "width": width, "height": height, "tile_size": tile_size, "n_cameras": Cn,
         "last_ids": last_ids,
     }
     return render, alphas, info
@@ -882,11 +1009,12 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
 
 def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
                           radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree, chunk,
-                          sparse_grad):
+                          sparse_grad, tile_size=TILE):
     """`rasterization(packed=True)`: the packed projection (_PackedProjection), the colours / opacities gathered per pair
     in torch (dense gradients of the caller's shapes, as in gsplat), every camera's range binned as a single-camera
     problem (eg_packed_bin), and the mode / wide compositing kernels on the packed records (record stride
-    _lib.PACKED_STRIDE).  Never the unit-colour fast path.  Two host read-backs: indptr, then the M_c."""
+    _lib.PACKED_STRIDE).  Never the unit-colour fast path.  Two host read-backs: indptr, then the M_c.  With a
+    `tile_size` of 8 or 32 (always with `chunk`): counting, emission and compositing by csrc/tiles.hip."""
     N, Cn = means.shape[0], viewmats.shape[0]
     dev = means.device
     depth = render_mode != "RGB"
@@ -895,7 +1023,7 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
     holder: Dict = {}
     radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids = _PackedProjection.apply(
         means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
-        float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder)
+        float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder, tile_size)
     indptr = holder["indptr"]
     nnz = indptr[-1]
     if colors is not None:
@@ -913,23 +1041,28 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
     opac = opacities[gaussian_ids]
     if antialiased:
         opac = opac * comps
-    tw, th = math.ceil(width / TILE), math.ceil(height / TILE)
+    tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
     T = tw * th
     with torch.no_grad():
-        offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
-        item_offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
-        total = torch.zeros(Cn, 4, dtype=torch.int32, device=dev)
-        call("eg_tile_offsets_cams", ptr(counts), T, Cn, 1 << 40, ptr(offsets), ptr(item_offsets), ptr(total), stream())
-        vals = total.reshape(-1).tolist()  # the second and last read-back of the call
-        Ms = [int(vals[4 * c]) for c in range(Cn)]
-        nmax = [int(vals[4 * c + 3]) for c in range(Cn)]
-        M = sum(Ms)
-        keys = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
-        flat = torch.zeros(max(M, 1), dtype=torch.int32, device=dev)
-        ids = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
-        call("eg_packed_bin", ptr(means2d), ptr(radii), ptr(depths), (C.c_int64 * (Cn + 1))(*indptr), Cn, width, height,
-             ptr(offsets), ptr(counts), (C.c_int64 * Cn)(*Ms), ptr(keys), ptr(flat), ptr(ids), (C.c_int32 * Cn)(*nmax),
-             stream())
+        if tile_size != TILE:
+            offsets, flat, ids, Ms = isect_tiles_and_sort_ts(means2d, radii, depths, indptr, counts, width, height,
+                                                             tile_size, rebase=True)
+            M = sum(Ms)
+        else:
+            offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
+            item_offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
+            total = torch.zeros(Cn, 4, dtype=torch.int32, device=dev)
+            call("eg_tile_offsets_cams", ptr(counts), T, Cn, 1 << 40, ptr(offsets), ptr(item_offsets), ptr(total), stream())
+            vals = total.reshape(-1).tolist()  # the second and last read-back of the call
+            Ms = [int(vals[4 * c]) for c in range(Cn)]
+            nmax = [int(vals[4 * c + 3]) for c in range(Cn)]
+            M = sum(Ms)
+            keys = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+            flat = torch.zeros(max(M, 1), dtype=torch.int32, device=dev)
+            ids = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
+            call("eg_packed_bin", ptr(means2d), ptr(radii), ptr(depths), (C.c_int64 * (Cn + 1))(*indptr), Cn, width, height,
+                 ptr(offsets), ptr(counts), (C.c_int64 * Cn)(*Ms), ptr(keys), ptr(flat), ptr(ids), (C.c_int32 * Cn)(*nmax),
+                 stream())
         bases = torch.tensor([sum(Ms[:c]) for c in range(Cn)], dtype=torch.int32, device=dev)
         binfo = {"isect_ids": ids[:M], "flatten_ids": flat[:M],
                  "isect_offsets": (offsets[:, :-1] + bases[:, None]).reshape(Cn, th, tw)}
@@ -937,7 +1070,11 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
         # plain RGB with 1 or 3 channels: the mode kernels' <CH, no depth, background> instantiation under a zero
         # background (T_final * 0 added to every channel), as `_mode_rasterization` runs RGB with real backgrounds
         backgrounds = torch.zeros(Cn, colors.shape[-1], device=dev)
-    if chunk is not None and colors is not None:
+    if tile_size != TILE:
+        render, alphas, last_ids = _TileCompositing.apply(
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            bool(absgrad), splat, depth, chunk, tile_size, Cn)
+    elif chunk is not None and colors is not None:
         render, alphas, last_ids = _WideCompositing.apply(
             means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
             bool(absgrad), splat, depth, chunk, Cn)
@@ -952,7 +1089,7 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
         "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
         "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
         **binfo,
-        "width": width, "height": height, "tile_size": TILE, "n_cameras": Cn,
+        "width": width, "height": height, "tile_size": tile_size, "n_cameras": Cn,
         "last_ids": last_ids,
     }
     return render, alphas, info
@@ -966,9 +1103,19 @@ def rasterization(
     backgrounds: Optional[Tensor] = None, render_mode: str = "RGB", sparse_grad: bool = False,
     absgrad: bool = False, rasterize_mode: str = "classic", channel_chunk: int = 32,
 ) -> Tuple[Tensor, Tensor, Dict]:
-    """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``, for tile_size=16 and colours of
-    any channel count D >= 1 (the reference's call, edge_gs.py:250-268, is packed=False, render_mode='RGB' with three
-    channels, without backgrounds and without sh_degree).
+    """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``, for tile_size 8, 16 or 32 and
+    colours of any channel count D >= 1 (the reference's call, edge_gs.py:250-268, is packed=False, render_mode='RGB'
+    with three channels, tile_size=16, without backgrounds and without sh_degree).
+
+    ``tile_size``: 8, 16 or 32 (NotImplementedError otherwise), with gsplat's meaning: ``info["tile_width"]`` /
+    ``["tile_height"]`` are ``ceil(width / tile_size)`` / ``ceil(height / tile_size)``, a Gaussian's tile box is
+    ``floor / ceil((x -+ r) / tile_size)``, a pixel walks the depth-sorted list of the tile that contains it, and
+    ``tiles_per_gauss``, ``isect_ids``, ``flatten_ids``, ``isect_offsets`` and ``last_ids`` refer to those tiles.  16
+    takes the paths described below.  8 and 32 take the general path with counting, key emission and compositing kernels
+    of their own (csrc/tiles.hip) -- every ``packed`` / ``sparse_grad`` / ``render_mode`` / ``backgrounds`` /
+    ``sh_degree`` / ``rasterize_mode`` / ``absgrad`` / cull / pose-gradient combination described below, never the
+    unit-colour fast path -- and composite every channel count, D = 1 and 3 included, in ``ceil(D / chunk)`` launches per
+    direction (the depth-only modes: one).
 
     ``packed`` (default True, as in gsplat): the projection keeps only the pairs (camera c, Gaussian n) that survive
     every cull -- exactly the set ``radii[c, n] > 0`` of the packed=False call -- in ascending order of ``c * N + n``
@@ -1019,6 +1166,9 @@ def rasterization(
     is added under the final transmittance of the colour channels (the depth channel's background is 0; the depth-only
     modes ignore it) and receives a gradient when it requires one.  The depth channel's gradient reaches ``means``,
     ``quats`` and ``scales`` through ``info["depths"]``."""
+    if isinstance(tile_size, bool) or tile_size not in TILE_SIZES:
+        raise NotImplementedError(f"tile_size must be 8, 16 or 32, got {tile_size!r} (the reference passes 16, edge_gs.py:232)")
+    tile_size = int(tile_size)
     N = means.shape[0]
     Cn = viewmats.shape[0]
     _check(means, (N, 3), "means")
@@ -1033,8 +1183,6 @@ def rasterization(
         _sh.check_view_coeffs(colors, sh_degree, Cn, N)
     if sparse_grad and not packed:
         raise ValueError("sparse_grad=True requires packed=True")
-    if tile_size != TILE:
-        raise NotImplementedError("tile_size must be 16 (edge_gs.py:232)")
     if rasterize_mode not in ("classic", "antialiased"):
         raise ValueError(f"Unknown rasterize_mode: {rasterize_mode}")
     if sh_degree is not None:
@@ -1056,7 +1204,12 @@ def rasterization(
         wide = D not in (1, 3) and render_mode not in ("D", "ED") and sh_degree is None
         return _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                      far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
-                                     sh_degree, min(channel_chunk, 32) if wide else None, sparse_grad)
+                                     sh_degree, min(channel_chunk, 32) if (wide or tile_size != TILE) else None,
+                                     sparse_grad, tile_size)
+    if tile_size != TILE:  # (every channel count and mode: one kernel family, csrc/tiles.hip; never the fast path)
+        return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
+                                   far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
+                                   sh_degree, min(channel_chunk, 32), tile_size)
     if D not in (1, 3) and render_mode not in ("D", "ED"):  # (the depth-only modes do not read the colours)
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                    far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,

@@ -5,7 +5,7 @@ The reference imports ``rasterization`` alone; ``spherical_harmonics`` is there 
 ``rasterization(..., sh_degree=L)`` calls it serves as well.  ``rasterization`` takes gsplat's defaults, ``packed=True``
 included (only the visible (camera, Gaussian) pairs are kept; ``info["camera_ids"]`` / ``info["gaussian_ids"]`` name
 them), and ``sparse_grad=True`` on top of it; ``viewmats`` that require grad receive their ``[C, 4, 4]`` gradient (pose
-optimisation); ``tile_size`` other than 16 is the one argument it refuses."""
+optimisation); ``tile_size`` may be 8, 16 or 32 (16 is the reference's)."""
 from edgegaussians_amd.rasterizer import rasterization  # noqa: F401
 from edgegaussians_amd.sh import spherical_harmonics  # noqa: F401
 

@@ -738,6 +738,53 @@ int eg_packed_bwd_sparse(const float *means, const float *quats, const float *sc
                          float *v_means /*[nnz,3]*/, float *v_quats /*[nnz,4]*/, float *v_scales /*[nnz,3]*/,
                          eg_stream_t stream);
 
+/* ---- tile sizes 8 and 32 (rasterization(tile_size=8 | 32)), csrc/tiles.hip.  Every entry above works on 16 x 16 pixel
+ * tiles (EG_TILE); these take the tile size as an argument, with gsplat's meaning: tile_width = ceil(width / tile_size),
+ * tile_height = ceil(height / tile_size), T their product, a Gaussian's tile box floor / ceil((x -+ r) / tile_size) in
+ * fp32, a pixel walks the list of the tile_size x tile_size tile that contains it.  eg_tile_offsets_cams and
+ * eg_sort_pairs depend on the tile size through T only and serve these entries as they are.  A tile size other than
+ * the ones named, or bad sizes, return EG_ERR_ARG before anything is launched.
+ * eg_tile_count_ts / eg_tile_emit_sort_ts (tile_size 8 or 32): eg_tile_count and eg_tile_emit + eg_sort_pairs for C
+ *   cameras in one native call.  ranges_host [C + 1] (HOST, ascending): camera c owns entries [ranges_host[c],
+ *   ranges_host[c + 1]) of means2d / radii / depths / tiles_per_gauss -- {0, N, 2 N, ...} for the dense [C, N, ...]
+ *   arrays of eg_project_fwd_cams (called with tiles_per_gauss and tile_counts NULL: its fused counting is 16-pixel),
+ *   indptr for the packed lists of eg_packed_write.  tile_counts [C, T]: zeroed by the caller, accumulated by the count,
+ *   returned to zero by the emission.  offsets [C, T + 1] from eg_tile_offsets_cams; M_host [C] and max_tile_host [C]
+ *   (or NULL) are HOST arrays; keys / flatten_ids / isect_ids (NULL ok) hold sum(M_host) entries, camera c's from
+ *   sum(M_host[:c]).  flatten_ids index inside the camera's range (rebase == 0) or the whole list (rebase != 0:
+ *   ranges_host[c] added, as eg_packed_bin leaves them); isect_ids carry the camera above the tile bits
+ *   (camera << (32 + floor(log2(T)) + 1)).
+ * eg_composite_fwd_ts_cams / eg_composite_bwd_ts_cams (tile_size 8 or 32): eg_composite_{fwd,bwd}_wide_cams with the
+ *   tile size behind `height` -- one chunk of `channels` <= 32 channels, n_real of them real, addressed by color_stride /
+ *   pixel_stride inside full-width tensors, N the record stride (EG_PACKED_STRIDE for packed records), offsets
+ *   [C, T + 1] and the cameras' lists one after the other in flatten_ids -- plus the DEPTH-ONLY form channels == 0,
+ *   which needs depth != 0 and n_real == 0, stages no colours and ignores colors / backgrounds / v_colors (NULL ok);
+ *   render / v_render then hold the depth in channel 0.  The same walk, hence the same alphas and last_ids for every
+ *   chunking; the backward accumulates with one atomic instruction per (wave, Gaussian). */
+int eg_tile_count_ts(const float *means2d /*[*,2]*/, const int32_t *radii, const int64_t *ranges_host /*[C+1]*/,
+                     int32_t C, int32_t width, int32_t height, int32_t tile_size,
+                     int32_t *tiles_per_gauss /*NULL ok*/, int32_t *tile_counts /*[C,T]*/, eg_stream_t stream);
+int eg_tile_emit_sort_ts(const float *means2d /*[*,2]*/, const int32_t *radii, const float *depths,
+                         const int64_t *ranges_host /*[C+1]*/, int32_t C, int32_t width, int32_t height,
+                         int32_t tile_size, const int32_t *offsets /*[C,T+1]*/,
+                         int32_t *tile_counts /*[C,T], returned to zero*/, const int64_t *M_host /*[C]*/, uint64_t *keys,
+                         int32_t *flatten_ids, int64_t *isect_ids /*NULL ok*/,
+                         const int32_t *max_tile_host /*[C] or NULL*/, int32_t rebase, eg_stream_t stream);
+int eg_composite_fwd_ts_cams(int32_t C, const float *splat /*[C,N,8]*/, int32_t N, const float *colors /*NULL: channels == 0*/,
+                             int32_t colors_per_camera, int32_t channels, int32_t depth,
+                             const float *backgrounds /*or NULL*/, const int32_t *offsets /*[C,T+1]*/,
+                             const int32_t *flatten_ids, int32_t width, int32_t height, int32_t tile_size, float *render,
+                             float *alphas /*or NULL*/, int32_t *last_ids /*or NULL*/, int32_t n_real,
+                             int32_t color_stride, int32_t pixel_stride, eg_stream_t stream);
+int eg_composite_bwd_ts_cams(int32_t C, const float *splat /*[C,N,8]*/, int32_t N, const float *colors /*NULL: channels == 0*/,
+                             int32_t colors_per_camera, int32_t channels, int32_t depth,
+                             const float *backgrounds /*or NULL*/, const int32_t *offsets /*[C,T+1]*/,
+                             const int32_t *flatten_ids, int32_t width, int32_t height, int32_t tile_size,
+                             const float *alphas, const int32_t *last_ids, const float *v_render,
+                             const float *v_alphas /*or NULL*/, float *g2d /*[C,N,8]*/, float *v_colors /*or NULL*/,
+                             float *v_depths /*[C,N], with depth*/, int32_t n_real, int32_t color_stride,
+                             int32_t pixel_stride, eg_stream_t stream);
+
 /* ---- camera-pose gradient of the projection (gsplat's v_viewmats), csrc/viewmat_grad.hip: for every visible pair
  * (c, n), with v_t the cotangent of its camera-space mean (the v_depths term included), vW the cotangent of
  * W = R_c Rq diag(s) and M = Rq diag(s):  v_R[c][i][j] += v_t[i] mean[j] + sum_k vW[3i+k] M[j][k],  v_tr[c][i] += v_t[i];
