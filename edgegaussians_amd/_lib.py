@@ -159,6 +159,11 @@ _SIGS = {
                                 _vp, _vp],
     "eg_sh_fwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp],
     "eg_sh_bwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "eg_quat_scale_to_covar_preci_fwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "eg_quat_scale_to_covar_preci_bwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "eg_project_covars_fwd_cams": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _f, _f, _f] + [_vp] * 5 + [_vp],
+    "eg_project_covars_bwd_cams": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f] + [_vp] * 7 + [_vp],
+    "eg_isect_offset_encode": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "eg_train_step_batched": [C.POINTER(StepArgs), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp],
 }
 EXPORTS = sorted(list(_SIGS) + ["eg_last_error_string", "eg_version", "eg_device_count",

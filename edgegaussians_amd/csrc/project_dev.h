@@ -142,6 +142,74 @@ __device__ __forceinline__ bool forward_geom(const Cam &cam, const float *__rest
                       flags, f);
 }
 
+// Projection from a covariance (gsplat `fully_fused_projection(covars=[N,6])`, csrc/functional.hip): the world
+// covariance arrives as its upper triangle cv = (00, 01, 02, 11, 12, 22) instead of quats + scales.  Fills the fields
+// of `f` that radius_of and the reverse sweep of functional.hip read (camera-space mean, clamp, J, cov2d, conic,
+// compensation, mean2d; the quaternion / scale / W / p0 / p1 fields stay untouched), the camera-space covariance
+// cc (same six entries) and Q = J cc (rows q0, q1).  Same culls, clamp and rounding discipline as forward_geom.
+__device__ __forceinline__ bool forward_geom_covar(const Cam &cam, const float *__restrict__ m,
+                                                   const float *__restrict__ cv, int width, int height,
+                                                   float near_plane, float far_plane, float eps2d, Fwd &f,
+                                                   float (&cc)[6], float (&q0)[3], float (&q1)[3]) {
+#pragma clang fp contract(off)  // (one rounding sequence in every kernel: see forward_geom)
+  const float mx = m[0], my = m[1], mz = m[2];
+  f.x = cam.R[0] * mx + cam.R[1] * my + cam.R[2] * mz + cam.t[0];
+  f.y = cam.R[3] * mx + cam.R[4] * my + cam.R[5] * mz + cam.t[1];
+  f.z = cam.R[6] * mx + cam.R[7] * my + cam.R[8] * mz + cam.t[2];
+  if (f.z < near_plane || f.z > far_plane) return false;
+
+  // cc = Rv S Rv^T, S symmetric: A = Rv S, then the upper triangle of A Rv^T
+  const float S[9] = {cv[0], cv[1], cv[2], cv[1], cv[3], cv[4], cv[2], cv[4], cv[5]};
+  float A[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      A[3 * i + k] = cam.R[3 * i] * S[k] + cam.R[3 * i + 1] * S[3 + k] + cam.R[3 * i + 2] * S[6 + k];
+  constexpr int ui[6] = {0, 0, 0, 1, 1, 2}, uj[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+  for (int e = 0; e < 6; ++e)
+    cc[e] = A[3 * ui[e]] * cam.R[3 * uj[e]] + A[3 * ui[e] + 1] * cam.R[3 * uj[e] + 1] + A[3 * ui[e] + 2] * cam.R[3 * uj[e] + 2];
+
+  const float lim_x = kFovClamp * (0.5f * (float)width / cam.fx);
+  const float lim_y = kFovClamp * (0.5f * (float)height / cam.fy);
+  f.rz = 1.f / f.z;
+  f.rz2 = f.rz * f.rz;
+  const float xr = f.x * f.rz, yr = f.y * f.rz;
+  f.in_x = (xr <= lim_x) && (xr >= -lim_x);
+  f.in_y = (yr <= lim_y) && (yr >= -lim_y);
+  f.tx = f.z * fminf(lim_x, fmaxf(-lim_x, xr));
+  f.ty = f.z * fminf(lim_y, fmaxf(-lim_y, yr));
+  f.J00 = cam.fx * f.rz;
+  f.J11 = cam.fy * f.rz;
+  f.J02 = -cam.fx * f.tx * f.rz2;
+  f.J12 = -cam.fy * f.ty * f.rz2;
+  // Q = J cc, cov2d = Q J^T
+  q0[0] = f.J00 * cc[0] + f.J02 * cc[2];
+  q0[1] = f.J00 * cc[1] + f.J02 * cc[4];
+  q0[2] = f.J00 * cc[2] + f.J02 * cc[5];
+  q1[0] = f.J11 * cc[1] + f.J12 * cc[2];
+  q1[1] = f.J11 * cc[3] + f.J12 * cc[4];
+  q1[2] = f.J11 * cc[4] + f.J12 * cc[5];
+  f.c00 = q0[0] * f.J00 + q0[2] * f.J02;
+  f.c01 = q0[1] * f.J11 + q0[2] * f.J12;
+  f.c11 = q1[1] * f.J11 + q1[2] * f.J12;
+  f.u = cam.fx * f.x * f.rz + cam.cx;
+  f.v = cam.fy * f.y * f.rz + cam.cy;
+
+  f.det0 = f.c00 * f.c11 - f.c01 * f.c01;
+  f.b00 = f.c00 + eps2d;
+  f.b11 = f.c11 + eps2d;
+  f.det1 = f.b00 * f.b11 - f.c01 * f.c01;
+  if (f.det1 <= 0.f) return false;
+  f.comp = sqrtf(fmaxf(0.f, f.det0 / f.det1));
+  const float inv = 1.f / f.det1;
+  f.a = f.b11 * inv;
+  f.b = -f.c01 * inv;
+  f.c = f.b00 * inv;
+  return true;
+}
+
 __device__ __forceinline__ int radius_of(const Fwd &f, int width, int height, float radius_clip) {
 #pragma clang fp contract(off)
   const float bh = 0.5f * (f.b00 + f.b11);

@@ -1,0 +1,335 @@
+"""gsplat 1.0.0's stage-by-stage API over the kernels `rasterization` runs: ``fully_fused_projection``,
+``quat_scale_to_covar_preci``, ``isect_tiles``, ``isect_offset_encode``, ``rasterize_to_pixels``, ``world_to_cam`` and
+``persp_proj``, with gsplat's signatures and return orders.
+
+Callers use the stages when they change something between them -- shift ``means2d``, substitute their own conics or
+opacities, render Gaussians that exist only as covariances, re-bin with another tile grid.  The projection from
+``quats`` + ``scales``, the binning and the compositing are the very kernels behind ``rasterization(packed=False)``;
+the projection from ``covars``, ``quat_scale_to_covar_preci`` and ``isect_offset_encode`` have kernels of their own
+(csrc/functional.hip).  ``world_to_cam`` and ``persp_proj`` are plain differentiable torch expressions (not a hot path;
+they work on CPU tensors too).  Everything else needs device tensors: there is no CPU path.
+
+Not supported, each a NotImplementedError: ``packed=True`` (use ``rasterization(packed=True)``), ``sparse_grad=True``,
+``sort=False``, ``masks``, and a ``viewmats`` that requires grad together with ``covars``."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import rasterizer as _R
+from ._lib import call, ptr, stream
+from .rasterizer import TILE, TILE_SIZES, _check
+
+__all__ = ["fully_fused_projection", "quat_scale_to_covar_preci", "isect_tiles", "isect_offset_encode",
+           "rasterize_to_pixels", "world_to_cam", "persp_proj"]
+
+
+def _no_packed(packed, what):
+    if packed:
+        raise NotImplementedError(f"{what}: packed=True is not available in the functional stages; use rasterization(packed=True)")
+
+
+def _tile_size(tile_size):
+    if isinstance(tile_size, bool) or tile_size not in TILE_SIZES:
+        raise NotImplementedError(f"tile_size must be 8, 16 or 32, got {tile_size!r}")
+    return int(tile_size)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+class _QuatScaleToCovarPreci(torch.autograd.Function):
+    """eg_quat_scale_to_covar_preci_fwd / _bwd: one lane per Gaussian."""
+
+    @staticmethod
+    def forward(ctx, quats, scales, compute_covar, compute_preci, triu):
+        N, dev = quats.shape[0], quats.device
+        q, s = quats.contiguous(), scales.contiguous()
+        shape = (N, 6) if triu else (N, 3, 3)
+        covars = torch.empty(shape, device=dev) if compute_covar else None
+        precis = torch.empty(shape, device=dev) if compute_preci else None
+        call("eg_quat_scale_to_covar_preci_fwd", ptr(q), ptr(s), N, int(triu), ptr(covars), ptr(precis), stream())
+        ctx.save_for_backward(q, s)
+        ctx.cfg = (bool(triu), compute_covar, compute_preci)
+        # (an output that is not computed is a placeholder autograd never differentiates; the wrapper returns None)
+        empty = torch.empty(0, device=dev)
+        if not compute_covar or not compute_preci:
+            ctx.mark_non_differentiable(empty)
+        return (covars if compute_covar else empty), (precis if compute_preci else empty)
+
+    @staticmethod
+    def backward(ctx, v_covars, v_precis):
+        q, s = ctx.saved_tensors
+        triu, compute_covar, compute_preci = ctx.cfg
+        N, dev = q.shape[0], q.device
+        vc = v_covars.contiguous() if (compute_covar and v_covars is not None) else None
+        vp = v_precis.contiguous() if (compute_preci and v_precis is not None) else None
+        v_quats = torch.empty(N, 4, device=dev)
+        v_scales = torch.empty(N, 3, device=dev)
+        call("eg_quat_scale_to_covar_preci_bwd", ptr(q), ptr(s), N, int(triu), ptr(vc), ptr(vp), ptr(v_quats), ptr(v_scales),
+             stream())
+        return v_quats, v_scales, None, None, None
+
+
+def quat_scale_to_covar_preci(quats: Tensor, scales: Tensor, compute_covar: bool = True, compute_preci: bool = True,
+                              triu: bool = False) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """gsplat ``quat_scale_to_covar_preci``: ``covars = R diag(s^2) R^T`` and ``precis = R diag(1 / s^2) R^T`` from
+    ``quats`` [N,4] (w, x, y, z; normalised inside) and ``scales`` [N,3]; ``[N,3,3]``, or with ``triu`` the upper
+    triangle ``[N,6]`` = (00, 01, 02, 11, 12, 22).  An output that is not computed is ``None``."""
+    N = quats.shape[0]
+    _check(quats, (N, 4), "quats")
+    _check(scales, (N, 3), "scales")
+    if not compute_covar and not compute_preci:
+        return None, None
+    covars, precis = _QuatScaleToCovarPreci.apply(quats, scales, bool(compute_covar), bool(compute_preci), bool(triu))
+    return (covars if compute_covar else None), (precis if compute_preci else None)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+class _CovarProjection(torch.autograd.Function):
+    """gsplat ``fully_fused_projection`` from covariances (packed=False) for C cameras: eg_project_covars_fwd_cams /
+    eg_project_covars_bwd_cams.  The backward sums over the cameras in camera order without atomics."""
+
+    @staticmethod
+    def forward(ctx, means, covars, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip, calc_comp):
+        Cn, N = viewmats.shape[0], means.shape[0]
+        dev = means.device
+        m, cv, vm, Kc = means.contiguous(), covars.contiguous(), viewmats.contiguous(), Ks.contiguous()
+        radii = torch.empty(Cn, N, dtype=torch.int32, device=dev)
+        means2d = torch.empty(Cn, N, 2, device=dev)
+        depths = torch.empty(Cn, N, device=dev)
+        conics = torch.empty(Cn, N, 3, device=dev)
+        comps = torch.empty(Cn, N, device=dev) if calc_comp else torch.empty(0, device=dev)
+        call("eg_project_covars_fwd_cams", ptr(m), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane, far_plane,
+             eps2d, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps) if calc_comp else None,
+             stream())
+        ctx.save_for_backward(m, cv, vm, Kc, radii)
+        ctx.cfg = (width, height, eps2d, calc_comp)
+        ctx.mark_non_differentiable(*((radii,) if calc_comp else (radii, comps)))
+        return radii, means2d, depths, conics, comps
+
+    @staticmethod
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps):
+        m, cv, vm, Kc, radii = ctx.saved_tensors
+        width, height, eps2d, calc_comp = ctx.cfg
+        Cn, N = vm.shape[0], m.shape[0]
+        dev = m.device
+        vm2d = v_means2d.contiguous() if v_means2d is not None else torch.zeros(Cn, N, 2, device=dev)
+        vcon = v_conics.contiguous() if v_conics is not None else torch.zeros(Cn, N, 3, device=dev)
+        vdep = v_depths.contiguous() if v_depths is not None else None
+        vcomp = v_comps.contiguous() if (calc_comp and v_comps is not None) else None
+        v_means = torch.empty(N, 3, device=dev)
+        v_covars = torch.empty(N, 6, device=dev)
+        call("eg_project_covars_bwd_cams", ptr(m), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, ptr(radii),
+             ptr(vm2d), ptr(vdep), ptr(vcon), ptr(vcomp), ptr(v_means), ptr(v_covars), stream())
+        return (v_means, v_covars) + (None,) * 9
+
+
+def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Optional[Tensor], scales: Optional[Tensor],
+                           viewmats: Tensor, Ks: Tensor, width: int, height: int, eps2d: float = 0.3,
+                           near_plane: float = 0.01, far_plane: float = 1e10, radius_clip: float = 0.0,
+                           packed: bool = False, sparse_grad: bool = False, calc_compensations: bool = False):
+    """gsplat ``fully_fused_projection`` (packed=False): ``(radii [C,N] int32, means2d [C,N,2], depths [C,N], conics
+    [C,N,3], compensations [C,N] | None)``; a culled pair has radius 0 and zeros in every float output.
+
+    Exactly one of ``covars`` [N,6] (upper triangle) and ``quats`` [N,4] + ``scales`` [N,3] must be given (ValueError).
+    With ``quats`` + ``scales`` this is the projection node of ``rasterization`` -- the same kernels, the same bits, and
+    ``viewmats`` receives its gradient when it requires one.  With ``covars`` a kernel pair of its own; ``viewmats``
+    must not require grad there (NotImplementedError)."""
+    _no_packed(packed, "fully_fused_projection")
+    if sparse_grad:
+        raise NotImplementedError("fully_fused_projection: sparse_grad=True needs packed=True; use rasterization(packed=True, sparse_grad=True)")
+    have_qs = quats is not None or scales is not None
+    if (covars is None) == (not have_qs) or (have_qs and (quats is None or scales is None)):
+        raise ValueError("fully_fused_projection: give either covars, or quats and scales (exactly one of the two forms)")
+    N, Cn = means.shape[0], viewmats.shape[0]
+    _check(means, (N, 3), "means")
+    _check(viewmats, (Cn, 4, 4), "viewmats")
+    _check(Ks, (Cn, 3, 3), "Ks")
+    width, height = int(width), int(height)
+    cfg = (float(eps2d), float(near_plane), float(far_plane), float(radius_clip))
+    if covars is None:
+        _check(quats, (N, 4), "quats")
+        _check(scales, (N, 3), "scales")
+        dummy = torch.ones(N, device=means.device)  # (the record's opacity: nobody reads the record here)
+        radii, means2d, depths, conics, comps = _R._Projection.apply(
+            means, quats, scales, dummy, viewmats, Ks, width, height, *cfg, bool(calc_compensations))[:5]
+        return radii, means2d, depths, conics, (comps if calc_compensations else None)
+    _check(covars, (N, 6), "covars")
+    if viewmats.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("fully_fused_projection: the gradient of viewmats is not available with covars; pass quats and scales")
+    radii, means2d, depths, conics, comps = _CovarProjection.apply(
+        means, covars, viewmats, Ks, width, height, *cfg, bool(calc_compensations))
+    return radii, means2d, depths, conics, (comps if calc_compensations else None)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def isect_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, tile_width: int, tile_height: int,
+                sort: bool = True, packed: bool = False, n_cameras: Optional[int] = None,
+                camera_ids: Optional[Tensor] = None, gaussian_ids: Optional[Tensor] = None):
+    """gsplat ``isect_tiles`` (packed=False, sort=True): ``(tiles_per_gauss [C,N] int32, isect_ids [M] int64,
+    flatten_ids [M] int32)`` for ``means2d`` [C,N,2], ``radii`` [C,N] int32 and ``depths`` [C,N] on a grid of
+    ``tile_width`` x ``tile_height`` tiles of ``tile_size`` (8, 16 or 32) pixels.  ``isect_ids`` = camera << (32 +
+    tile_bits) | tile << 32 | depth bits, sorted; ``flatten_ids`` = c * N + n.  One host read-back (the M_c)."""
+    _no_packed(packed, "isect_tiles")
+    if not sort:
+        raise NotImplementedError("isect_tiles: sort=False is not available (the emission and the sort are one native call)")
+    tile_size = _tile_size(tile_size)
+    if means2d.dim() != 3:
+        raise ValueError(f"means2d must have shape (C, N, 2), got {tuple(means2d.shape)}")
+    Cn, N = means2d.shape[0], means2d.shape[1]
+    _check(means2d, (Cn, N, 2), "means2d")
+    _check(radii, (Cn, N), "radii", torch.int32)
+    _check(depths, (Cn, N), "depths")
+    tw, th = int(tile_width), int(tile_height)
+    if tw < 1 or th < 1:
+        raise ValueError(f"tile_width and tile_height must be positive, got {tile_width!r}, {tile_height!r}")
+    if n_cameras is not None and int(n_cameras) != Cn:
+        raise ValueError(f"n_cameras is {n_cameras}, means2d holds {Cn} cameras")
+    dev = means2d.device
+    width, height = tw * tile_size, th * tile_size
+    T = tw * th
+    m2, rd, dp = means2d.detach().contiguous(), radii.contiguous(), depths.detach().contiguous()
+    tpg = torch.zeros(Cn, N, dtype=torch.int32, device=dev)
+    empty = (tpg, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev))
+    if N == 0:
+        return empty
+    counts = torch.zeros(Cn, T, dtype=torch.int32, device=dev)
+    tile_bits = int(math.floor(math.log2(T))) + 1
+    if tile_size != TILE:
+        ranges = [c * N for c in range(Cn + 1)]
+        call("eg_tile_count_ts", ptr(m2), ptr(rd), (C.c_int64 * (Cn + 1))(*ranges), Cn, width, height, tile_size, ptr(tpg),
+             ptr(counts), stream())
+        _offsets, flat, ids, Ms = _R.isect_tiles_and_sort_ts(m2, rd, dp, ranges, counts, width, height, tile_size, rebase=True)
+        M = sum(Ms)
+        return tpg, ids[:M], flat[:M]
+    for c in range(Cn):
+        call("eg_tile_count", ptr(m2[c]), ptr(rd[c]), N, width, height, ptr(tpg[c]), ptr(counts[c]), stream())
+    _o, f_l, i_l, Ms = _R.isect_tiles_and_sort_cams(m2, rd, dp, counts, width, height)[:4]
+    if sum(Ms) == 0:
+        return empty
+    return (tpg, torch.cat([i_l[c] | (c << (32 + tile_bits)) for c in range(Cn)]),
+            torch.cat([f_l[c] + c * N for c in range(Cn)]))
+
+
+@torch.no_grad()
+def isect_offset_encode(isect_ids: Tensor, n_cameras: int, tile_width: int, tile_height: int) -> Tensor:
+    """gsplat ``isect_offset_encode``: ``offsets [C, tile_height, tile_width]`` int32 from SORTED ``isect_ids`` [M]
+    int64, ``offsets[c, i, j]`` = the number of entries whose (camera, tile) is below (c, i * tile_width + j).  No host
+    read-back (eg_isect_offset_encode)."""
+    if isect_ids.dim() != 1:
+        raise ValueError(f"isect_ids must have shape (M,), got {tuple(isect_ids.shape)}")
+    M = isect_ids.shape[0]
+    _check(isect_ids, (M,), "isect_ids", torch.int64)
+    Cn, tw, th = int(n_cameras), int(tile_width), int(tile_height)
+    if Cn < 1 or tw < 1 or th < 1:
+        raise ValueError(f"n_cameras, tile_width and tile_height must be positive, got {n_cameras!r}, {tile_width!r}, {tile_height!r}")
+    offsets = torch.empty(Cn, th, tw, dtype=torch.int32, device=isect_ids.device)
+    ids = isect_ids.contiguous()
+    call("eg_isect_offset_encode", ptr(ids) if M > 0 else None, M, Cn, tw, th, ptr(offsets), stream())
+    return offsets
+
+
+# ----------------------------------------------------------------------------------------------------------------
+def rasterize_to_pixels(means2d: Tensor, conics: Tensor, colors: Tensor, opacities: Tensor, image_width: int,
+                        image_height: int, tile_size: int, isect_offsets: Tensor, flatten_ids: Tensor,
+                        backgrounds: Optional[Tensor] = None, masks: Optional[Tensor] = None, packed: bool = False,
+                        absgrad: bool = False) -> Tuple[Tensor, Tensor]:
+    """gsplat ``rasterize_to_pixels`` (packed=False): ``(render_colors [C,H,W,D], render_alphas [C,H,W,1])`` from
+    ``means2d`` [C,N,2], ``conics`` [C,N,3], ``colors`` [C,N,D] (any D >= 1), ``opacities`` [C,N], ``isect_offsets``
+    [C,th,tw] int32 and ``flatten_ids`` [M] int32 (c * N + n) as ``isect_tiles`` / ``isect_offset_encode`` return them.
+
+    The record the compositing kernels read is built here from the caller's tensors (they may have changed since the
+    projection), the global offsets become the kernels' per-camera form in torch (no host read-back), and the
+    compositing is the kernel family ``rasterization`` takes for this (tile_size, D).  ``means2d`` receives
+    ``.absgrad`` [C,N,2] in the backward with ``absgrad=True``."""
+    _no_packed(packed, "rasterize_to_pixels")
+    if masks is not None:
+        raise NotImplementedError("rasterize_to_pixels: masks are not available")
+    tile_size = _tile_size(tile_size)
+    if means2d.dim() != 3:
+        raise ValueError(f"means2d must have shape (C, N, 2), got {tuple(means2d.shape)}")
+    Cn, N = means2d.shape[0], means2d.shape[1]
+    width, height = int(image_width), int(image_height)
+    tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
+    T = tw * th
+    _check(means2d, (Cn, N, 2), "means2d")
+    _check(conics, (Cn, N, 3), "conics")
+    _check(opacities, (Cn, N), "opacities")
+    if colors.dim() != 3 or colors.shape[-1] < 1:
+        raise ValueError(f"colors must have shape (C, N, D) with D >= 1, got {tuple(colors.shape)}")
+    D = colors.shape[-1]
+    _check(colors, (Cn, N, D), "colors")
+    if backgrounds is not None:
+        _check(backgrounds, (Cn, D), "backgrounds")
+    _check(isect_offsets, (Cn, th, tw), "isect_offsets", torch.int32)
+    if flatten_ids.dim() != 1:
+        raise ValueError(f"flatten_ids must have shape (M,), got {tuple(flatten_ids.shape)}")
+    M = flatten_ids.shape[0]
+    _check(flatten_ids, (M,), "flatten_ids", torch.int32)
+    dev = means2d.device
+    if N == 0:  # (nothing to composite: the backgrounds under a transmittance of one, on their graph)
+        alphas = torch.zeros(Cn, height, width, 1, device=dev)
+        render = (backgrounds[:, None, None, :].expand(Cn, height, width, D) if backgrounds is not None
+                  else torch.zeros(Cn, height, width, D, device=dev))
+        return render + colors.sum() * 0.0, alphas
+    with torch.no_grad():
+        # (x y a b c opacity | depth radius): the last two are read by kernels this path never runs
+        splat = torch.cat([means2d, conics, opacities[..., None], torch.zeros(Cn, N, 2, device=dev)], dim=-1).contiguous()
+        first = isect_offsets.reshape(Cn, T)
+        ends = torch.cat([first[1:, 0], torch.full((1,), M, dtype=torch.int32, device=dev)])
+        flat = (flatten_ids % N) if M > 0 else torch.zeros(1, dtype=torch.int32, device=dev)
+        # the cameras' lists one after the other, every row of offsets local to its camera's list
+        # (clamped into the list: offsets outside it must not send a kernel outside `flatten_ids`)
+        local = torch.cat([first - first[:, :1], (ends - first[:, 0])[:, None]], dim=1).clamp_(0, M).contiguous()
+    opac = opacities.contiguous()
+    if tile_size != TILE:
+        render, alphas, _ = _R._TileCompositing.apply(means2d, conics, colors, opac, None, backgrounds, width, height, local,
+                                                      flat, bool(absgrad), splat, False, 32, tile_size)
+    elif D not in (1, 3):
+        render, alphas, _ = _R._WideCompositing.apply(means2d, conics, colors, opac, None, backgrounds, width, height, local,
+                                                      flat, bool(absgrad), splat, False, 32)
+    elif backgrounds is not None:
+        render, alphas, _ = _R._ModeCompositing.apply(means2d, conics, colors, opac, None, backgrounds, width, height, local,
+                                                      flat, bool(absgrad), splat, False)
+    else:
+        # the per-camera entry takes one list per camera: the whole list with the GLOBAL offsets of that camera's tiles
+        with torch.no_grad():
+            glob = torch.cat([first, ends[:, None]], dim=1).clamp_(0, M).contiguous()
+        render, alphas, _ = _R._Compositing.apply(means2d, conics, colors, opac, width, height,
+                                                  tuple(glob[c] for c in range(Cn)), (flat,) * Cn, bool(absgrad), False,
+                                                  (None,) * Cn, (None,) * Cn, (0,) * Cn, splat)
+    return render, alphas
+
+
+# ----------------------------------------------------------------------------------------------------------------
+def world_to_cam(means: Tensor, covars: Tensor, viewmats: Tensor) -> Tuple[Tensor, Tensor]:
+    """gsplat ``world_to_cam``: ``means`` [N,3], ``covars`` [N,3,3], ``viewmats`` [C,4,4] -> ``(means_c [C,N,3],
+    covars_c [C,N,3,3])``, ``means_c = R means + t``, ``covars_c = R covars R^T``.  Plain torch, any device."""
+    R = viewmats[:, :3, :3]
+    t = viewmats[:, :3, 3]
+    means_c = torch.einsum("cij,nj->cni", R, means) + t[:, None, :]
+    covars_c = torch.einsum("cij,njk,clk->cnil", R, covars, R)
+    return means_c, covars_c
+
+
+def persp_proj(means: Tensor, covars: Tensor, Ks: Tensor, width: int, height: int) -> Tuple[Tensor, Tensor]:
+    """gsplat ``persp_proj``: camera-space ``means`` [C,N,3] and ``covars`` [C,N,3,3], ``Ks`` [C,3,3] -> ``(means2d
+    [C,N,2], covars2d [C,N,2,2])`` with the 1.3 tan-fov clamp on the Jacobian's x / z and y / z (``means2d`` is not
+    clamped) and WITHOUT eps2d on the diagonal.  Plain torch, any device."""
+    tx, ty, tz = means.unbind(-1)
+    fx, fy = Ks[:, 0, 0, None], Ks[:, 1, 1, None]
+    cx, cy = Ks[:, 0, 2, None], Ks[:, 1, 2, None]
+    lim_x = 1.3 * (0.5 * width / fx)
+    lim_y = 1.3 * (0.5 * height / fy)
+    rz = 1.0 / tz
+    cxz = tz * torch.minimum(lim_x, torch.maximum(-lim_x, tx * rz))
+    cyz = tz * torch.minimum(lim_y, torch.maximum(-lim_y, ty * rz))
+    zero = torch.zeros_like(tz)
+    J = torch.stack([fx * rz, zero, -fx * cxz * rz * rz, zero, fy * rz, -fy * cyz * rz * rz], dim=-1).reshape(means.shape[:-1] + (2, 3))
+    covars2d = J @ covars @ J.transpose(-1, -2)
+    means2d = torch.stack([fx * tx * rz + cx, fy * ty * rz + cy], dim=-1)
+    return means2d, covars2d

@@ -909,6 +909,42 @@ int eg_train_steps_dp(const eg_step_args *a, const eg_adam_hyper *hyper, float *
                       const float *Ks /*[V,3,3]*/, const float *gts /*[V,H,W]*/, int32_t next_view_after,
                       eg_stream_t stream);
 
+/* ---- gsplat's functional API (csrc/functional.hip; edgegaussians_amd/functional.py).  Every entry is asynchronous on
+ * `stream`, rejects null pointers (other than the ones named) and bad sizes with EG_ERR_ARG before any device call, and
+ * uses no atomics: the same bits every run.  A [N,6] tensor holds the upper triangle (00, 01, 02, 11, 12, 22) of a
+ * symmetric matrix; in a GRADIENT of that shape an off-diagonal entry stands for both symmetric entries (what autograd
+ * gives through "build the matrix, select the upper triangle" / "place the six numbers into the symmetric matrix").
+ *
+ * eg_quat_scale_to_covar_preci_fwd: covars = R diag(s^2) R^T, precis = R diag(1 / s^2) R^T from quats [N,4] (w, x, y, z;
+ *   normalised inside with rsqrtf of the squared norm) and scales [N,3]; either output NULL = not computed; triu != 0:
+ *   [N,6], else [N,3,3].  _bwd: v_covars / v_precis in the same layout (either NULL) -> v_quats [N,4], v_scales [N,3],
+ *   every row written.  N == 0: nothing to do. */
+int eg_quat_scale_to_covar_preci_fwd(const float *quats, const float *scales, int32_t N, int32_t triu,
+                                     float *covars /*NULL ok*/, float *precis /*NULL ok*/, eg_stream_t stream);
+int eg_quat_scale_to_covar_preci_bwd(const float *quats, const float *scales, int32_t N, int32_t triu,
+                                     const float *v_covars /*NULL ok*/, const float *v_precis /*NULL ok*/,
+                                     float *v_quats, float *v_scales, eg_stream_t stream);
+/* gsplat fully_fused_projection(means, covars = [N,6], quats = None, scales = None, packed = False) for C cameras:
+ * cov2d = J Rv S Rv^T J^T, everything else as eg_project_fwd_cams (near / far cull, the 1.3 tan-fov clamp, + eps2d,
+ * det <= 0 cull, compensation, radius, radius_clip, off-screen cull).  radii int32 [C,N], means2d [C,N,2], depths
+ * [C,N], conics [C,N,3], compensations [C,N] or NULL; a culled pair has radius 0 and zeros in every float output.
+ * _bwd: v_means [N,3] and v_covars [N,6], the sum over the cameras with radii > 0 in camera order, every row written;
+ * v_depths and v_compensations (gsplat's 0.5 v / (comp + 1e-6)) may be NULL.  N == 0: nothing to do. */
+int eg_project_covars_fwd_cams(const float *means, const float *covars, const float *viewmats, const float *Ks,
+                               int32_t N, int32_t C, int32_t width, int32_t height, float near_plane, float far_plane,
+                               float eps2d, float radius_clip, int32_t *radii, float *means2d, float *depths,
+                               float *conics, float *compensations /*NULL ok*/, eg_stream_t stream);
+int eg_project_covars_bwd_cams(const float *means, const float *covars, const float *viewmats, const float *Ks,
+                               int32_t N, int32_t C, int32_t width, int32_t height, float eps2d, const int32_t *radii,
+                               const float *v_means2d, const float *v_depths /*NULL ok*/, const float *v_conics,
+                               const float *v_compensations /*NULL ok*/, float *v_means, float *v_covars,
+                               eg_stream_t stream);
+/* gsplat isect_offset_encode on a caller's SORTED isect ids [M] (camera << (32 + tile_bits) | tile << 32 | depth bits,
+ * tile_bits = floor(log2(T)) + 1, T = tile_width * tile_height): offsets [C, T] int32, offsets[c, t] = number of
+ * entries whose (camera, tile) is below (c, t).  M == 0 (isect_ids may be NULL): all zeros.  No host read-back. */
+int eg_isect_offset_encode(const int64_t *isect_ids, int64_t M, int32_t C, int32_t tile_width, int32_t tile_height,
+                           int32_t *offsets, eg_stream_t stream);
+
 /* ---- measurement aid: between eg_timing_begin(n) and eg_timing_end(), the next n eg_train_step
  * calls record HIP events between their stages on the launch stream; eg_timing_end synchronises
  * once and returns the average microseconds per stage (eg_timing_stage_count() entries, names by
