@@ -26,6 +26,7 @@ FLAG_LOGIT_OPACITIES = 2
 FLAG_ANTIALIASED = 4
 FLAG_TIGHT_TILES = 8
 FLAG_ABSGRAD_WRITE = 16
+FLAG_ORTHO = 128         # EG_FLAG_ORTHO: camera_model="ortho" (operator path only)
 FLAG_FRONT_PREFIX = 32   # EG_FLAG_FRONT_PREFIX (tile grids above PREFIX_HERE_MAX_TILES: `ticket` is [T + 2])
 PREFIX_HERE_MAX_TILES = 2560  # kPrefixHereMaxTiles (csrc/common.h)
 REWALK_SPECULATE = -2  # EG_REWALK_SPECULATE
@@ -163,6 +164,8 @@ _SIGS = {
     "eg_quat_scale_to_covar_preci_bwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "eg_project_covars_fwd_cams": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _f, _f, _f] + [_vp] * 5 + [_vp],
     "eg_project_covars_bwd_cams": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f] + [_vp] * 7 + [_vp],
+    "eg_project_covars_fwd_cams_flags": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _f, _f, _f] + [_vp] * 5 + [_u32, _vp],
+    "eg_project_covars_bwd_cams_flags": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f] + [_vp] * 7 + [_u32, _vp],
     "eg_isect_offset_encode": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "eg_train_step_batched": [C.POINTER(StepArgs), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp],
 }

@@ -5,6 +5,7 @@
 //   projection from covariances gsplat `fully_fused_projection(means, covars=[N,6], quats=None, scales=None)` for C
 //                               cameras (packed=False) with the VJP.  Forward: grid (ceil(N / 256), C), one lane per
 //                               pair, forward_geom_covar + radius_of (csrc/project_dev.h), zeros on a culled row.
+//                               The `_flags` entry pair takes the camera model (EG_FLAG_ORTHO), a template parameter.
 //                               Backward: one lane per Gaussian walks the cameras 0 .. C-1, recomputes the forward of the
 //                               pairs with radii > 0, sums in registers and writes every row once (eg_packed_bwd's and
 //                               eg_sh_bwd's scheme): no atomics, no zero-fill, the same bits every run.
@@ -170,6 +171,9 @@ qs2cp_bwd_kernel(const float *__restrict__ quats, const float *__restrict__ scal
 }
 
 // ---------------------------------------------------------------------------------------------
+// CM: the camera model (csrc/project_dev.h) of the two projection kernels: kPinhole behind eg_project_covars_{fwd,bwd}_cams,
+// either behind eg_project_covars_{fwd,bwd}_cams_flags (kOrtho with EG_FLAG_ORTHO).
+template <int CM>
 __global__ void __launch_bounds__(kFn)
 project_covars_fwd_kernel(const float *__restrict__ means, const float *__restrict__ covars,
                           const float *__restrict__ viewmats, const float *__restrict__ Ks, int N, int width,
@@ -187,7 +191,7 @@ project_covars_fwd_kernel(const float *__restrict__ means, const float *__restri
   for (int k = 0; k < 6; ++k) cv[k] = covars[6 * (size_t)g + k];
   Fwd f;
   int radius = 0;
-  if (forward_geom_covar(cam, m, cv, width, height, near_plane, far_plane, eps2d, f, cc, q0, q1))
+  if (forward_geom_covar<CM>(cam, m, cv, width, height, near_plane, far_plane, eps2d, f, cc, q0, q1))
     radius = radius_of(f, width, height, radius_clip);
   const bool keep = radius > 0;
   const size_t p = (size_t)c * N + g;
@@ -201,6 +205,7 @@ project_covars_fwd_kernel(const float *__restrict__ means, const float *__restri
   if (comps) comps[p] = keep ? f.comp : 0.f;
 }
 
+template <int CM>
 __global__ void __launch_bounds__(kFn)
 project_covars_bwd_kernel(const float *__restrict__ means, const float *__restrict__ covars,
                           const float *__restrict__ viewmats, const float *__restrict__ Ks, int N, int C, int width,
@@ -224,7 +229,7 @@ project_covars_bwd_kernel(const float *__restrict__ means, const float *__restri
     Fwd f;
     float cc[6], q0[3], q1[3];
     // near / far already passed in the forward (the radius is positive), so pass open limits
-    if (!forward_geom_covar(cam, m, cv, width, height, -3.0e38f, 3.0e38f, eps2d, f, cc, q0, q1)) continue;
+    if (!forward_geom_covar<CM>(cam, m, cv, width, height, -3.0e38f, 3.0e38f, eps2d, f, cc, q0, q1)) continue;
     const float vx = v_means2d[2 * p], vy = v_means2d[2 * p + 1];
     const float va = v_conics[3 * p], vb = v_conics[3 * p + 1], vc = v_conics[3 * p + 2];
     // conic = B^-1  =>  G = -A V A with V = [[va, vb/2],[vb/2, vc]] (b is stored once): backward_geom's sweep
@@ -243,29 +248,42 @@ project_covars_bwd_kernel(const float *__restrict__ means, const float *__restri
       G01 += vs * (omc * f.b);
       G11 += vs * (omc * f.c - eps2d * det_conic);
     }
-    // cov2d = J cc J^T (cc symmetric)  =>  v_J = 2 G Q with Q = J cc, v_cc = J^T G J
-    const float vJ00 = 2.f * (G00 * q0[0] + G01 * q1[0]);
-    const float vJ02 = 2.f * (G00 * q0[2] + G01 * q1[2]);
-    const float vJ11 = 2.f * (G01 * q0[1] + G11 * q1[1]);
-    const float vJ12 = 2.f * (G01 * q0[2] + G11 * q1[2]);
-    const float g0 = G00 * f.J02 + G01 * f.J12, g1 = G01 * f.J02 + G11 * f.J12;  // G J[:, 2]
     float vcc[9];
-    vcc[0] = f.J00 * f.J00 * G00;
-    vcc[1] = vcc[3] = f.J00 * f.J11 * G01;
-    vcc[2] = vcc[6] = f.J00 * g0;
-    vcc[4] = f.J11 * f.J11 * G11;
-    vcc[5] = vcc[7] = f.J11 * g1;
-    vcc[8] = f.J02 * g0 + f.J12 * g1;
-    // camera-space mean: through mean2d, the depth and J (fov clamp freezes tx = +-lim z)
-    const float rz3 = f.rz2 * f.rz;
-    float vtx = cam.fx * f.rz * vx;
-    float vty = cam.fy * f.rz * vy;
-    float vtz = -(cam.fx * f.x * vx + cam.fy * f.y * vy) * f.rz2 + (v_depths ? v_depths[p] : 0.f);
-    vtz += -cam.fx * f.rz2 * vJ00 - cam.fy * f.rz2 * vJ11;
-    if (f.in_x) { vtx += -cam.fx * f.rz2 * vJ02; vtz += 2.f * cam.fx * f.tx * rz3 * vJ02; }
-    else        { vtz += cam.fx * f.tx * rz3 * vJ02; }
-    if (f.in_y) { vty += -cam.fy * f.rz2 * vJ12; vtz += 2.f * cam.fy * f.ty * rz3 * vJ12; }
-    else        { vtz += cam.fy * f.ty * rz3 * vJ12; }
+    float vtx, vty, vtz;
+    if constexpr (CM == kOrtho) {
+      // cov2d = J cc J^T with the constant J = [[fx, 0, 0], [0, fy, 0]]: v_cc = J^T G J has the upper-left block only;
+      // camera-space mean: through mean2d and the depth
+      vcc[0] = f.J00 * f.J00 * G00;
+      vcc[1] = vcc[3] = f.J00 * f.J11 * G01;
+      vcc[4] = f.J11 * f.J11 * G11;
+      vcc[2] = vcc[6] = vcc[5] = vcc[7] = vcc[8] = 0.f;
+      vtx = cam.fx * vx;
+      vty = cam.fy * vy;
+      vtz = v_depths ? v_depths[p] : 0.f;
+    } else {
+      // cov2d = J cc J^T (cc symmetric)  =>  v_J = 2 G Q with Q = J cc, v_cc = J^T G J
+      const float vJ00 = 2.f * (G00 * q0[0] + G01 * q1[0]);
+      const float vJ02 = 2.f * (G00 * q0[2] + G01 * q1[2]);
+      const float vJ11 = 2.f * (G01 * q0[1] + G11 * q1[1]);
+      const float vJ12 = 2.f * (G01 * q0[2] + G11 * q1[2]);
+      const float g0 = G00 * f.J02 + G01 * f.J12, g1 = G01 * f.J02 + G11 * f.J12;  // G J[:, 2]
+      vcc[0] = f.J00 * f.J00 * G00;
+      vcc[1] = vcc[3] = f.J00 * f.J11 * G01;
+      vcc[2] = vcc[6] = f.J00 * g0;
+      vcc[4] = f.J11 * f.J11 * G11;
+      vcc[5] = vcc[7] = f.J11 * g1;
+      vcc[8] = f.J02 * g0 + f.J12 * g1;
+      // camera-space mean: through mean2d, the depth and J (fov clamp freezes tx = +-lim z)
+      const float rz3 = f.rz2 * f.rz;
+      vtx = cam.fx * f.rz * vx;
+      vty = cam.fy * f.rz * vy;
+      vtz = -(cam.fx * f.x * vx + cam.fy * f.y * vy) * f.rz2 + (v_depths ? v_depths[p] : 0.f);
+      vtz += -cam.fx * f.rz2 * vJ00 - cam.fy * f.rz2 * vJ11;
+      if (f.in_x) { vtx += -cam.fx * f.rz2 * vJ02; vtz += 2.f * cam.fx * f.tx * rz3 * vJ02; }
+      else        { vtz += cam.fx * f.tx * rz3 * vJ02; }
+      if (f.in_y) { vty += -cam.fy * f.rz2 * vJ12; vtz += 2.f * cam.fy * f.ty * rz3 * vJ12; }
+      else        { vtz += cam.fy * f.ty * rz3 * vJ12; }
+    }
     am[0] += cam.R[0] * vtx + cam.R[3] * vty + cam.R[6] * vtz;
     am[1] += cam.R[1] * vtx + cam.R[4] * vty + cam.R[7] * vtz;
     am[2] += cam.R[2] * vtx + cam.R[5] * vty + cam.R[8] * vtz;
@@ -348,10 +366,32 @@ extern "C" int eg_project_covars_fwd_cams(const float *means, const float *covar
   EG_REQUIRE(N >= 0 && C >= 1 && C <= 65535 && width > 0 && height > 0, "bad sizes");
   if (N == 0) return EG_OK;
   EG_REQUIRE(means && covars && viewmats && Ks && radii && means2d && depths && conics, "null pointer");
-  project_covars_fwd_kernel<<<dim3(cdiv(N, kFn), C), kFn, 0, as_stream(stream)>>>(
+  project_covars_fwd_kernel<kPinhole><<<dim3(cdiv(N, kFn), C), kFn, 0, as_stream(stream)>>>(
       means, covars, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip, radii, means2d, depths,
       conics, compensations);
   return check_launch("project_covars_fwd_cams");
+}
+
+// the same projection with a camera model: flags = 0 (pinhole, the kernels above) or EG_FLAG_ORTHO
+extern "C" int eg_project_covars_fwd_cams_flags(const float *means, const float *covars, const float *viewmats,
+                                                const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height,
+                                                float near_plane, float far_plane, float eps2d, float radius_clip,
+                                                int32_t *radii, float *means2d, float *depths, float *conics,
+                                                float *compensations, uint32_t flags, eg_stream_t stream) {
+  EG_REQUIRE(N >= 0 && C >= 1 && C <= 65535 && width > 0 && height > 0, "bad sizes");
+  EG_REQUIRE(!(flags & ~EG_FLAG_ORTHO), "flags: EG_FLAG_ORTHO or 0");
+  if (N == 0) return EG_OK;
+  EG_REQUIRE(means && covars && viewmats && Ks && radii && means2d && depths && conics, "null pointer");
+  const dim3 grid(cdiv(N, kFn), C);
+  if (flags & EG_FLAG_ORTHO)
+    project_covars_fwd_kernel<kOrtho><<<grid, kFn, 0, as_stream(stream)>>>(
+        means, covars, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip, radii, means2d, depths,
+        conics, compensations);
+  else
+    project_covars_fwd_kernel<kPinhole><<<grid, kFn, 0, as_stream(stream)>>>(
+        means, covars, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip, radii, means2d, depths,
+        conics, compensations);
+  return check_launch("project_covars_fwd_cams_flags");
 }
 
 extern "C" int eg_project_covars_bwd_cams(const float *means, const float *covars, const float *viewmats,
@@ -362,10 +402,31 @@ extern "C" int eg_project_covars_bwd_cams(const float *means, const float *covar
   EG_REQUIRE(N >= 0 && C >= 1 && width > 0 && height > 0, "bad sizes");
   if (N == 0) return EG_OK;
   EG_REQUIRE(means && covars && viewmats && Ks && radii && v_means2d && v_conics && v_means && v_covars, "null pointer");
-  project_covars_bwd_kernel<<<cdiv(N, kFn), kFn, 0, as_stream(stream)>>>(
+  project_covars_bwd_kernel<kPinhole><<<cdiv(N, kFn), kFn, 0, as_stream(stream)>>>(
       means, covars, viewmats, Ks, N, C, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_compensations,
       v_means, v_covars);
   return check_launch("project_covars_bwd_cams");
+}
+
+extern "C" int eg_project_covars_bwd_cams_flags(const float *means, const float *covars, const float *viewmats,
+                                                const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height,
+                                                float eps2d, const int32_t *radii, const float *v_means2d,
+                                                const float *v_depths, const float *v_conics,
+                                                const float *v_compensations, float *v_means, float *v_covars,
+                                                uint32_t flags, eg_stream_t stream) {
+  EG_REQUIRE(N >= 0 && C >= 1 && width > 0 && height > 0, "bad sizes");
+  EG_REQUIRE(!(flags & ~EG_FLAG_ORTHO), "flags: EG_FLAG_ORTHO or 0");
+  if (N == 0) return EG_OK;
+  EG_REQUIRE(means && covars && viewmats && Ks && radii && v_means2d && v_conics && v_means && v_covars, "null pointer");
+  if (flags & EG_FLAG_ORTHO)
+    project_covars_bwd_kernel<kOrtho><<<cdiv(N, kFn), kFn, 0, as_stream(stream)>>>(
+        means, covars, viewmats, Ks, N, C, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_compensations,
+        v_means, v_covars);
+  else
+    project_covars_bwd_kernel<kPinhole><<<cdiv(N, kFn), kFn, 0, as_stream(stream)>>>(
+        means, covars, viewmats, Ks, N, C, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_compensations,
+        v_means, v_covars);
+  return check_launch("project_covars_bwd_cams_flags");
 }
 
 extern "C" int eg_isect_offset_encode(const int64_t *isect_ids, int64_t M, int32_t C, int32_t tile_width,

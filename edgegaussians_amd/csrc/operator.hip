@@ -46,6 +46,7 @@ using namespace eg;
 
 extern "C" int eg_operator_fwd(const eg_operator_args *a, eg_stream_t stream) {
   EG_REQUIRE(a != nullptr, "null args");
+  EG_REQUIRE(!(a->flags & EG_FLAG_ORTHO), "EG_FLAG_ORTHO is not implemented here (the unit-colour fast path is pinhole only)");
   EG_REQUIRE(a->N > 0 && a->width > 0 && a->height > 0 && a->seg_cap > 0 && a->max_items > 0, "bad sizes");
   EG_REQUIRE(a->means && a->quats && a->scales && a->opacities && a->viewmat && a->K && a->splat && a->alphas && a->gtstop &&
                  a->tile_counts && a->tile_start && a->tile_end && a->item_first && a->item_end && a->item_tile &&
@@ -91,6 +92,7 @@ extern "C" int eg_operator_bwd(const eg_operator_args *a, const float *v_alphas,
                                float *v_opacities, eg_stream_t stream) {
   EG_REQUIRE(a != nullptr && v_alphas && rec && g2d && v_means && v_quats && v_scales && v_opacities, "null pointer");
   EG_REQUIRE(a->N > 0 && a->width > 0 && a->height > 0 && v_stride >= 1, "bad sizes");
+  EG_REQUIRE(!(a->flags & EG_FLAG_ORTHO), "EG_FLAG_ORTHO is not implemented here (the unit-colour fast path is pinhole only)");
   hipStream_t st = as_stream(stream);
   const int hw = a->width * a->height;
   scale_record_kernel<<<cdiv(hw, 256), 256, 0, st>>>((const StopRec *)a->gtstop, v_alphas, v_stride, (StopRec *)rec, hw);

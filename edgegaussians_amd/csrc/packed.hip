@@ -27,7 +27,9 @@ namespace eg {
 
 constexpr int kPk = 256;  // threads (= Gaussians) per workgroup of the count and write passes
 
-// this thread's Gaussian in camera blockIdx.y: radius after every cull (0 = not kept)
+// this thread's Gaussian in camera blockIdx.y: radius after every cull (0 = not kept).  CM: the camera model
+// (csrc/project_dev.h) of every kernel here, kOrtho with EG_FLAG_ORTHO.
+template <int CM>
 __device__ __forceinline__ int packed_project(const float *__restrict__ means, const float *__restrict__ quats,
                                               const float *__restrict__ scales, const float *__restrict__ opacities,
                                               const float *__restrict__ viewmats, const float *__restrict__ Ks, int N,
@@ -35,11 +37,12 @@ __device__ __forceinline__ int packed_project(const float *__restrict__ means, c
                                               float radius_clip, uint32_t flags, int g, Fwd &f) {
   if (g >= N) return 0;
   const Cam cam = load_cam(viewmats + 16 * (size_t)blockIdx.y, Ks + 9 * (size_t)blockIdx.y);
-  if (!forward_geom(cam, means, quats, scales, opacities, g, width, height, near_plane, far_plane, eps2d, flags, f))
+  if (!forward_geom<CM>(cam, means, quats, scales, opacities, g, width, height, near_plane, far_plane, eps2d, flags, f))
     return 0;
   return radius_of(f, width, height, radius_clip);
 }
 
+template <int CM>
 __global__ void __launch_bounds__(kPk)
 packed_count_kernel(const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
                     const float *__restrict__ opacities, const float *__restrict__ viewmats,
@@ -48,8 +51,8 @@ packed_count_kernel(const float *__restrict__ means, const float *__restrict__ q
   __shared__ int s_wave[kPk / 64];
   const int g = blockIdx.x * kPk + threadIdx.x;
   Fwd f;
-  const int radius = packed_project(means, quats, scales, opacities, viewmats, Ks, N, width, height, near_plane,
-                                    far_plane, eps2d, radius_clip, flags, g, f);
+  const int radius = packed_project<CM>(means, quats, scales, opacities, viewmats, Ks, N, width, height, near_plane,
+                                        far_plane, eps2d, radius_clip, flags, g, f);
   const unsigned long long vote = __ballot(radius > 0);
   if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(vote);
   __syncthreads();
@@ -81,7 +84,7 @@ packed_scan_kernel(int *__restrict__ block_counts, int nb, int C, long long *__r
   if (threadIdx.x == 0) indptr[C] = carry;
 }
 
-template <bool LDS_COUNT>
+template <bool LDS_COUNT, int CM>
 __global__ void __launch_bounds__(kPk)
 packed_write_kernel(const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
                     const float *__restrict__ opacities, const float *__restrict__ viewmats,
@@ -100,8 +103,8 @@ packed_write_kernel(const float *__restrict__ means, const float *__restrict__ q
   }
   const int g = blockIdx.x * kPk + threadIdx.x;
   Fwd f;
-  const int radius = packed_project(means, quats, scales, opacities, viewmats, Ks, N, width, height, near_plane,
-                                    far_plane, eps2d, radius_clip, flags, g, f);
+  const int radius = packed_project<CM>(means, quats, scales, opacities, viewmats, Ks, N, width, height, near_plane,
+                                        far_plane, eps2d, radius_clip, flags, g, f);
   const bool keep = radius > 0;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const unsigned long long vote = __ballot(keep);
@@ -149,6 +152,7 @@ packed_rebase_kernel(int *__restrict__ flatten_ids, long long *__restrict__ isec
   if (isect_ids) isect_ids[i] |= camera_bits;
 }
 
+template <int CM>
 __device__ __forceinline__ void packed_pair_vjp(const float *__restrict__ means, const float *__restrict__ quats,
                                                 const float *__restrict__ scales, const float *__restrict__ opacities,
                                                 const float *__restrict__ viewmats, const float *__restrict__ Ks,
@@ -160,10 +164,11 @@ __device__ __forceinline__ void packed_pair_vjp(const float *__restrict__ means,
   const float4 ga = g2d[2 * p], gb = g2d[2 * p + 1];
   Fwd f;
   // near / far and det culls already passed in the forward (the pair exists), so pass open limits
-  forward_geom(cam, means, quats, scales, opacities, g, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f);
-  backward_geom(cam, f, eps2d, flags, ga, gb, true, v_comps[p], v_depths ? v_depths[p] : 0.f, gr);
+  forward_geom<CM>(cam, means, quats, scales, opacities, g, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f);
+  backward_geom<false, CM>(cam, f, eps2d, flags, ga, gb, true, v_comps[p], v_depths ? v_depths[p] : 0.f, gr);
 }
 
+template <int CM>
 __global__ void __launch_bounds__(256)
 packed_bwd_dense_kernel(const float *__restrict__ means, const float *__restrict__ quats,
                         const float *__restrict__ scales, const float *__restrict__ opacities,
@@ -189,8 +194,8 @@ packed_bwd_dense_kernel(const float *__restrict__ means, const float *__restrict
     }
     if (lo >= end || gaussian_ids[lo] != g) continue;
     Grads gr;
-    packed_pair_vjp(means, quats, scales, opacities, viewmats, Ks, c, g, lo, width, height, eps2d, flags, g2d, v_comps,
-                    v_depths, gr);
+    packed_pair_vjp<CM>(means, quats, scales, opacities, viewmats, Ks, c, g, lo, width, height, eps2d, flags, g2d, v_comps,
+                        v_depths, gr);
 #pragma unroll
     for (int k = 0; k < 3; ++k) { acc.mean[k] += gr.mean[k]; acc.scale[k] += gr.scale[k]; }
 #pragma unroll
@@ -202,6 +207,7 @@ packed_bwd_dense_kernel(const float *__restrict__ means, const float *__restrict
   for (int k = 0; k < 4; ++k) v_quats[4 * g + k] = acc.quat[k];
 }
 
+template <int CM>
 __global__ void __launch_bounds__(256)
 packed_bwd_sparse_kernel(const float *__restrict__ means, const float *__restrict__ quats,
                          const float *__restrict__ scales, const float *__restrict__ opacities,
@@ -220,8 +226,8 @@ packed_bwd_sparse_kernel(const float *__restrict__ means, const float *__restric
 #pragma unroll
   for (int k = 0; k < 4; ++k) gr.quat[k] = 0.f;
   if (c >= 0 && c < C && g >= 0 && g < N)  // (ids written by packed_write_kernel: a guard against a caller's stale arrays)
-    packed_pair_vjp(means, quats, scales, opacities, viewmats, Ks, (int)c, (int)g, p, width, height, eps2d, flags, g2d,
-                    v_comps, v_depths, gr);
+    packed_pair_vjp<CM>(means, quats, scales, opacities, viewmats, Ks, (int)c, (int)g, p, width, height, eps2d, flags, g2d,
+                        v_comps, v_depths, gr);
 #pragma unroll
   for (int k = 0; k < 3; ++k) { v_means[3 * p + k] = gr.mean[k]; v_scales[3 * p + k] = gr.scale[k]; }
 #pragma unroll
@@ -244,9 +250,13 @@ extern "C" int eg_packed_count(const float *means, const float *quats, const flo
   EG_REQUIRE(N == 0 || (means && quats && scales && opacities && block_base), "null pointer");
   hipStream_t s = as_stream(stream);
   const int nb = cdiv(N, kPk);
-  if (N > 0)
-    packed_count_kernel<<<dim3(nb, C), kPk, 0, s>>>(means, quats, scales, opacities, viewmats, Ks, N, width, height,
-                                                    near_plane, far_plane, eps2d, radius_clip, flags, block_base);
+#define EG_PACKED_COUNT(CM_)                                                                                       \
+  packed_count_kernel<CM_><<<dim3(nb, C), kPk, 0, s>>>(means, quats, scales, opacities, viewmats, Ks, N, width, height, \
+                                                       near_plane, far_plane, eps2d, radius_clip, flags, block_base)
+  if (N > 0) {
+    if (flags & EG_FLAG_ORTHO) EG_PACKED_COUNT(kOrtho); else EG_PACKED_COUNT(kPinhole);
+  }
+#undef EG_PACKED_COUNT
   packed_scan_kernel<<<1, 256, 0, s>>>(block_base, nb, C, (long long *)indptr);
   return check_launch("packed_count");
 }
@@ -266,12 +276,16 @@ extern "C" int eg_packed_write(const float *means, const float *quats, const flo
              "null pointer");
   hipStream_t s = as_stream(stream);
   const int T = cdiv(width, kTile) * cdiv(height, kTile);
-#define EG_PACKED_WRITE(LDS, SMEM)                                                                                   \
-  packed_write_kernel<LDS><<<dim3(cdiv(N, kPk), C), kPk, SMEM, s>>>(                                                 \
+#define EG_PACKED_WRITE(LDS, CM_, SMEM)                                                                              \
+  packed_write_kernel<LDS, CM_><<<dim3(cdiv(N, kPk), C), kPk, SMEM, s>>>(                                            \
       means, quats, scales, opacities, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip,    \
       flags, block_base, (long long)nnz, (float4 *)splat, radii, means2d, depths, conics, compensations,             \
       tiles_per_gauss, (long long *)camera_ids, (long long *)gaussian_ids, tile_counts)
-  if (T <= 16384) EG_PACKED_WRITE(true, sizeof(int) * T); else EG_PACKED_WRITE(false, 0);
+  if (flags & EG_FLAG_ORTHO) {
+    if (T <= 16384) EG_PACKED_WRITE(true, kOrtho, sizeof(int) * T); else EG_PACKED_WRITE(false, kOrtho, 0);
+  } else {
+    if (T <= 16384) EG_PACKED_WRITE(true, kPinhole, sizeof(int) * T); else EG_PACKED_WRITE(false, kPinhole, 0);
+  }
 #undef EG_PACKED_WRITE
   return check_launch("packed_write");
 }
@@ -332,9 +346,12 @@ extern "C" int eg_packed_bwd(const float *means, const float *quats, const float
   EG_REQUIRE(means && quats && scales && opacities && viewmats && Ks && indptr && v_means && v_quats && v_scales,
              "null pointer");
   EG_REQUIRE(nnz == 0 || (gaussian_ids && g2d && v_comps), "null pointer");
-  packed_bwd_dense_kernel<<<cdiv(N, 256), 256, 0, as_stream(stream)>>>(
-      means, quats, scales, opacities, viewmats, Ks, N, C, width, height, eps2d, flags, (const long long *)indptr,
-      (long long)nnz, (const long long *)gaussian_ids, (const float4 *)g2d, v_comps, v_depths, v_means, v_quats, v_scales);
+#define EG_PACKED_BWD(CM_)                                                                                           \
+  packed_bwd_dense_kernel<CM_><<<cdiv(N, 256), 256, 0, as_stream(stream)>>>(                                         \
+      means, quats, scales, opacities, viewmats, Ks, N, C, width, height, eps2d, flags, (const long long *)indptr,   \
+      (long long)nnz, (const long long *)gaussian_ids, (const float4 *)g2d, v_comps, v_depths, v_means, v_quats, v_scales)
+  if (flags & EG_FLAG_ORTHO) EG_PACKED_BWD(kOrtho); else EG_PACKED_BWD(kPinhole);
+#undef EG_PACKED_BWD
   return check_launch("packed_bwd");
 }
 
@@ -351,9 +368,12 @@ extern "C" int eg_packed_bwd_sparse(const float *means, const float *quats, cons
   EG_REQUIRE(means && quats && scales && opacities && viewmats && Ks && camera_ids && gaussian_ids && g2d && v_comps &&
                  v_means && v_quats && v_scales,
              "null pointer");
-  packed_bwd_sparse_kernel<<<cdiv(nnz, 256), 256, 0, as_stream(stream)>>>(
-      means, quats, scales, opacities, viewmats, Ks, N, C, width, height, eps2d, flags, (long long)nnz,
-      (const long long *)camera_ids, (const long long *)gaussian_ids, (const float4 *)g2d, v_comps, v_depths, v_means,
-      v_quats, v_scales);
+#define EG_PACKED_BWD_SPARSE(CM_)                                                                                    \
+  packed_bwd_sparse_kernel<CM_><<<cdiv(nnz, 256), 256, 0, as_stream(stream)>>>(                                      \
+      means, quats, scales, opacities, viewmats, Ks, N, C, width, height, eps2d, flags, (long long)nnz,              \
+      (const long long *)camera_ids, (const long long *)gaussian_ids, (const float4 *)g2d, v_comps, v_depths, v_means, \
+      v_quats, v_scales)
+  if (flags & EG_FLAG_ORTHO) EG_PACKED_BWD_SPARSE(kOrtho); else EG_PACKED_BWD_SPARSE(kPinhole);
+#undef EG_PACKED_BWD_SPARSE
   return check_launch("packed_bwd_sparse");
 }

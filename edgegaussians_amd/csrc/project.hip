@@ -21,7 +21,8 @@ namespace eg {
 
 // The per-tile counters are privatised in LDS (one global atomic per workgroup per touched tile):
 // the hot counters of a view share a dozen cache lines and direct atomics serialise on them.
-template <bool LDS_COUNT>
+// CM: the camera model (csrc/project_dev.h), kOrtho on the operator path with EG_FLAG_ORTHO.
+template <bool LDS_COUNT, int CM = kPinhole>
 __global__ void __launch_bounds__(256)
 project_fwd_kernel(const float *__restrict__ means, const float *__restrict__ quats,
                    const float *__restrict__ scales, const float *__restrict__ opacities,
@@ -45,7 +46,7 @@ project_fwd_kernel(const float *__restrict__ means, const float *__restrict__ qu
   Fwd f;
   int radius = 0;
   if (live &&
-      forward_geom(cam, means, quats, scales, opacities, g, width, height, near_plane, far_plane, eps2d, flags, f))
+      forward_geom<CM>(cam, means, quats, scales, opacities, g, width, height, near_plane, far_plane, eps2d, flags, f))
     radius = radius_of(f, width, height, radius_clip);
 
   const bool aa = flags & EG_FLAG_ANTIALIASED;
@@ -145,7 +146,7 @@ project_fwd_kernel(const float *__restrict__ means, const float *__restrict__ qu
 }
 
 
-template <bool ADAM>
+template <bool ADAM, int CM = kPinhole>
 __global__ void __launch_bounds__(256)
 project_bwd_kernel(float *__restrict__ means, float *__restrict__ quats, float *__restrict__ scales,
                    float *__restrict__ opacities, const float *__restrict__ viewmat, const float *__restrict__ K,
@@ -169,9 +170,9 @@ project_bwd_kernel(float *__restrict__ means, float *__restrict__ quats, float *
     const float4 ga = g2d[2 * g], gb = g2d[2 * g + 1];
     Fwd f;
     // near/far and det culls already passed in the forward (radius > 0), so pass open limits
-    forward_geom(cam, means, quats, scales, opacities, g, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f);
-    backward_geom(cam, f, eps2d, flags, ga, gb, v_comps_ext != nullptr, v_comps_ext ? v_comps_ext[g] : 0.f,
-                  v_depths_ext ? v_depths_ext[g] : 0.f, gr);
+    forward_geom<CM>(cam, means, quats, scales, opacities, g, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f);
+    backward_geom<false, CM>(cam, f, eps2d, flags, ga, gb, v_comps_ext != nullptr, v_comps_ext ? v_comps_ext[g] : 0.f,
+                             v_depths_ext ? v_depths_ext[g] : 0.f, gr);
     if (absgrads && !(flags & EG_FLAG_ABSGRAD_WRITE)) absgrads[g] += sqrtf(ga.z * ga.z + ga.w * ga.w);
     if (absgrads && (flags & EG_FLAG_ABSGRAD_WRITE)) absgrads[g] = sqrtf(ga.z * ga.z + ga.w * ga.w);
   } else if (absgrads && (flags & EG_FLAG_ABSGRAD_WRITE)) {
@@ -710,16 +711,18 @@ static int launch_project_fwd(const float *means, const float *quats, const floa
                               uint32_t *tile_mask, int32_t *offsets, int32_t *item_offsets, int32_t *total,
                               int64_t capacity, int32_t *ticket, eg_stream_t stream) {
   const int T = cdiv(width, kTile) * cdiv(height, kTile);
-  if (tile_counts && T <= 16384)
-    project_fwd_kernel<true><<<cdiv(N, 256), 256, sizeof(int) * T, as_stream(stream)>>>(
-        means, quats, scales, opacities, viewmat, K, N, width, height, near_plane, far_plane, eps2d, radius_clip,
-        flags, (float4 *)splat, radii, means2d, depths, conics, compensations, tiles_per_gauss, tile_counts,
-        (float4 *)g2d, tile_mask, offsets, item_offsets, total, (long long)capacity, ticket);
-  else
-    project_fwd_kernel<false><<<cdiv(N, 256), 256, 0, as_stream(stream)>>>(
-        means, quats, scales, opacities, viewmat, K, N, width, height, near_plane, far_plane, eps2d, radius_clip,
-        flags, (float4 *)splat, radii, means2d, depths, conics, compensations, tiles_per_gauss, tile_counts,
-        (float4 *)g2d, tile_mask, offsets, item_offsets, total, (long long)capacity, ticket);
+#define EG_PROJECT_FWD(LDS, CM_, SMEM)                                                                               \
+  project_fwd_kernel<LDS, CM_><<<cdiv(N, 256), 256, SMEM, as_stream(stream)>>>(                                      \
+      means, quats, scales, opacities, viewmat, K, N, width, height, near_plane, far_plane, eps2d, radius_clip,      \
+      flags, (float4 *)splat, radii, means2d, depths, conics, compensations, tiles_per_gauss, tile_counts,           \
+      (float4 *)g2d, tile_mask, offsets, item_offsets, total, (long long)capacity, ticket)
+  const bool lds = tile_counts && T <= 16384;
+  if (flags & EG_FLAG_ORTHO) {
+    if (lds) EG_PROJECT_FWD(true, kOrtho, sizeof(int) * T); else EG_PROJECT_FWD(false, kOrtho, 0);
+  } else {
+    if (lds) EG_PROJECT_FWD(true, kPinhole, sizeof(int) * T); else EG_PROJECT_FWD(false, kPinhole, 0);
+  }
+#undef EG_PROJECT_FWD
   return check_launch("project_fwd");
 }
 
@@ -743,6 +746,7 @@ extern "C" int eg_project_bin(const float *means, const float *quats, const floa
                               uint32_t *tile_mask, int64_t capacity, int32_t *offsets, int32_t *item_offsets,
                               int32_t *total, int32_t *ticket, eg_stream_t stream) {
   EG_REQUIRE(N > 0 && width > 0 && height > 0, "bad sizes");
+  EG_REQUIRE(!(flags & EG_FLAG_ORTHO), "EG_FLAG_ORTHO is not implemented here (the training path is pinhole only)");
   EG_REQUIRE(means && quats && log_scales && logit_opacities && viewmat && K && splat && tile_counts && tile_mask &&
                  offsets && item_offsets && total && ticket,
              "null pointer");
@@ -783,6 +787,7 @@ extern "C" int eg_project_emit(const float *means, const float *quats, const flo
                                int32_t seg_cap, uint64_t *keys, int32_t *item_first, int32_t max_items,
                                int32_t *total, int32_t *ticket, eg_stream_t stream) {
   EG_REQUIRE(N > 0 && width > 0 && height > 0 && seg_cap > 0 && max_items > 0, "bad sizes");
+  EG_REQUIRE(!(flags & EG_FLAG_ORTHO), "EG_FLAG_ORTHO is not implemented here (the training path is pinhole only)");
   EG_REQUIRE(means && quats && log_scales && logit_opacities && viewmat && K && splat && tile_cursor && keys &&
                  item_first && total && ticket,
              "null pointer");
@@ -805,10 +810,13 @@ extern "C" int eg_project_bwd(const float *means, const float *quats, const floa
   EG_REQUIRE(means && quats && scales && opacities && viewmat && K && splat && g2d, "null pointer");
   EG_REQUIRE(v_means && v_quats && v_scales && (v_opacities || v_comps_ext), "null gradient output");
   AdamK dummy = {};
-  project_bwd_kernel<false><<<cdiv(N, 256), 256, 0, as_stream(stream)>>>(
-      (float *)means, (float *)quats, (float *)scales, (float *)opacities, viewmat, K, N, width, height, eps2d,
-      flags, (const float4 *)splat, (const float4 *)g2d, v_means, v_quats, v_scales, v_opacities, absgrads,
-      v_comps_ext, v_depths_ext, nullptr, nullptr, dummy);
+#define EG_PROJECT_BWD(CM_)                                                                                          \
+  project_bwd_kernel<false, CM_><<<cdiv(N, 256), 256, 0, as_stream(stream)>>>(                                       \
+      (float *)means, (float *)quats, (float *)scales, (float *)opacities, viewmat, K, N, width, height, eps2d,      \
+      flags, (const float4 *)splat, (const float4 *)g2d, v_means, v_quats, v_scales, v_opacities, absgrads,          \
+      v_comps_ext, v_depths_ext, nullptr, nullptr, dummy)
+  if (flags & EG_FLAG_ORTHO) EG_PROJECT_BWD(kOrtho); else EG_PROJECT_BWD(kPinhole);
+#undef EG_PROJECT_BWD
   return check_launch("project_bwd");
 }
 
@@ -817,6 +825,7 @@ extern "C" int eg_project_bwd_adam(float *means, float *quats, float *scales, fl
                                    float eps2d, uint32_t flags, const float *splat, const float *g2d, float *m,
                                    float *v, float *absgrads, eg_adam_hyper hyper, eg_stream_t stream) {
   EG_REQUIRE(N >= 0 && hyper.step >= 1, "bad sizes / step");
+  EG_REQUIRE(!(flags & EG_FLAG_ORTHO), "EG_FLAG_ORTHO is not implemented here (the training path is pinhole only)");
   if (N == 0) return EG_OK;
   EG_REQUIRE(means && quats && scales && opacities && viewmat && K && splat && g2d && m && v, "null pointer");
   project_bwd_kernel<true><<<cdiv(N, 256), 256, 0, as_stream(stream)>>>(
@@ -863,6 +872,7 @@ extern "C" int eg_backward_fused(float *means, float *quats, float *scales, floa
                                  float *absgrads, float *m, float *v, const eg_adam_hyper *hyper_host,
                                  eg_stream_t stream) {
   EG_REQUIRE(N >= 0 && width > 0 && height > 0, "bad sizes");
+  EG_REQUIRE(!(flags & EG_FLAG_ORTHO), "EG_FLAG_ORTHO is not implemented here (the training path is pinhole only)");
   if (N == 0) return EG_OK;
   EG_REQUIRE(means && quats && scales && opacities && viewmat && K && splat && gtstop && g2d, "null pointer");
   int rc = eg_composite_bwd_footprint(splat, N, width, height, gtstop, g2d, stream);
@@ -957,6 +967,7 @@ extern "C" int eg_adam_emit(float *means, float *scales, float *quats, float *op
                             int32_t *item_first, int32_t max_items, int32_t *total, int32_t *ticket,
                             eg_stream_t stream) {
   EG_REQUIRE(N > 0 && hyper.step >= 1 && width > 0 && height > 0 && seg_cap > 0 && max_items > 0, "bad sizes / step");
+  EG_REQUIRE(!(flags & EG_FLAG_ORTHO), "EG_FLAG_ORTHO is not implemented here (the training path is pinhole only)");
   EG_REQUIRE(means && scales && quats && opacities && g_means && g_scales && g_quats && g_opacities && m && v &&
                  next_viewmat && next_K && splat && tile_cursor && keys && item_first && total,
              "null pointer");

@@ -12,6 +12,12 @@ struct Cam {
   float R[9], t[3], fx, fy, cx, cy;
 };
 
+// Camera model, a COMPILE-TIME parameter of forward_geom / forward_geom_covar / backward_geom (default: pinhole, the only
+// model the training kernels instantiate).  kOrtho (EG_FLAG_ORTHO on the operator path, gsplat camera_model="ortho"):
+// mean2d = (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]] -- no division by z, no fov clamp, cov2d independent of
+// the mean; culls, depth and everything behind cov2d are the pinhole's.
+enum CamModel : int { kPinhole = 0, kOrtho = 1 };
+
 __device__ __forceinline__ Cam load_cam(const float *__restrict__ vm, const float *__restrict__ K) {
   Cam c;
   c.R[0] = vm[0]; c.R[1] = vm[1]; c.R[2] = vm[2];  c.t[0] = vm[3];
@@ -54,6 +60,7 @@ __device__ __forceinline__ Raw load_raw(const float *__restrict__ means, const f
   return r;
 }
 
+template <int CM = kPinhole>
 __device__ __forceinline__ bool forward_geom(const Cam &cam, const Raw &raw, int width, int height,
                                              float near_plane, float far_plane, float eps2d, uint32_t flags,
                                              Fwd &f) {
@@ -96,29 +103,45 @@ __device__ __forceinline__ bool forward_geom(const Cam &cam, const Raw &raw, int
       f.W[3 * i + k] =
           (cam.R[3 * i] * f.Rq[k] + cam.R[3 * i + 1] * f.Rq[3 + k] + cam.R[3 * i + 2] * f.Rq[6 + k]) * f.s[k];
 
-  const float lim_x = kFovClamp * (0.5f * (float)width / cam.fx);
-  const float lim_y = kFovClamp * (0.5f * (float)height / cam.fy);
-  f.rz = 1.f / f.z;
-  f.rz2 = f.rz * f.rz;
-  const float xr = f.x * f.rz, yr = f.y * f.rz;
-  f.in_x = (xr <= lim_x) && (xr >= -lim_x);
-  f.in_y = (yr <= lim_y) && (yr >= -lim_y);
-  f.tx = f.z * fminf(lim_x, fmaxf(-lim_x, xr));
-  f.ty = f.z * fminf(lim_y, fmaxf(-lim_y, yr));
-  f.J00 = cam.fx * f.rz;
-  f.J11 = cam.fy * f.rz;
-  f.J02 = -cam.fx * f.tx * f.rz2;
-  f.J12 = -cam.fy * f.ty * f.rz2;
+  if constexpr (CM == kOrtho) {
+    // J = [[fx, 0, 0], [0, fy, 0]]: P = J W takes the first two rows of W; the pinhole-only fields read as "no clamp"
+    f.rz = 0.f; f.rz2 = 0.f;
+    f.in_x = true; f.in_y = true;
+    f.tx = f.x; f.ty = f.y;
+    f.J00 = cam.fx; f.J11 = cam.fy;
+    f.J02 = 0.f; f.J12 = 0.f;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    f.p0[k] = f.J00 * f.W[k] + f.J02 * f.W[6 + k];
-    f.p1[k] = f.J11 * f.W[3 + k] + f.J12 * f.W[6 + k];
+    for (int k = 0; k < 3; ++k) {
+      f.p0[k] = f.J00 * f.W[k];
+      f.p1[k] = f.J11 * f.W[3 + k];
+    }
+    f.u = cam.fx * f.x + cam.cx;
+    f.v = cam.fy * f.y + cam.cy;
+  } else {
+    const float lim_x = kFovClamp * (0.5f * (float)width / cam.fx);
+    const float lim_y = kFovClamp * (0.5f * (float)height / cam.fy);
+    f.rz = 1.f / f.z;
+    f.rz2 = f.rz * f.rz;
+    const float xr = f.x * f.rz, yr = f.y * f.rz;
+    f.in_x = (xr <= lim_x) && (xr >= -lim_x);
+    f.in_y = (yr <= lim_y) && (yr >= -lim_y);
+    f.tx = f.z * fminf(lim_x, fmaxf(-lim_x, xr));
+    f.ty = f.z * fminf(lim_y, fmaxf(-lim_y, yr));
+    f.J00 = cam.fx * f.rz;
+    f.J11 = cam.fy * f.rz;
+    f.J02 = -cam.fx * f.tx * f.rz2;
+    f.J12 = -cam.fy * f.ty * f.rz2;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      f.p0[k] = f.J00 * f.W[k] + f.J02 * f.W[6 + k];
+      f.p1[k] = f.J11 * f.W[3 + k] + f.J12 * f.W[6 + k];
+    }
+    f.u = cam.fx * f.x * f.rz + cam.cx;
+    f.v = cam.fy * f.y * f.rz + cam.cy;
   }
   f.c00 = f.p0[0] * f.p0[0] + f.p0[1] * f.p0[1] + f.p0[2] * f.p0[2];
   f.c01 = f.p0[0] * f.p1[0] + f.p0[1] * f.p1[1] + f.p0[2] * f.p1[2];
   f.c11 = f.p1[0] * f.p1[0] + f.p1[1] * f.p1[1] + f.p1[2] * f.p1[2];
-  f.u = cam.fx * f.x * f.rz + cam.cx;
-  f.v = cam.fy * f.y * f.rz + cam.cy;
 
   f.det0 = f.c00 * f.c11 - f.c01 * f.c01;
   f.b00 = f.c00 + eps2d;
@@ -133,13 +156,14 @@ __device__ __forceinline__ bool forward_geom(const Cam &cam, const Raw &raw, int
   return true;
 }
 
+template <int CM = kPinhole>
 __device__ __forceinline__ bool forward_geom(const Cam &cam, const float *__restrict__ means,
                                              const float *__restrict__ quats, const float *__restrict__ scales,
                                              const float *__restrict__ opacities, int g, int width, int height,
                                              float near_plane, float far_plane, float eps2d, uint32_t flags,
                                              Fwd &f) {
-  return forward_geom(cam, load_raw(means, quats, scales, opacities, g), width, height, near_plane, far_plane, eps2d,
-                      flags, f);
+  return forward_geom<CM>(cam, load_raw(means, quats, scales, opacities, g), width, height, near_plane, far_plane, eps2d,
+                          flags, f);
 }
 
 // Projection from a covariance (gsplat `fully_fused_projection(covars=[N,6])`, csrc/functional.hip): the world
@@ -147,6 +171,7 @@ __device__ __forceinline__ bool forward_geom(const Cam &cam, const float *__rest
 // of `f` that radius_of and the reverse sweep of functional.hip read (camera-space mean, clamp, J, cov2d, conic,
 // compensation, mean2d; the quaternion / scale / W / p0 / p1 fields stay untouched), the camera-space covariance
 // cc (same six entries) and Q = J cc (rows q0, q1).  Same culls, clamp and rounding discipline as forward_geom.
+template <int CM = kPinhole>
 __device__ __forceinline__ bool forward_geom_covar(const Cam &cam, const float *__restrict__ m,
                                                    const float *__restrict__ cv, int width, int height,
                                                    float near_plane, float far_plane, float eps2d, Fwd &f,
@@ -171,31 +196,47 @@ __device__ __forceinline__ bool forward_geom_covar(const Cam &cam, const float *
   for (int e = 0; e < 6; ++e)
     cc[e] = A[3 * ui[e]] * cam.R[3 * uj[e]] + A[3 * ui[e] + 1] * cam.R[3 * uj[e] + 1] + A[3 * ui[e] + 2] * cam.R[3 * uj[e] + 2];
 
-  const float lim_x = kFovClamp * (0.5f * (float)width / cam.fx);
-  const float lim_y = kFovClamp * (0.5f * (float)height / cam.fy);
-  f.rz = 1.f / f.z;
-  f.rz2 = f.rz * f.rz;
-  const float xr = f.x * f.rz, yr = f.y * f.rz;
-  f.in_x = (xr <= lim_x) && (xr >= -lim_x);
-  f.in_y = (yr <= lim_y) && (yr >= -lim_y);
-  f.tx = f.z * fminf(lim_x, fmaxf(-lim_x, xr));
-  f.ty = f.z * fminf(lim_y, fmaxf(-lim_y, yr));
-  f.J00 = cam.fx * f.rz;
-  f.J11 = cam.fy * f.rz;
-  f.J02 = -cam.fx * f.tx * f.rz2;
-  f.J12 = -cam.fy * f.ty * f.rz2;
-  // Q = J cc, cov2d = Q J^T
-  q0[0] = f.J00 * cc[0] + f.J02 * cc[2];
-  q0[1] = f.J00 * cc[1] + f.J02 * cc[4];
-  q0[2] = f.J00 * cc[2] + f.J02 * cc[5];
-  q1[0] = f.J11 * cc[1] + f.J12 * cc[2];
-  q1[1] = f.J11 * cc[3] + f.J12 * cc[4];
-  q1[2] = f.J11 * cc[4] + f.J12 * cc[5];
-  f.c00 = q0[0] * f.J00 + q0[2] * f.J02;
-  f.c01 = q0[1] * f.J11 + q0[2] * f.J12;
-  f.c11 = q1[1] * f.J11 + q1[2] * f.J12;
-  f.u = cam.fx * f.x * f.rz + cam.cx;
-  f.v = cam.fy * f.y * f.rz + cam.cy;
+  if constexpr (CM == kOrtho) {
+    // J = [[fx, 0, 0], [0, fy, 0]]: Q = J cc scales the first two rows of cc, cov2d = Q J^T its upper-left block
+    f.rz = 0.f; f.rz2 = 0.f;
+    f.in_x = true; f.in_y = true;
+    f.tx = f.x; f.ty = f.y;
+    f.J00 = cam.fx; f.J11 = cam.fy;
+    f.J02 = 0.f; f.J12 = 0.f;
+    q0[0] = f.J00 * cc[0]; q0[1] = f.J00 * cc[1]; q0[2] = f.J00 * cc[2];
+    q1[0] = f.J11 * cc[1]; q1[1] = f.J11 * cc[3]; q1[2] = f.J11 * cc[4];
+    f.c00 = q0[0] * f.J00;
+    f.c01 = q0[1] * f.J11;
+    f.c11 = q1[1] * f.J11;
+    f.u = cam.fx * f.x + cam.cx;
+    f.v = cam.fy * f.y + cam.cy;
+  } else {
+    const float lim_x = kFovClamp * (0.5f * (float)width / cam.fx);
+    const float lim_y = kFovClamp * (0.5f * (float)height / cam.fy);
+    f.rz = 1.f / f.z;
+    f.rz2 = f.rz * f.rz;
+    const float xr = f.x * f.rz, yr = f.y * f.rz;
+    f.in_x = (xr <= lim_x) && (xr >= -lim_x);
+    f.in_y = (yr <= lim_y) && (yr >= -lim_y);
+    f.tx = f.z * fminf(lim_x, fmaxf(-lim_x, xr));
+    f.ty = f.z * fminf(lim_y, fmaxf(-lim_y, yr));
+    f.J00 = cam.fx * f.rz;
+    f.J11 = cam.fy * f.rz;
+    f.J02 = -cam.fx * f.tx * f.rz2;
+    f.J12 = -cam.fy * f.ty * f.rz2;
+    // Q = J cc, cov2d = Q J^T
+    q0[0] = f.J00 * cc[0] + f.J02 * cc[2];
+    q0[1] = f.J00 * cc[1] + f.J02 * cc[4];
+    q0[2] = f.J00 * cc[2] + f.J02 * cc[5];
+    q1[0] = f.J11 * cc[1] + f.J12 * cc[2];
+    q1[1] = f.J11 * cc[3] + f.J12 * cc[4];
+    q1[2] = f.J11 * cc[4] + f.J12 * cc[5];
+    f.c00 = q0[0] * f.J00 + q0[2] * f.J02;
+    f.c01 = q0[1] * f.J11 + q0[2] * f.J12;
+    f.c11 = q1[1] * f.J11 + q1[2] * f.J12;
+    f.u = cam.fx * f.x * f.rz + cam.cx;
+    f.v = cam.fy * f.y * f.rz + cam.cy;
+  }
 
   f.det0 = f.c00 * f.c11 - f.c01 * f.c01;
   f.b00 = f.c00 + eps2d;
@@ -254,7 +295,9 @@ struct Grads {
 // v_cam[12] -- rows of [v_R | v_tr], v_R[i][j] = v_t[i] mean[j] + sum_k vW[3 i + k] M[j][k] with M = Rq diag(s) (the
 // transpose-side product of W = Rv M), v_tr = v_t -- from the world mean `mean`; `o` is not touched.  The default
 // instantiation is the function every other kernel inlines, instruction for instruction.
-template <bool CAM = false>
+// CM = kOrtho: v_P reaches W through the first two rows only, the camera-space mean receives (fx v_u, fy v_v, v_depth)
+// and nothing through J (it is constant); the chain from vW and (vtx, vty, vtz) on is the shared one.
+template <bool CAM = false, int CM = kPinhole>
 __device__ __forceinline__ void backward_geom(const Cam &cam, const Fwd &f, float eps2d, uint32_t flags,
                                               const float4 ga, const float4 gb, bool ext, float v_comp_ext,
                                               float v_depth_ext, Grads &o, float *v_cam = nullptr,
@@ -293,28 +336,42 @@ __device__ __forceinline__ void backward_geom(const Cam &cam, const Fwd &f, floa
     vp0[k] = 2.f * (G00 * f.p0[k] + G01 * f.p1[k]);
     vp1[k] = 2.f * (G01 * f.p0[k] + G11 * f.p1[k]);
   }
-  // P = J W
-  const float vJ00 = vp0[0] * f.W[0] + vp0[1] * f.W[1] + vp0[2] * f.W[2];
-  const float vJ02 = vp0[0] * f.W[6] + vp0[1] * f.W[7] + vp0[2] * f.W[8];
-  const float vJ11 = vp1[0] * f.W[3] + vp1[1] * f.W[4] + vp1[2] * f.W[5];
-  const float vJ12 = vp1[0] * f.W[6] + vp1[1] * f.W[7] + vp1[2] * f.W[8];
   float vW[9];
+  float vtx, vty, vtz;
+  if constexpr (CM == kOrtho) {
+    // P = J W with the constant J = [[fx, 0, 0], [0, fy, 0]]; camera-space mean: through mean2d and the depth only
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    vW[k] = f.J00 * vp0[k];
-    vW[3 + k] = f.J11 * vp1[k];
-    vW[6 + k] = f.J02 * vp0[k] + f.J12 * vp1[k];
+    for (int k = 0; k < 3; ++k) {
+      vW[k] = f.J00 * vp0[k];
+      vW[3 + k] = f.J11 * vp1[k];
+      vW[6 + k] = 0.f;
+    }
+    vtx = cam.fx * vx;
+    vty = cam.fy * vy;
+    vtz = v_depth_ext;
+  } else {
+    // P = J W
+    const float vJ00 = vp0[0] * f.W[0] + vp0[1] * f.W[1] + vp0[2] * f.W[2];
+    const float vJ02 = vp0[0] * f.W[6] + vp0[1] * f.W[7] + vp0[2] * f.W[8];
+    const float vJ11 = vp1[0] * f.W[3] + vp1[1] * f.W[4] + vp1[2] * f.W[5];
+    const float vJ12 = vp1[0] * f.W[6] + vp1[1] * f.W[7] + vp1[2] * f.W[8];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      vW[k] = f.J00 * vp0[k];
+      vW[3 + k] = f.J11 * vp1[k];
+      vW[6 + k] = f.J02 * vp0[k] + f.J12 * vp1[k];
+    }
+    // camera-space mean: through mean2d and through J (fov clamp freezes tx = +-lim z)
+    const float rz3 = f.rz2 * f.rz;
+    vtx = cam.fx * f.rz * vx;
+    vty = cam.fy * f.rz * vy;
+    vtz = -(cam.fx * f.x * vx + cam.fy * f.y * vy) * f.rz2 + v_depth_ext;
+    vtz += -cam.fx * f.rz2 * vJ00 - cam.fy * f.rz2 * vJ11;
+    if (f.in_x) { vtx += -cam.fx * f.rz2 * vJ02; vtz += 2.f * cam.fx * f.tx * rz3 * vJ02; }
+    else        { vtz += cam.fx * f.tx * rz3 * vJ02; }
+    if (f.in_y) { vty += -cam.fy * f.rz2 * vJ12; vtz += 2.f * cam.fy * f.ty * rz3 * vJ12; }
+    else        { vtz += cam.fy * f.ty * rz3 * vJ12; }
   }
-  // camera-space mean: through mean2d and through J (fov clamp freezes tx = +-lim z)
-  const float rz3 = f.rz2 * f.rz;
-  float vtx = cam.fx * f.rz * vx;
-  float vty = cam.fy * f.rz * vy;
-  float vtz = -(cam.fx * f.x * vx + cam.fy * f.y * vy) * f.rz2 + v_depth_ext;
-  vtz += -cam.fx * f.rz2 * vJ00 - cam.fy * f.rz2 * vJ11;
-  if (f.in_x) { vtx += -cam.fx * f.rz2 * vJ02; vtz += 2.f * cam.fx * f.tx * rz3 * vJ02; }
-  else        { vtz += cam.fx * f.tx * rz3 * vJ02; }
-  if (f.in_y) { vty += -cam.fy * f.rz2 * vJ12; vtz += 2.f * cam.fy * f.ty * rz3 * vJ12; }
-  else        { vtz += cam.fy * f.ty * rz3 * vJ12; }
   if constexpr (CAM) {
     const float vt[3] = {vtx, vty, vtz};
 #pragma unroll

@@ -33,7 +33,8 @@ __device__ __forceinline__ void block_sum12(const float (&v)[12], float (*s_part
   __syncthreads();
 }
 
-template <bool PACKED>
+// CM: the camera model (csrc/project_dev.h), kOrtho with EG_FLAG_ORTHO.
+template <bool PACKED, int CM>
 __global__ void __launch_bounds__(kVg)
 viewmat_partial_kernel(const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
                        const float *__restrict__ opacities, const float *__restrict__ viewmats,
@@ -68,9 +69,9 @@ viewmat_partial_kernel(const float *__restrict__ means, const float *__restrict_
     const Raw raw = load_raw(means, quats, scales, opacities, g);
     const float4 ga = g2d[2 * p], gb = g2d[2 * p + 1];
     Fwd f;
-    forward_geom(cam, raw, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f);
+    forward_geom<CM>(cam, raw, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f);
     Grads unused;
-    backward_geom<true>(cam, f, eps2d, flags, ga, gb, true, v_comps[p], v_depths ? v_depths[p] : 0.f, unused, v, raw.m);
+    backward_geom<true, CM>(cam, f, eps2d, flags, ga, gb, true, v_comps[p], v_depths ? v_depths[p] : 0.f, unused, v, raw.m);
   }
   block_sum12(v, s_part);
   if (threadIdx.x < 12) {
@@ -121,17 +122,19 @@ extern "C" int eg_project_bwd_viewmats(const float *means, const float *quats, c
     EG_REQUIRE(!packed || gaussian_ids, "null pointer");
   }
   hipStream_t s = as_stream(stream);
-  if (B > 0) {
-    if (packed)
-      viewmat_partial_kernel<true><<<dim3(B, C), kVg, 0, s>>>(
-          means, quats, scales, opacities, viewmats, Ks, N, width, height, eps2d, flags, nullptr,
-          (const long long *)indptr, (long long)nnz, (const long long *)gaussian_ids, (const float4 *)g2d, v_comps,
-          v_depths, scratch);
-    else
-      viewmat_partial_kernel<false><<<dim3(B, C), kVg, 0, s>>>(
-          means, quats, scales, opacities, viewmats, Ks, N, width, height, eps2d, flags, (const float4 *)splat, nullptr,
-          0ll, nullptr, (const float4 *)g2d, v_comps, v_depths, scratch);
+#define EG_VIEWMAT_PARTIAL(PACKED_, CM_)                                                                             \
+  viewmat_partial_kernel<PACKED_, CM_><<<dim3(B, C), kVg, 0, s>>>(                                                   \
+      means, quats, scales, opacities, viewmats, Ks, N, width, height, eps2d, flags, (const float4 *)splat,          \
+      (const long long *)indptr, (long long)nnz, (const long long *)gaussian_ids, (const float4 *)g2d, v_comps,      \
+      v_depths, scratch)
+  if (B > 0) {  // (dense: indptr, nnz and gaussian_ids are NULL / 0, checked above; packed: splat is NULL)
+    if (flags & EG_FLAG_ORTHO) {
+      if (packed) EG_VIEWMAT_PARTIAL(true, kOrtho); else EG_VIEWMAT_PARTIAL(false, kOrtho);
+    } else {
+      if (packed) EG_VIEWMAT_PARTIAL(true, kPinhole); else EG_VIEWMAT_PARTIAL(false, kPinhole);
+    }
   }
+#undef EG_VIEWMAT_PARTIAL
   viewmat_fold_kernel<<<C, kVg, 0, s>>>(scratch, B, v_viewmats);
   return check_launch("project_bwd_viewmats");
 }

@@ -1,13 +1,17 @@
 """gsplat 1.0.0's stage-by-stage API over the kernels `rasterization` runs: ``fully_fused_projection``,
-``quat_scale_to_covar_preci``, ``isect_tiles``, ``isect_offset_encode``, ``rasterize_to_pixels``, ``world_to_cam`` and
-``persp_proj``, with gsplat's signatures and return orders.
+``quat_scale_to_covar_preci``, ``isect_tiles``, ``isect_offset_encode``, ``rasterize_to_pixels``, ``world_to_cam``,
+``persp_proj`` and ``proj``, with gsplat's signatures and return orders.
 
 Callers use the stages when they change something between them -- shift ``means2d``, substitute their own conics or
 opacities, render Gaussians that exist only as covariances, re-bin with another tile grid.  The projection from
 ``quats`` + ``scales``, the binning and the compositing are the very kernels behind ``rasterization(packed=False)``;
 the projection from ``covars``, ``quat_scale_to_covar_preci`` and ``isect_offset_encode`` have kernels of their own
-(csrc/functional.hip).  ``world_to_cam`` and ``persp_proj`` are plain differentiable torch expressions (not a hot path;
-they work on CPU tensors too).  Everything else needs device tensors: there is no CPU path.
+(csrc/functional.hip).  ``world_to_cam``, ``persp_proj`` and ``proj`` are plain differentiable torch expressions (not a
+hot path; they work on CPU tensors too).  Everything else needs device tensors: there is no CPU path.
+
+``fully_fused_projection`` and ``proj`` take gsplat's ``camera_model``: "pinhole" (the default) or "ortho" (the
+orthographic camera of ``rasterization(camera_model="ortho")``, in both forms of the projection); "fisheye" is a
+NotImplementedError, anything else a ValueError.
 
 Not supported, each a NotImplementedError: ``packed=True`` (use ``rasterization(packed=True)``), ``sparse_grad=True``,
 ``sort=False``, ``masks``, and a ``viewmats`` that requires grad together with ``covars``."""
@@ -22,10 +26,11 @@ from torch import Tensor
 
 from . import rasterizer as _R
 from ._lib import call, ptr, stream
-from .rasterizer import TILE, TILE_SIZES, _check
+from . import _lib
+from .rasterizer import TILE, TILE_SIZES, _check, _is_ortho
 
 __all__ = ["fully_fused_projection", "quat_scale_to_covar_preci", "isect_tiles", "isect_offset_encode",
-           "rasterize_to_pixels", "world_to_cam", "persp_proj"]
+           "rasterize_to_pixels", "world_to_cam", "persp_proj", "proj"]
 
 
 def _no_packed(packed, what):
@@ -90,10 +95,12 @@ def quat_scale_to_covar_preci(quats: Tensor, scales: Tensor, compute_covar: bool
 # ----------------------------------------------------------------------------------------------------------------
 class _CovarProjection(torch.autograd.Function):
     """gsplat ``fully_fused_projection`` from covariances (packed=False) for C cameras: eg_project_covars_fwd_cams /
-    eg_project_covars_bwd_cams.  The backward sums over the cameras in camera order without atomics."""
+    eg_project_covars_bwd_cams.  The backward sums over the cameras in camera order without atomics.  `ortho`: the
+    orthographic instantiations, through eg_project_covars_{fwd,bwd}_cams_flags with EG_FLAG_ORTHO."""
 
     @staticmethod
-    def forward(ctx, means, covars, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip, calc_comp):
+    def forward(ctx, means, covars, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip, calc_comp,
+                ortho=False):
         Cn, N = viewmats.shape[0], means.shape[0]
         dev = means.device
         m, cv, vm, Kc = means.contiguous(), covars.contiguous(), viewmats.contiguous(), Ks.contiguous()
@@ -102,18 +109,21 @@ class _CovarProjection(torch.autograd.Function):
         depths = torch.empty(Cn, N, device=dev)
         conics = torch.empty(Cn, N, 3, device=dev)
         comps = torch.empty(Cn, N, device=dev) if calc_comp else torch.empty(0, device=dev)
-        call("eg_project_covars_fwd_cams", ptr(m), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane, far_plane,
-             eps2d, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps) if calc_comp else None,
-             stream())
+        args = (ptr(m), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane, far_plane, eps2d, radius_clip,
+                ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps) if calc_comp else None)
+        if ortho:
+            call("eg_project_covars_fwd_cams_flags", *args, _lib.FLAG_ORTHO, stream())
+        else:
+            call("eg_project_covars_fwd_cams", *args, stream())
         ctx.save_for_backward(m, cv, vm, Kc, radii)
-        ctx.cfg = (width, height, eps2d, calc_comp)
+        ctx.cfg = (width, height, eps2d, calc_comp, bool(ortho))
         ctx.mark_non_differentiable(*((radii,) if calc_comp else (radii, comps)))
         return radii, means2d, depths, conics, comps
 
     @staticmethod
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps):
         m, cv, vm, Kc, radii = ctx.saved_tensors
-        width, height, eps2d, calc_comp = ctx.cfg
+        width, height, eps2d, calc_comp, ortho = ctx.cfg
         Cn, N = vm.shape[0], m.shape[0]
         dev = m.device
         vm2d = v_means2d.contiguous() if v_means2d is not None else torch.zeros(Cn, N, 2, device=dev)
@@ -122,22 +132,31 @@ class _CovarProjection(torch.autograd.Function):
         vcomp = v_comps.contiguous() if (calc_comp and v_comps is not None) else None
         v_means = torch.empty(N, 3, device=dev)
         v_covars = torch.empty(N, 6, device=dev)
-        call("eg_project_covars_bwd_cams", ptr(m), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, ptr(radii),
-             ptr(vm2d), ptr(vdep), ptr(vcon), ptr(vcomp), ptr(v_means), ptr(v_covars), stream())
-        return (v_means, v_covars) + (None,) * 9
+        args = (ptr(m), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, ptr(radii), ptr(vm2d), ptr(vdep), ptr(vcon),
+                ptr(vcomp), ptr(v_means), ptr(v_covars))
+        if ortho:
+            call("eg_project_covars_bwd_cams_flags", *args, _lib.FLAG_ORTHO, stream())
+        else:
+            call("eg_project_covars_bwd_cams", *args, stream())
+        return (v_means, v_covars) + (None,) * 10
 
 
 def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Optional[Tensor], scales: Optional[Tensor],
                            viewmats: Tensor, Ks: Tensor, width: int, height: int, eps2d: float = 0.3,
                            near_plane: float = 0.01, far_plane: float = 1e10, radius_clip: float = 0.0,
-                           packed: bool = False, sparse_grad: bool = False, calc_compensations: bool = False):
+                           packed: bool = False, sparse_grad: bool = False, calc_compensations: bool = False,
+                           camera_model: str = "pinhole"):
     """gsplat ``fully_fused_projection`` (packed=False): ``(radii [C,N] int32, means2d [C,N,2], depths [C,N], conics
     [C,N,3], compensations [C,N] | None)``; a culled pair has radius 0 and zeros in every float output.
 
     Exactly one of ``covars`` [N,6] (upper triangle) and ``quats`` [N,4] + ``scales`` [N,3] must be given (ValueError).
     With ``quats`` + ``scales`` this is the projection node of ``rasterization`` -- the same kernels, the same bits, and
     ``viewmats`` receives its gradient when it requires one.  With ``covars`` a kernel pair of its own; ``viewmats``
-    must not require grad there (NotImplementedError)."""
+    must not require grad there (NotImplementedError).
+
+    ``camera_model``: "pinhole" or "ortho" (``means2d = (fx x + cx, fy y + cy)``, the constant Jacobian ``[[fx, 0, 0],
+    [0, fy, 0]]``, no fov clamp; see ``rasterization``), in both forms; checked before any tensor is looked at."""
+    ortho = _is_ortho(camera_model)
     _no_packed(packed, "fully_fused_projection")
     if sparse_grad:
         raise NotImplementedError("fully_fused_projection: sparse_grad=True needs packed=True; use rasterization(packed=True, sparse_grad=True)")
@@ -155,13 +174,13 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Optio
         _check(scales, (N, 3), "scales")
         dummy = torch.ones(N, device=means.device)  # (the record's opacity: nobody reads the record here)
         radii, means2d, depths, conics, comps = _R._Projection.apply(
-            means, quats, scales, dummy, viewmats, Ks, width, height, *cfg, bool(calc_compensations))[:5]
+            means, quats, scales, dummy, viewmats, Ks, width, height, *cfg, bool(calc_compensations), TILE, ortho)[:5]
         return radii, means2d, depths, conics, (comps if calc_compensations else None)
     _check(covars, (N, 6), "covars")
     if viewmats.requires_grad and torch.is_grad_enabled():
         raise NotImplementedError("fully_fused_projection: the gradient of viewmats is not available with covars; pass quats and scales")
     radii, means2d, depths, conics, comps = _CovarProjection.apply(
-        means, covars, viewmats, Ks, width, height, *cfg, bool(calc_compensations))
+        means, covars, viewmats, Ks, width, height, *cfg, bool(calc_compensations), ortho)
     return radii, means2d, depths, conics, (comps if calc_compensations else None)
 
 
@@ -332,4 +351,21 @@ def persp_proj(means: Tensor, covars: Tensor, Ks: Tensor, width: int, height: in
     J = torch.stack([fx * rz, zero, -fx * cxz * rz * rz, zero, fy * rz, -fy * cyz * rz * rz], dim=-1).reshape(means.shape[:-1] + (2, 3))
     covars2d = J @ covars @ J.transpose(-1, -2)
     means2d = torch.stack([fx * tx * rz + cx, fy * ty * rz + cy], dim=-1)
+    return means2d, covars2d
+
+
+def proj(means: Tensor, covars: Tensor, Ks: Tensor, width: int, height: int,
+         camera_model: str = "pinhole") -> Tuple[Tensor, Tensor]:
+    """gsplat ``proj`` (1.4): camera-space ``means`` [C,N,3] and ``covars`` [C,N,3,3], ``Ks`` [C,3,3] -> ``(means2d
+    [C,N,2], covars2d [C,N,2,2])`` under ``camera_model``.  "pinhole" is ``persp_proj``.  "ortho": ``means2d = (fx x +
+    cx, fy y + cy)`` and ``covars2d = J covars J^T`` with the constant ``J = [[fx, 0, 0], [0, fy, 0]]`` (``width`` and
+    ``height`` play no part), WITHOUT eps2d on the diagonal.  Plain torch, any device."""
+    if not _is_ortho(camera_model):
+        return persp_proj(means, covars, Ks, width, height)
+    fx, fy = Ks[:, 0, 0, None], Ks[:, 1, 1, None]
+    cx, cy = Ks[:, 0, 2, None], Ks[:, 1, 2, None]
+    tx, ty, _tz = means.unbind(-1)
+    f = torch.stack([fx, fy], dim=-1)  # [C,1,2]: J scales rows / columns 0 and 1, and drops the third
+    covars2d = covars[..., :2, :2] * f[..., :, None] * f[..., None, :]
+    means2d = torch.stack([fx * tx + cx, fy * ty + cy], dim=-1)
     return means2d, covars2d

@@ -33,6 +33,19 @@ import os as _os
 _FAST_ENABLED = bool(int(_os.environ.get("EG_OPERATOR_FAST", "1")))
 
 
+CAMERA_MODELS = ("pinhole", "ortho")
+
+
+def _is_ortho(camera_model) -> bool:
+    """Checks gsplat's ``camera_model`` ("pinhole" | "ortho"; "fisheye": NotImplementedError, anything else:
+    ValueError) before any tensor is looked at; True for "ortho"."""
+    if camera_model == "fisheye":
+        raise NotImplementedError('camera_model="fisheye" is not available; "pinhole" and "ortho" are')
+    if not isinstance(camera_model, str) or camera_model not in CAMERA_MODELS:
+        raise ValueError(f"Unknown camera_model: {camera_model}")
+    return camera_model == "ortho"
+
+
 def _check(t: Tensor, shape, name: str, dtype=torch.float32):
     if not t.is_cuda:
         raise ValueError(f"{name} must be a device tensor (got {t.device}); edgegaussians_amd has no CPU path")
@@ -44,11 +57,12 @@ def _check(t: Tensor, shape, name: str, dtype=torch.float32):
 
 class _Projection(torch.autograd.Function):
     """gsplat ``fully_fused_projection`` (packed=False) for C cameras, tile counting fused in (tile_size 16; any other
-    tile size: the projection without its counting, then eg_tile_count_ts)."""
+    tile size: the projection without its counting, then eg_tile_count_ts).  `ortho`: EG_FLAG_ORTHO, the orthographic
+    instantiations of the same kernels, forward and backward."""
 
     @staticmethod
     def forward(ctx, means, quats, scales, opac_for_splat, viewmats, Ks, width, height, eps2d,
-                near_plane, far_plane, radius_clip, antialiased, tile_size=TILE):
+                near_plane, far_plane, radius_clip, antialiased, tile_size=TILE, ortho=False):
         Cn, N = viewmats.shape[0], means.shape[0]
         dev = means.device
         tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
@@ -63,7 +77,7 @@ class _Projection(torch.autograd.Function):
         comps = torch.empty(Cn, N, device=dev)
         tpg = torch.empty(Cn, N, dtype=torch.int32, device=dev)
         counts = torch.zeros(Cn, tw * th, dtype=torch.int32, device=dev)
-        flags = _lib.FLAG_ANTIALIASED if antialiased else 0
+        flags = (_lib.FLAG_ANTIALIASED if antialiased else 0) | (_lib.FLAG_ORTHO if ortho else 0)
         # (round 6: the C cameras by ONE native call -- csrc/cams.hip loops over the per-camera launcher)
         fused = tile_size == TILE  # (the counting fused into the projection kernel is the 16-pixel one)
         call("eg_project_fwd_cams", ptr(means_c), ptr(quats_c), ptr(scales_c), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height,
@@ -113,7 +127,7 @@ class _Projection(torch.autograd.Function):
                 call("eg_project_bwd_viewmats", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width,
                      height, eps2d, flags, ptr(splat), None, 0, None, ptr(g2d), ptr(vcomp), ptr(vdep), ptr(scratch), blocks,
                      ptr(v_viewmats), stream())
-        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 9
+        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 10
 
 
 _DUMMY: Dict = {}
@@ -138,18 +152,19 @@ class _PackedProjection(torch.autograd.Function):
     [N, k] gradients, summed over the cameras in camera order, no atomics) or, with `sparse_grad`, eg_packed_bwd_sparse
     (sparse COO gradients of size [N, k] with indices gaussian_ids[None] and values [nnz, k], coalesced iff C == 1).
     `holder` receives the host copy of indptr.  A `tile_size` other than 16: eg_packed_write counts 16-pixel tiles into
-    a throw-away buffer, and eg_tile_count_ts counts the pairs' tiles of the asked size."""
+    a throw-away buffer, and eg_tile_count_ts counts the pairs' tiles of the asked size.  `ortho`: EG_FLAG_ORTHO in every
+    call, forward and backward."""
 
     @staticmethod
     def forward(ctx, means, quats, scales, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-                radius_clip, antialiased, sparse_grad, holder, tile_size=TILE):
+                radius_clip, antialiased, sparse_grad, holder, tile_size=TILE, ortho=False):
         Cn, N = viewmats.shape[0], means.shape[0]
         dev = means.device
         tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
         means_c, quats_c, scales_c = means.contiguous(), quats.contiguous(), scales.contiguous()
         opac_c = opac_for_splat.contiguous()
         vm, Kc = viewmats.contiguous(), Ks.contiguous()
-        flags = _lib.FLAG_ANTIALIASED if antialiased else 0
+        flags = (_lib.FLAG_ANTIALIASED if antialiased else 0) | (_lib.FLAG_ORTHO if ortho else 0)
         # the only scratch: one int32 per workgroup of 256 pairs
         block_base = torch.empty(Cn * math.ceil(N / 256), dtype=torch.int32, device=dev)
         indptr = torch.empty(Cn + 1, dtype=torch.int64, device=dev)
@@ -223,7 +238,7 @@ class _PackedProjection(torch.autograd.Function):
             call("eg_project_bwd_viewmats", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width,
                  height, eps2d, flags, None, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d),
                  ptr(vcomp), ptr(vdep), ptr(scratch), blocks, ptr(v_viewmats), stream())
-        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 11
+        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 12
 
 
 class _Compositing(torch.autograd.Function):
@@ -941,20 +956,21 @@ RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
 
 def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
                         radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree=None, chunk=None,
-                        tile_size=TILE):
+                        tile_size=TILE, ortho=False):
     """`rasterization` with a depth channel and / or backgrounds: the general two-node path (projection -> compositing)
     with the compositing of eg_composite_{fwd,bwd}_modes_cams, which takes `depths` as an input.  With `sh_degree`,
     `colors` holds the coefficients and the colours are evaluated behind the projection (its radii are their mask).
     With `chunk` (colours of a channel count other than 1 or 3, in any mode that renders them): the same projection,
     binning and sort, then the compositing of eg_composite_{fwd,bwd}_wide_cams in chunks of `chunk` channels.
-    With a `tile_size` of 8 or 32 (always with `chunk`): counting, emission and compositing by csrc/tiles.hip."""
+    With a `tile_size` of 8 or 32 (always with `chunk`): counting, emission and compositing by csrc/tiles.hip.
+    `ortho`: the orthographic projection; everything behind the projection is the same."""
     N, Cn = means.shape[0], viewmats.shape[0]
     depth = render_mode != "RGB"
     if render_mode in ("D", "ED"):
         colors, backgrounds = None, None  # (gsplat: the depth is the only channel, its background is 0)
     radii, means2d, depths, conics, comps, tpg, counts, _splat = _Projection.apply(
         means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
-        float(near_plane), float(far_plane), float(radius_clip), antialiased, tile_size)
+        float(near_plane), float(far_plane), float(radius_clip), antialiased, tile_size, ortho)
     if sh_degree is not None and colors is not None:
         colors = _sh.view_colors(means, viewmats, colors, radii, sh_degree)
     opac = opacities[None, :].expand(Cn, N)
@@ -1009,7 +1025,7 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
 
 def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
                           radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree, chunk,
-                          sparse_grad, tile_size=TILE):
+                          sparse_grad, tile_size=TILE, ortho=False):
     """`rasterization(packed=True)`: the packed projection (_PackedProjection), the colours / opacities gathered per pair
     in torch (dense gradients of the caller's shapes, as in gsplat), every camera's range binned as a single-camera
     problem (eg_packed_bin), and the mode / wide compositing kernels on the packed records (record stride
@@ -1023,7 +1039,7 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
     holder: Dict = {}
     radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids = _PackedProjection.apply(
         means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
-        float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder, tile_size)
+        float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder, tile_size, ortho)
     indptr = holder["indptr"]
     nnz = indptr[-1]
     if colors is not None:
@@ -1102,6 +1118,7 @@ def rasterization(
     sh_degree: Optional[int] = None, packed: bool = True, tile_size: int = 16,
     backgrounds: Optional[Tensor] = None, render_mode: str = "RGB", sparse_grad: bool = False,
     absgrad: bool = False, rasterize_mode: str = "classic", channel_chunk: int = 32,
+    camera_model: str = "pinhole",
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``, for tile_size 8, 16 or 32 and
     colours of any channel count D >= 1 (the reference's call, edge_gs.py:250-268, is packed=False, render_mode='RGB'
@@ -1165,7 +1182,20 @@ def rasterization(
     the "ED" modes divide that channel by ``alphas.clamp(min=1e-10)``.  ``backgrounds`` [C,D] (fp32, on the device)
     is added under the final transmittance of the colour channels (the depth channel's background is 0; the depth-only
     modes ignore it) and receives a gradient when it requires one.  The depth channel's gradient reaches ``means``,
-    ``quats`` and ``scales`` through ``info["depths"]``."""
+    ``quats`` and ``scales`` through ``info["depths"]``.
+
+    ``camera_model`` (gsplat >= 1.4; appended last, so positional calls written for 1.0.0 keep their meaning):
+    "pinhole" (the default: everything above, bit for bit) or "ortho"; "fisheye" is a NotImplementedError, anything
+    else a ValueError, both raised before any tensor is looked at.  "ortho" is the orthographic camera: with (x, y, z)
+    the camera-space mean, ``means2d = (fx x + cx, fy y + cy)`` without a division by z, the projection Jacobian is the
+    constant ``[[fx, 0, 0], [0, fy, 0]]`` (no fov clamp), so ``Ks`` is in pixels per world unit; the near / far culls
+    act on z, the depth is z, and everything behind the 2-D covariance (``eps2d``, the compensation, conics, radii,
+    ``radius_clip``, the off-screen cull, binning, compositing) is unchanged.  It works with every combination
+    described above -- ``packed``, ``sparse_grad``, every ``render_mode``, ``backgrounds``, ``sh_degree`` (the view
+    directions stay ``means - campos``, as in gsplat), any D, ``rasterize_mode``, ``absgrad``, the cull arguments,
+    ``tile_size`` 8 / 16 / 32 and the ``viewmats`` gradient -- through orthographic instantiations of the projection
+    kernels (EG_FLAG_ORTHO); an "ortho" call never takes the unit-colour fast path."""
+    ortho = _is_ortho(camera_model)
     if isinstance(tile_size, bool) or tile_size not in TILE_SIZES:
         raise NotImplementedError(f"tile_size must be 8, 16 or 32, got {tile_size!r} (the reference passes 16, edge_gs.py:232)")
     tile_size = int(tile_size)
@@ -1205,20 +1235,21 @@ def rasterization(
         return _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                      far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
                                      sh_degree, min(channel_chunk, 32) if (wide or tile_size != TILE) else None,
-                                     sparse_grad, tile_size)
+                                     sparse_grad, tile_size, ortho)
     if tile_size != TILE:  # (every channel count and mode: one kernel family, csrc/tiles.hip; never the fast path)
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                    far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
-                                   sh_degree, min(channel_chunk, 32), tile_size)
+                                   sh_degree, min(channel_chunk, 32), tile_size, ortho)
     if D not in (1, 3) and render_mode not in ("D", "ED"):  # (the depth-only modes do not read the colours)
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                    far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
-                                   chunk=min(channel_chunk, 32))
+                                   chunk=min(channel_chunk, 32), ortho=ortho)
     if render_mode != "RGB" or backgrounds is not None:
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
-                                   far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree)
+                                   far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree,
+                                   ortho=ortho)
 
-    if (sh_degree is None and Cn == 1 and colors.dim() == 2 and not colors.requires_grad and float(eps2d) == 0.3 and float(near_plane) == 0.01
+    if (not ortho and sh_degree is None and Cn == 1 and colors.dim() == 2 and not colors.requires_grad and float(eps2d) == 0.3 and float(near_plane) == 0.01
             and float(far_plane) == 1e10 and float(radius_clip) == 0.0 and N > 0 and _FAST_ENABLED and not viewmats.requires_grad):
         # the reference's own call (edge_gs.py:247-268): colours torch.ones(N, 3) without grad, one camera (and a fixed
         # one: the fast path's single node has no pose gradient, a camera that requires grad takes the general path)
@@ -1228,7 +1259,7 @@ def rasterization(
 
     radii, means2d, depths, conics, comps, tpg, counts, _splat = _Projection.apply(
         means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
-        float(near_plane), float(far_plane), float(radius_clip), antialiased)
+        float(near_plane), float(far_plane), float(radius_clip), antialiased, TILE, ortho)
     if sh_degree is not None:
         colors = _sh.view_colors(means, viewmats, colors, radii, sh_degree)
     opac = opacities[None, :].expand(Cn, N)

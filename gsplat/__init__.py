@@ -5,18 +5,20 @@ The reference imports ``rasterization`` alone; ``spherical_harmonics`` is there 
 ``rasterization(..., sh_degree=L)`` calls it serves as well.  ``rasterization`` takes gsplat's defaults, ``packed=True``
 included (only the visible (camera, Gaussian) pairs are kept; ``info["camera_ids"]`` / ``info["gaussian_ids"]`` name
 them), and ``sparse_grad=True`` on top of it; ``viewmats`` that require grad receive their ``[C, 4, 4]`` gradient (pose
-optimisation); ``tile_size`` may be 8, 16 or 32 (16 is the reference's).
+optimisation); ``tile_size`` may be 8, 16 or 32 (16 is the reference's); ``camera_model`` (gsplat 1.4's argument, appended
+last) may be "pinhole" or "ortho" (the orthographic camera of CAD views).
 
 The stage-by-stage API -- ``fully_fused_projection`` (from ``quats`` + ``scales`` or from ``covars``),
 ``quat_scale_to_covar_preci``, ``isect_tiles``, ``isect_offset_encode``, ``rasterize_to_pixels``, ``world_to_cam``,
-``persp_proj`` -- is edgegaussians_amd/functional.py: the same kernels, for callers that change something between the
-stages (``packed=False`` only; see that module for the unsupported corners)."""
+``persp_proj``, ``proj`` -- is edgegaussians_amd/functional.py: the same kernels, for callers that change something between
+the stages (``packed=False`` only; see that module for the unsupported corners); ``fully_fused_projection`` and ``proj``
+take ``camera_model`` as well."""
 from edgegaussians_amd.rasterizer import rasterization  # noqa: F401
 from edgegaussians_amd.sh import spherical_harmonics  # noqa: F401
 from edgegaussians_amd.functional import (  # noqa: F401
-    fully_fused_projection, isect_offset_encode, isect_tiles, persp_proj, quat_scale_to_covar_preci, rasterize_to_pixels,
-    world_to_cam)
+    fully_fused_projection, isect_offset_encode, isect_tiles, persp_proj, proj, quat_scale_to_covar_preci,
+    rasterize_to_pixels, world_to_cam)
 
 __version__ = "1.0.0+edgegaussians_amd"
 __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "quat_scale_to_covar_preci", "isect_tiles",
-           "isect_offset_encode", "rasterize_to_pixels", "world_to_cam", "persp_proj"]
+           "isect_offset_encode", "rasterize_to_pixels", "world_to_cam", "persp_proj", "proj"]

@@ -58,6 +58,12 @@ typedef void *eg_stream_t; /* hipStream_t */
                                       grids above 2560 tiles: the sort kernel then writes the item records front slices first) */
 #define EG_FLAG_GRAD_ACCUM 64u       /* eg_project_bwd: v_means / v_quats / v_scales / v_opacities += instead of = (the sum over the \
                                       cameras of eg_project_bwd_cams) */
+#define EG_FLAG_ORTHO 128u           /* orthographic camera (gsplat camera_model="ortho") on the operator path -- eg_project_fwd /       \
+                                      _bwd and their _cams forms, eg_project_bwd_viewmats, eg_packed_count / _write / _bwd /        \
+                                      _bwd_sparse, eg_project_covars_{fwd,bwd}_cams_flags: mean2d = (fx x + cx, fy y + cy), J =      \
+                                      [[fx, 0, 0], [0, fy, 0]] (no division by z, no fov clamp; Ks in pixels per world unit), culls,  \
+                                      depth = z and everything behind cov2d as under the pinhole.  The same bit goes to the forward   \
+                                      and its backward.  Every other entry that takes caller flags refuses it with EG_ERR_ARG */
 #define EG_FRONT_LARGE 9
 #define EG_FLAG_TIGHT_TILES 8u     /* bin with the opacity-aware tile box (subset of gsplat's box that \
                                       drops only (Gaussian, tile) pairs contributing exactly nothing) */
@@ -939,6 +945,18 @@ int eg_project_covars_bwd_cams(const float *means, const float *covars, const fl
                                const float *v_means2d, const float *v_depths /*NULL ok*/, const float *v_conics,
                                const float *v_compensations /*NULL ok*/, float *v_means, float *v_covars,
                                eg_stream_t stream);
+/* The same pair with a camera model: flags = 0 (pinhole: the kernels and bits of the pair above) or EG_FLAG_ORTHO; any
+ * other bit is refused.  Arguments, culls, layouts and NULL rules as above. */
+int eg_project_covars_fwd_cams_flags(const float *means, const float *covars, const float *viewmats, const float *Ks,
+                                     int32_t N, int32_t C, int32_t width, int32_t height, float near_plane,
+                                     float far_plane, float eps2d, float radius_clip, int32_t *radii, float *means2d,
+                                     float *depths, float *conics, float *compensations /*NULL ok*/, uint32_t flags,
+                                     eg_stream_t stream);
+int eg_project_covars_bwd_cams_flags(const float *means, const float *covars, const float *viewmats, const float *Ks,
+                                     int32_t N, int32_t C, int32_t width, int32_t height, float eps2d,
+                                     const int32_t *radii, const float *v_means2d, const float *v_depths /*NULL ok*/,
+                                     const float *v_conics, const float *v_compensations /*NULL ok*/, float *v_means,
+                                     float *v_covars, uint32_t flags, eg_stream_t stream);
 /* gsplat isect_offset_encode on a caller's SORTED isect ids [M] (camera << (32 + tile_bits) | tile << 32 | depth bits,
  * tile_bits = floor(log2(T)) + 1, T = tile_width * tile_height): offsets [C, T] int32, offsets[c, t] = number of
  * entries whose (camera, tile) is below (c, t).  M == 0 (isect_ids may be NULL): all zeros.  No host read-back. */
