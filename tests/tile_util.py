@@ -67,39 +67,16 @@ def borderline_pixels_ts(sc, view, ts, antialiased, rel_alpha=REL_ALPHA, rel_T=R
     (relative) of 1/255 or of 0.999, or takes the running T within `rel_T` of 1e-4; number of pixels that reach the
     transmittance stop; the tiles' list lengths [T])."""
     from oracle import ref_torch as O
+    from tests.composite_util import borderline_walk
     W, H = sc.width, sc.height
     tw, th = math.ceil(W / ts), math.ceil(H / ts)
     radii, m2d, depths, conics, comp = _project(sc, view)
     op = torch.sigmoid(sc.logit_opacities).squeeze(-1)
-    op = (op * comp if antialiased else op).numpy().astype(np.float64)
+    op = (op * comp if antialiased else op).numpy()
     _tpg, ids, flat = O.isect_tiles(m2d.numpy(), radii.numpy(), depths.numpy(), ts, tw, th)
     offs = np.concatenate([O.isect_offset_encode(ids, tw, th).reshape(-1).astype(np.int64), [flat.shape[0]]])
-    m, con = m2d.numpy().astype(np.float64), conics.numpy().astype(np.float64)
-    amin, amax, tstop = 1.0 / 255.0, 0.999, 1e-4
-    mask = np.zeros((H, W), bool)
-    stopped = 0
-    for t in range(tw * th):
-        g = flat[offs[t]:offs[t + 1]]
-        if g.size == 0:
-            continue
-        ty, tx = divmod(t, tw)
-        ii, jj = np.meshgrid(np.arange(ty * ts, min(ty * ts + ts, H)), np.arange(tx * ts, min(tx * ts + ts, W)), indexing="ij")
-        dx = m[g, 0][None, :] - (jj.reshape(-1, 1) + 0.5)
-        dy = m[g, 1][None, :] - (ii.reshape(-1, 1) + 0.5)
-        sigma = 0.5 * (con[g, 0] * dx * dx + con[g, 2] * dy * dy) + con[g, 1] * dx * dy
-        araw = op[g][None, :] * np.exp(-sigma)
-        alpha = np.minimum(amax, araw)
-        incl = (sigma >= 0.0) & (alpha >= amin)
-        T_after = np.cumprod(np.where(incl, 1.0 - alpha, 1.0), axis=1)
-        stops = incl & (T_after <= tstop)
-        has_stop = stops.any(axis=1)
-        first = np.where(has_stop, stops.argmax(axis=1), g.size)
-        looked = np.arange(g.size)[None, :] <= first[:, None]
-        near_a = (np.abs(araw - amin) <= rel_alpha * amin) | (np.abs(araw - amax) <= rel_alpha * amax)
-        near_T = incl & (np.abs(T_after - tstop) <= rel_T * tstop)
-        mask[ii.reshape(-1), jj.reshape(-1)] = (looked & (near_a | near_T)).any(axis=1)
-        stopped += int(has_stop.sum())
-    return torch.from_numpy(mask), stopped, np.diff(offs)
+    walk = borderline_walk(m2d.numpy(), conics.numpy(), op, flat, offs, ts, W, H, None, rel_alpha, rel_T)
+    return walk.mask, walk.stopped, walk.lens
 
 
 @functools.lru_cache(maxsize=None)
