@@ -167,6 +167,10 @@ _SIGS = {
     "eg_project_covars_fwd_cams_flags": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _f, _f, _f] + [_vp] * 5 + [_u32, _vp],
     "eg_project_covars_bwd_cams_flags": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f] + [_vp] * 7 + [_u32, _vp],
     "eg_isect_offset_encode": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "eg_indices_count": [_i32, _i32] + [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "eg_indices_write": [_i32, _i32] + [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp],
+    "eg_accumulate_fwd": [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp],
+    "eg_accumulate_bwd": [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp],
     "eg_train_step_batched": [C.POINTER(StepArgs), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp],
 }
 EXPORTS = sorted(list(_SIGS) + ["eg_last_error_string", "eg_version", "eg_device_count",

@@ -1,13 +1,17 @@
 """gsplat 1.0.0's stage-by-stage API over the kernels `rasterization` runs: ``fully_fused_projection``,
-``quat_scale_to_covar_preci``, ``isect_tiles``, ``isect_offset_encode``, ``rasterize_to_pixels``, ``world_to_cam``,
-``persp_proj`` and ``proj``, with gsplat's signatures and return orders.
+``quat_scale_to_covar_preci``, ``isect_tiles``, ``isect_offset_encode``, ``rasterize_to_pixels``,
+``rasterize_to_indices_in_range``, ``accumulate``, ``world_to_cam``, ``persp_proj`` and ``proj``, with gsplat's signatures and
+return orders.
 
 Callers use the stages when they change something between them -- shift ``means2d``, substitute their own conics or
 opacities, render Gaussians that exist only as covariances, re-bin with another tile grid.  The projection from
 ``quats`` + ``scales``, the binning and the compositing are the very kernels behind ``rasterization(packed=False)``;
 the projection from ``covars``, ``quat_scale_to_covar_preci`` and ``isect_offset_encode`` have kernels of their own
-(csrc/functional.hip).  ``world_to_cam``, ``persp_proj`` and ``proj`` are plain differentiable torch expressions (not a
-hot path; they work on CPU tensors too).  Everything else needs device tensors: there is no CPU path.
+(csrc/functional.hip), and so have the per-pixel intersection lists -- ``rasterize_to_indices_in_range``, which walks a
+range of every tile's list exactly as the compositing does and returns the (pixel, Gaussian) pairs it takes, and
+``accumulate``, which composites such pairs (csrc/indices.hip).  ``world_to_cam``, ``persp_proj`` and ``proj`` are plain
+differentiable torch expressions (not a hot path; they work on CPU tensors too).  Everything else needs device
+tensors: there is no CPU path.
 
 ``fully_fused_projection`` and ``proj`` take gsplat's ``camera_model``: "pinhole" (the default) or "ortho" (the
 orthographic camera of ``rasterization(camera_model="ortho")``, in both forms of the projection); "fisheye" is a
@@ -30,7 +34,7 @@ from . import _lib
 from .rasterizer import TILE, TILE_SIZES, _check, _is_ortho
 
 __all__ = ["fully_fused_projection", "quat_scale_to_covar_preci", "isect_tiles", "isect_offset_encode",
-           "rasterize_to_pixels", "world_to_cam", "persp_proj", "proj"]
+           "rasterize_to_pixels", "rasterize_to_indices_in_range", "accumulate", "world_to_cam", "persp_proj", "proj"]
 
 
 def _no_packed(packed, what):
@@ -322,6 +326,192 @@ def rasterize_to_pixels(means2d: Tensor, conics: Tensor, colors: Tensor, opaciti
                                                   tuple(glob[c] for c in range(Cn)), (flat,) * Cn, bool(absgrad), False,
                                                   (None,) * Cn, (None,) * Cn, (0,) * Cn, splat)
     return render, alphas
+
+
+# ----------------------------------------------------------------------------------------------------------------
+_RANGE_MAX = 2 ** 31 - 1  # (more batches than any int32-indexed list has)
+
+
+def _clamp_range(range_start, range_end):
+    """The batch range as the entries take it (int32): negative bounds are a ValueError, huge ones are clamped."""
+    rs, re = int(range_start), int(range_end)
+    if rs < 0 or re < 0:
+        raise ValueError(f"range_start and range_end must not be negative, got {range_start!r}, {range_end!r}")
+    return min(rs, _RANGE_MAX), min(re, _RANGE_MAX)
+
+
+@torch.no_grad()
+def rasterize_to_indices_in_range(range_start: int, range_end: int, transmittances: Tensor, means2d: Tensor,
+                                  conics: Tensor, opacities: Tensor, image_width: int, image_height: int,
+                                  tile_size: int, isect_offsets: Tensor, flatten_ids: Tensor
+                                  ) -> Tuple[Tensor, Tensor, Tensor]:
+    """gsplat ``rasterize_to_indices_in_range``: which Gaussians reach which pixel, in depth order.  Returns
+    ``(gaussian_ids [M], pixel_ids [M], camera_ids [M])``, all int64, one row per (pixel, Gaussian) pair the walk of
+    ``rasterize_to_pixels`` composites, in ascending ``(camera, pixel_id = i * W + j)`` order and in list order inside
+    a pixel; ``gaussian_ids = flatten_id % N``.
+
+    ``transmittances`` [C,H,W], ``means2d`` [C,N,2], ``conics`` [C,N,3], ``opacities`` [C,N] fp32; ``isect_offsets``
+    [C,th,tw] int32 and ``flatten_ids`` int32 as ``isect_tiles`` / ``isect_offset_encode`` return them.
+
+    Per call: a tile's sorted list is cut into batches of ``tile_size ** 2`` entries, and the call looks only at the
+    batches ``b`` with ``range_start <= b < range_end`` (``range_end`` may be huge).  Pixel (i, j) of camera c starts
+    with ``T = transmittances[c, i, j]`` and walks those batches of its own tile: centre (j + 0.5, i + 0.5), ``alpha
+    = min(0.999, opacity * exp(-sigma))``, an entry with ``sigma < 0`` or ``alpha < 1/255`` is skipped, the walk stops
+    for the rest of THIS CALL before an entry that would give ``T (1 - alpha) <= 1e-4``, every other entry is recorded
+    and ``T <- T (1 - alpha)``.  The stop is not remembered between calls: a later call with a larger ``range_start``
+    resumes the walk from the ``T`` it is given (as in gsplat), so a caller who slices the list carries ``T`` forward
+    with ``accumulate`` (``T <- T (1 - alphas)``).
+
+    Two passes of one kernel (count, int64 scan, write), no atomics: the same bits every run.  One host read-back
+    (the number of rows)."""
+    tile_size = _tile_size(tile_size)
+    rs, re = _clamp_range(range_start, range_end)
+    if means2d.dim() != 3:
+        raise ValueError(f"means2d must have shape (C, N, 2), got {tuple(means2d.shape)}")
+    Cn, N = means2d.shape[0], means2d.shape[1]
+    width, height = int(image_width), int(image_height)
+    if width < 0 or height < 0:
+        raise ValueError(f"image_width and image_height must not be negative, got {image_width!r}, {image_height!r}")
+    tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
+    T = tw * th
+    _check(transmittances, (Cn, height, width), "transmittances")
+    _check(means2d, (Cn, N, 2), "means2d")
+    _check(conics, (Cn, N, 3), "conics")
+    _check(opacities, (Cn, N), "opacities")
+    _check(isect_offsets, (Cn, th, tw), "isect_offsets", torch.int32)
+    if flatten_ids.dim() != 1:
+        raise ValueError(f"flatten_ids must have shape (M,), got {tuple(flatten_ids.shape)}")
+    M = flatten_ids.shape[0]
+    _check(flatten_ids, (M,), "flatten_ids", torch.int32)
+    dev = means2d.device
+    P = Cn * height * width
+    empty = tuple(torch.empty(0, dtype=torch.int64, device=dev) for _ in range(3))
+    if P == 0 or N == 0 or M == 0 or re <= rs:
+        return empty
+    # the cameras' lists one after the other, every row of offsets local to its camera's list and clamped into the
+    # list, the ids as Gaussian indices: what rasterize_to_pixels hands its kernels
+    first = isect_offsets.reshape(Cn, T)
+    ends = torch.cat([first[1:, 0], torch.full((1,), M, dtype=torch.int32, device=dev)])
+    local = torch.cat([first - first[:, :1], (ends - first[:, 0])[:, None]], dim=1).clamp_(0, M).contiguous()
+    flat = flatten_ids % N
+    m2, con, op, tr = (t.detach().contiguous() for t in (means2d, conics, opacities, transmittances))
+    args = (Cn, N, ptr(m2), ptr(con), ptr(op), ptr(tr), ptr(local), ptr(flat), M, width, height, tile_size, rs, re)
+    counts = torch.empty(P, dtype=torch.int32, device=dev)
+    call("eg_indices_count", *args, ptr(counts), stream())
+    csum = torch.cumsum(counts, 0, dtype=torch.int64)
+    total = int(csum[-1].item())  # the one read-back
+    if total < 0 or total >= 2 ** 62:
+        raise RuntimeError(f"rasterize_to_indices_in_range: the number of rows ({total}) does not fit")
+    if total == 0:
+        return empty
+    starts = csum - counts
+    gaussian_ids = torch.empty(total, dtype=torch.int64, device=dev)
+    pixel_ids = torch.empty(total, dtype=torch.int64, device=dev)
+    camera_ids = torch.empty(total, dtype=torch.int64, device=dev)
+    call("eg_indices_write", *args, ptr(starts), total, ptr(gaussian_ids), ptr(pixel_ids), ptr(camera_ids), stream())
+    return gaussian_ids, pixel_ids, camera_ids
+
+
+_ACC_CHUNK = 32  # channels per launch of the segmented sums (the chunk width of the wide compositing)
+
+
+class _Accumulate(torch.autograd.Function):
+    """eg_accumulate_fwd / eg_accumulate_bwd: per pixel p, over the entries [starts[p], starts[p] + counts[p]) in order,
+    renders[p] = sum_k alpha_k T_k feat_k and alphas[p] = sum_k alpha_k T_k with T_k the product of (1 - alpha) over the
+    segment's earlier entries.  One lane per pixel, no atomics; D in chunks of 32 channels."""
+
+    @staticmethod
+    def forward(ctx, alpha, feat, starts, counts, P):
+        M, D = feat.shape
+        dev = feat.device
+        a, f = alpha.contiguous(), feat.contiguous()
+        renders = torch.empty(P, D, device=dev)
+        alphas = torch.empty(P, device=dev)
+        T_k = torch.empty(M, device=dev)
+        for c0 in range(0, D, _ACC_CHUNK):
+            head = c0 == 0
+            call("eg_accumulate_fwd", ptr(a), ptr(f) + 4 * c0, D, min(_ACC_CHUNK, D - c0), ptr(starts), ptr(counts), P, M,
+                 ptr(renders) + 4 * c0, D, ptr(alphas) if head else None, ptr(T_k) if head else None, stream())
+        ctx.save_for_backward(a, f, starts, counts, T_k)
+        ctx.P = P
+        return renders, alphas
+
+    @staticmethod
+    def backward(ctx, v_renders, v_alphas):
+        a, f, starts, counts, T_k = ctx.saved_tensors
+        M, D = f.shape
+        P, dev = ctx.P, f.device
+        vr = v_renders.contiguous() if v_renders is not None else torch.zeros(P, D, device=dev)
+        va = v_alphas.contiguous() if v_alphas is not None else None
+        v_alpha = torch.empty(M, device=dev)
+        v_feat = torch.empty(M, D, device=dev)
+        for c0 in range(0, D, _ACC_CHUNK):
+            head = c0 == 0
+            call("eg_accumulate_bwd", ptr(a), ptr(f) + 4 * c0, D, min(_ACC_CHUNK, D - c0), ptr(starts), ptr(counts), P, M,
+                 ptr(T_k), ptr(vr) + 4 * c0, D, ptr(va) if head else None, ptr(v_alpha), 0 if head else 1,
+                 ptr(v_feat) + 4 * c0, stream())
+        return v_alpha, v_feat, None, None, None
+
+
+def accumulate(means2d: Tensor, conics: Tensor, opacities: Tensor, colors: Tensor, gaussian_ids: Tensor,
+               pixel_ids: Tensor, camera_ids: Tensor, image_width: int, image_height: int) -> Tuple[Tensor, Tensor]:
+    """gsplat ``accumulate``: alpha-composite the (pixel, Gaussian) pairs of ``rasterize_to_indices_in_range``.
+    Returns ``(renders [C,H,W,D], alphas [C,H,W,1])``; differentiable in ``means2d`` [C,N,2], ``conics`` [C,N,3],
+    ``opacities`` [C,N] and ``colors`` [C,N,D] (any D >= 1).  ``gaussian_ids`` / ``pixel_ids`` / ``camera_ids`` [M]
+    int64.
+
+    For entry k, ``alpha_k = min(0.999, opacity * exp(-sigma))`` of its (camera, Gaussian, pixel); there is NO 1/255
+    skip and NO transmittance stop here.  Inside each (camera, pixel), in the order given, ``w_k = alpha_k * prod over
+    the earlier k' of (1 - alpha_k')``; ``renders = sum w_k colors``, ``alphas = sum w_k``; pixels without entries are
+    zero.
+
+    PRECONDITION, not checked (checking would cost a host read-back): the entries are sorted by ``camera_ids * H * W +
+    pixel_ids``, as ``rasterize_to_indices_in_range`` returns them, and every id is in range.  Unsorted entries give a
+    wrong image (a pixel then walks a segment of its own LENGTH somewhere in the list), never an out-of-bounds access.
+
+    The gathers and the per-entry alpha are torch operations on the autograd graph; the segmented products and sums
+    are one kernel pair without atomics.  The gradients' scatter-adds (the backward of the gathers) are torch's
+    atomics: the gradient bits may vary from run to run."""
+    if means2d.dim() != 3:
+        raise ValueError(f"means2d must have shape (C, N, 2), got {tuple(means2d.shape)}")
+    Cn, N = means2d.shape[0], means2d.shape[1]
+    width, height = int(image_width), int(image_height)
+    if width < 0 or height < 0:
+        raise ValueError(f"image_width and image_height must not be negative, got {image_width!r}, {image_height!r}")
+    _check(means2d, (Cn, N, 2), "means2d")
+    _check(conics, (Cn, N, 3), "conics")
+    _check(opacities, (Cn, N), "opacities")
+    if colors.dim() != 3 or colors.shape[-1] < 1:
+        raise ValueError(f"colors must have shape (C, N, D) with D >= 1, got {tuple(colors.shape)}")
+    D = colors.shape[-1]
+    _check(colors, (Cn, N, D), "colors")
+    if gaussian_ids.dim() != 1:
+        raise ValueError(f"gaussian_ids must have shape (M,), got {tuple(gaussian_ids.shape)}")
+    M = gaussian_ids.shape[0]
+    _check(gaussian_ids, (M,), "gaussian_ids", torch.int64)
+    _check(pixel_ids, (M,), "pixel_ids", torch.int64)
+    _check(camera_ids, (M,), "camera_ids", torch.int64)
+    dev = means2d.device
+    P = Cn * height * width
+    if M == 0 or P == 0:  # (nothing to sum: zeros, on the inputs' graph)
+        zero = (means2d.sum() + conics.sum() + opacities.sum() + colors.sum()) * 0.0
+        return (torch.zeros(Cn, height, width, D, device=dev) + zero, torch.zeros(Cn, height, width, 1, device=dev) + zero)
+    with torch.no_grad():
+        key = camera_ids * (height * width) + pixel_ids
+        counts = torch.bincount(key, minlength=P)[:P].contiguous()  # a pixel's segment has ITS OWN length, whatever the order
+        starts = (torch.cumsum(counts, 0) - counts).contiguous()
+        px = (pixel_ids % width).to(torch.float32) + 0.5
+        py = torch.div(pixel_ids, width, rounding_mode="floor").to(torch.float32) + 0.5
+        row = camera_ids * N + gaussian_ids
+    # (index_select, not t[row]: its backward is one index_add, where advanced indexing sorts the M indices first)
+    xy = means2d.reshape(Cn * N, 2).index_select(0, row)
+    con = conics.reshape(Cn * N, 3).index_select(0, row)
+    dx, dy = xy[:, 0] - px, xy[:, 1] - py
+    sigma = 0.5 * (con[:, 0] * dx * dx + con[:, 2] * dy * dy) + con[:, 1] * dx * dy
+    alpha = torch.clamp(opacities.reshape(Cn * N).index_select(0, row) * torch.exp(-sigma), max=0.999)
+    feat = colors.reshape(Cn * N, D).index_select(0, row)
+    renders, alphas = _Accumulate.apply(alpha, feat, starts, counts, P)
+    return renders.reshape(Cn, height, width, D), alphas.reshape(Cn, height, width, 1)
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -9,16 +9,18 @@ optimisation); ``tile_size`` may be 8, 16 or 32 (16 is the reference's); ``camer
 last) may be "pinhole" or "ortho" (the orthographic camera of CAD views).
 
 The stage-by-stage API -- ``fully_fused_projection`` (from ``quats`` + ``scales`` or from ``covars``),
-``quat_scale_to_covar_preci``, ``isect_tiles``, ``isect_offset_encode``, ``rasterize_to_pixels``, ``world_to_cam``,
-``persp_proj``, ``proj`` -- is edgegaussians_amd/functional.py: the same kernels, for callers that change something between
-the stages (``packed=False`` only; see that module for the unsupported corners); ``fully_fused_projection`` and ``proj``
-take ``camera_model`` as well."""
+``quat_scale_to_covar_preci``, ``isect_tiles``, ``isect_offset_encode``, ``rasterize_to_pixels``,
+``rasterize_to_indices_in_range``, ``accumulate``, ``world_to_cam``, ``persp_proj``, ``proj`` -- is
+edgegaussians_amd/functional.py: the same kernels, for callers that change something between the stages
+(``packed=False`` only; see that module for the unsupported corners); ``fully_fused_projection`` and ``proj`` take
+``camera_model`` as well."""
 from edgegaussians_amd.rasterizer import rasterization  # noqa: F401
 from edgegaussians_amd.sh import spherical_harmonics  # noqa: F401
 from edgegaussians_amd.functional import (  # noqa: F401
-    fully_fused_projection, isect_offset_encode, isect_tiles, persp_proj, proj, quat_scale_to_covar_preci,
-    rasterize_to_pixels, world_to_cam)
+    accumulate, fully_fused_projection, isect_offset_encode, isect_tiles, persp_proj, proj, quat_scale_to_covar_preci,
+    rasterize_to_indices_in_range, rasterize_to_pixels, world_to_cam)
 
 __version__ = "1.0.0+edgegaussians_amd"
 __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "quat_scale_to_covar_preci", "isect_tiles",
-           "isect_offset_encode", "rasterize_to_pixels", "world_to_cam", "persp_proj", "proj"]
+           "isect_offset_encode", "rasterize_to_pixels", "rasterize_to_indices_in_range", "accumulate", "world_to_cam",
+           "persp_proj", "proj"]

@@ -963,6 +963,46 @@ int eg_project_covars_bwd_cams_flags(const float *means, const float *covars, co
 int eg_isect_offset_encode(const int64_t *isect_ids, int64_t M, int32_t C, int32_t tile_width, int32_t tile_height,
                            int32_t *offsets, eg_stream_t stream);
 
+/* ---- per-pixel intersection lists (csrc/indices.hip; functional.rasterize_to_indices_in_range / accumulate).  No
+ * atomics anywhere: the same bits every run.  Null pointers (other than the ones named) and bad sizes are refused with
+ * EG_ERR_ARG before any device call.
+ * eg_indices_count / eg_indices_write (tile_size 8, 16 or 32): two passes of ONE walk, the forward walk of the
+ *   compositing kernels (same sigma, threshold skip, alpha cap 0.999, 1/255 cut, stop BEFORE the entry that would take
+ *   T to <= 1e-4).  A tile's list is cut into batches of tile_size^2 entries; pixel p of camera c starts from
+ *   transmittances[c, p] and walks the batches b, range_start <= b < range_end, of its tile.  means2d [C,N,2], conics
+ *   [C,N,3], opacities [C,N]; offsets [C, T + 1] local to each camera's list and the cameras' lists one after the other
+ *   in flatten_ids [n_isects], whose values are Gaussian indices in [0, N) (what eg_composite_*_wide_cams take); a
+ *   tile's range is clamped into [0, n_isects] before any load.  The count writes counts [C * H * W] (every pixel);
+ *   the caller scans them into starts [C * H * W] (exclusive, 64-bit) and their sum `total`; the write stores row
+ *   starts[p] + k of gaussian_ids / pixel_ids (i * width + j) / camera_ids [total] for the k-th entry pixel p takes,
+ *   and never a row outside [0, total).  C * H * W == 0 or N == 0: EG_OK without a launch.
+ * eg_accumulate_fwd / eg_accumulate_bwd: per pixel p the entries k of [starts[p], starts[p] + counts[p]) (clamped into
+ *   [0, M]), in order: T_k = prod over the earlier k' of (1 - alpha[k']), w_k = alpha[k] T_k, render[p, ch] = sum w_k
+ *   feat[k, ch] for ONE chunk of `channels` <= 32 channels addressed by feat_stride / pixel_stride inside full-width
+ *   tensors, alphas[p] = sum w_k (NULL: not wanted), T_k [M] (NULL: not wanted).  The backward takes T_k back and
+ *   walks the segments in reverse without dividing by (1 - alpha): v_feat[k, ch] = w_k v_render[p, ch] (written, same
+ *   stride as feat), v_alpha[k] = (add ? v_alpha[k] : 0) + T_k (s_k - S_k) with s_k = feat[k] . v_render[p] +
+ *   v_alphas[p] (NULL: 0) and S_k the suffix sum of alpha_j s_j prod_{k<k'<j} (1 - alpha_k').  One lane owns one
+ *   pixel's segment.  P == 0: EG_OK without a launch. */
+int eg_indices_count(int32_t C, int32_t N, const float *means2d, const float *conics, const float *opacities,
+                     const float *transmittances /*[C,H,W]*/, const int32_t *offsets /*[C,T+1]*/,
+                     const int32_t *flatten_ids, int64_t n_isects, int32_t width, int32_t height, int32_t tile_size,
+                     int32_t range_start, int32_t range_end, int32_t *counts /*[C*H*W]*/, eg_stream_t stream);
+int eg_indices_write(int32_t C, int32_t N, const float *means2d, const float *conics, const float *opacities,
+                     const float *transmittances /*[C,H,W]*/, const int32_t *offsets /*[C,T+1]*/,
+                     const int32_t *flatten_ids, int64_t n_isects, int32_t width, int32_t height, int32_t tile_size,
+                     int32_t range_start, int32_t range_end, const int64_t *starts /*[C*H*W]*/, int64_t total,
+                     int64_t *gaussian_ids, int64_t *pixel_ids, int64_t *camera_ids, eg_stream_t stream);
+int eg_accumulate_fwd(const float *alpha /*[M]*/, const float *feat, int32_t feat_stride, int32_t channels,
+                      const int64_t *starts /*[P]*/, const int64_t *counts /*[P]*/, int64_t P, int64_t M, float *render,
+                      int32_t pixel_stride, float *alphas /*[P] or NULL*/, float *T_k /*[M] or NULL*/,
+                      eg_stream_t stream);
+int eg_accumulate_bwd(const float *alpha /*[M]*/, const float *feat, int32_t feat_stride, int32_t channels,
+                      const int64_t *starts /*[P]*/, const int64_t *counts /*[P]*/, int64_t P, int64_t M,
+                      const float *T_k /*[M]*/, const float *v_render, int32_t pixel_stride,
+                      const float *v_alphas /*[P] or NULL*/, float *v_alpha /*[M]*/, int32_t add, float *v_feat,
+                      eg_stream_t stream);
+
 /* ---- measurement aid: between eg_timing_begin(n) and eg_timing_end(), the next n eg_train_step
  * calls record HIP events between their stages on the launch stream; eg_timing_end synchronises
  * once and returns the average microseconds per stage (eg_timing_stage_count() entries, names by
