@@ -282,6 +282,28 @@ int eg_adam_multi(float *means, float *scales, float *quats, float *opacities,
 int eg_adam_tensor(float *param, float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, double lr, double beta1,
                    double beta2, double eps, int32_t step, int32_t zero_grad, eg_stream_t stream);
 
+/* ---- Adam on the rows one call saw (csrc/adam_sparse.hip; edgegaussians_amd/optim.py: SparseAdam, SelectiveAdam).
+ * Both: m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, p -= step_size m / (sqrt(v) + eps) -- eps on the UNCORRECTED
+ * root, unlike eg_adam_tensor.  Rows that are not stepped are neither read nor written.  No float atomics: the same
+ * bits every run.  Sizes are checked first (negative sizes, a width below 1, nnz * w or N * M at or above 2^31:
+ * EG_ERR_ARG); nnz == 0 or N == 0 is EG_OK without a launch; then null pointers are refused by name.
+ * eg_adam_sparse_rows: one torch.optim.SparseAdam step (torch/optim/_functional.py: sparse_adam) with
+ *   step_size = lr sqrt(1 - beta2^step) / (1 - beta1^step) formed in double; `step` is the 1-based count AFTER this
+ *   step.  param / exp_avg / exp_avg_sq [N, w]; values [nnz, w]; sorted_indices [nnz] ascending row indices; perm [nnz]
+ *   the permutation of a STABLE sort that produced them (values row perm[k] belongs to sorted_indices[k]), or NULL when
+ *   sorted_indices is the gradient's own coalesced index list (perm = identity).  The values of one row are added in
+ *   fp32 in the order of the values tensor and the row is stepped once with the sum.  An index outside [0, N) and a
+ *   perm entry outside [0, nnz) are skipped.  One thread walks a whole run of equal indices (see the file's header).
+ * eg_adam_masked_rows: gsplat's SelectiveAdam step, step_size = lr (no bias correction).  param / grad / exp_avg /
+ *   exp_avg_sq [N, M], visibility [N] bytes (a torch.bool tensor): rows with a non-zero byte step. */
+int eg_adam_sparse_rows(float *param, float *exp_avg, float *exp_avg_sq, const float *values /*[nnz,w]*/,
+                        const int64_t *sorted_indices /*[nnz]*/, const int64_t *perm /*[nnz] or NULL*/, int64_t nnz,
+                        int64_t N, int32_t w, double lr, double beta1, double beta2, double eps, int32_t step,
+                        eg_stream_t stream);
+int eg_adam_masked_rows(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
+                        const uint8_t *visibility /*[N]*/, int64_t N, int32_t M, double lr, double beta1, double beta2,
+                        double eps, eg_stream_t stream);
+
 /* The same four Adam steps (identical arithmetic) fused with eg_project_emit of the view this rank rasterises NEXT:
  * the tail of a data-parallel step (after the all-reduce of the gradients), one launch and one read of the
  * parameters instead of two.  The step that follows passes eg_step_args.have_projection = 1.  flags as
