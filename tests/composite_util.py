@@ -11,6 +11,7 @@ The chunked entries and the kernels behind them (DISPATCH below is checked again
       CH in {2, 4, 8, 16, 32}, all four (DEPTH, BG)
   eg_composite_{fwd,bwd}_modes_cams csrc/composite.hip       composite_fwd_kernel<CH, false, DEPTH, BG> /
       composite_bwd_colors_kernel<CH, DEPTH, BG>: CH = 0 with (1, 0); CH in {1, 3} with (1, 0), (0, 1), (1, 1)
+  eg_composite_fwd / eg_composite_bwd_colors csrc/composite.hip  the same kernels with CH in {1, 3} and (0, 0)
 """
 import collections
 import functools
@@ -201,12 +202,19 @@ def kernel_of(c):
     return (c.family, c.ts, ch, c.depth, c.bg and c.channels > 0)
 
 
+# eg_composite_bwd_colors (the operator's backward for general colours, tests/test_gpu_step_composite.py): the mode
+# kernels without a depth channel and without a background, composite_bwd_colors_kernel<1 | 3, false, false>
+COLORS_CASES = tuple(case("modes", 16, ch, 0, 0, scene=s, va=va)
+                     for s, ch, va in (("dense", 1, True), ("dense", 1, False), ("dense", 3, True), ("dense", 3, False),
+                                       ("sparse", 1, True), ("sparse", 3, False)))
+
 DISPATCH = frozenset(
     [("ts", ts, 0, True, False) for ts in (8, 32)]
     + [("ts", ts, ch, bool(d), bool(b)) for ts in (8, 32) for ch in WIDTHS for d, b in ALL_DB]
     + [("wide", 16, ch, bool(d), bool(b)) for ch in WIDTHS for d, b in ALL_DB]
     + [("modes", 16, 0, True, False)]
-    + [("modes", 16, ch, bool(d), bool(b)) for ch in (1, 3) for d, b in MODE_DB])
+    + [("modes", 16, ch, bool(d), bool(b)) for ch in (1, 3) for d, b in MODE_DB]
+    + [("modes", 16, ch, False, False) for ch in (1, 3)])
 
 
 @functools.lru_cache(maxsize=None)

@@ -97,10 +97,14 @@ def test_untouched_pixels_have_exactly_zero_alpha_in_the_reference():
 
 def test_case_table_launches_every_instantiation():
     """48 ts kernels with colours + 2 x 2 depth-only, 20 x 2 wide, 7 x 2 mode instantiations: each is the kernel of a
-    dense-scene case (forward and backward run in the same case)."""
-    got = {CU.kernel_of(c) for c in CU.DENSE_CASES}
+    dense-scene case (forward and backward run in the same case); 2 x 2 mode instantiations without depth and
+    background: each the kernel of a CU.COLORS_CASES case on the dense scene."""
+    got = {CU.kernel_of(c) for c in CU.DENSE_CASES + CU.COLORS_CASES}
     assert got == CU.DISPATCH
-    assert len([k for k in got if k[0] == "ts" and k[2] >= 8]) == 24 and len(got) == 42 + 20 + 7
+    # (+ 2: the (DEPTH, BG) = (0, 0) mode kernels, which only eg_composite_fwd / eg_composite_bwd_colors reach)
+    assert {CU.kernel_of(c) for c in CU.COLORS_CASES} == {("modes", 16, 1, False, False), ("modes", 16, 3, False, False)}
+    assert not {CU.kernel_of(c) for c in CU.DENSE_CASES} & {CU.kernel_of(c) for c in CU.COLORS_CASES}
+    assert len([k for k in got if k[0] == "ts" and k[2] >= 8]) == 24 and len(got) == 42 + 20 + 7 + 2
     assert all(c.scene == "dense" and c.n_real == c.channels for c in CU.DENSE_CASES)
     for fam in ("ts", "wide", "modes"):  # the cross-section: one narrow and one widest case per family and scene
         for s in ("sparse", "twocam"):

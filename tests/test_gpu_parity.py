@@ -1582,7 +1582,7 @@ def test_native_run_of_steps_equals_single_steps(env):
     assert int(tb.tile_counts.abs().sum()) == 0 and int(tb.ticket[0]) == 0
 
 
-@pytest.mark.parametrize("case", ["small", "stops", "config1_size", "tiny", "wide_footprints", "native_800"])
+@pytest.mark.parametrize("case", ["small", "stops", "config1_size", "tiny", "wide_footprints", "native_800", "mixed_footprints"])
 def test_fused_backward_kernel_equals_the_two_kernel_path(env, case):
     """Round 6: inside a native run of steps the backward of a scene of <= 32768 Gaussians is ONE kernel (csrc/backward_fused.hip:
     footprint backward, then -- in the workgroup's first wave -- projection backward + absgrads + Adam + the next view's
@@ -1604,6 +1604,12 @@ def test_fused_backward_kernel_equals_the_two_kernel_path(env, case):
         # 100 Gaussians that each cover most of a 45 x 25-tile grid: a workgroup's 64 Gaussians touch more tiles than the
         # touched list holds (512) -- the wave sweeps the whole histogram instead
         sc = synth.make_scene(100, 4, 720, 400, seed=4, scale=0.25, anisotropy=1.5, spread_opacity=True)
+    elif case == "mixed_footprints":
+        # log-scales spread over three decades, Gaussian by Gaussian: single waves (8 consecutive Gaussians) of the
+        # footprint walk hold a footprint that fills the image beside sub-pixel ones, which is where the lane dealing
+        # can go wrong (tests/test_gpu_step_composite.py pins the two-kernel path's rows to float64 on such waves)
+        sc = synth.make_scene(2003, 4, 200, 136, seed=9, spread_opacity=True)
+        sc.log_scales += math.log(10.0) * (3.0 * torch.rand(2003, 1, generator=torch.Generator().manual_seed(90)) - 1.5)
     else:
         sc = synth.make_scene(30011, 6, 512, 512, seed=11)
     sched = LRSchedule(scales_start=0, quats_start=0, opacities_start=0)
