@@ -173,6 +173,10 @@ _SIGS = {
     "eg_indices_write": [_i32, _i32] + [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp],
     "eg_accumulate_fwd": [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp],
     "eg_accumulate_bwd": [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp],
+    "eg_compute_relocation": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "eg_inject_noise": [_vp, _vp, _vp, _vp, _vp, _f, _i32, _vp],
+    "eg_strategy_update": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "eg_strategy_update_packed": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "eg_train_step_batched": [C.POINTER(StepArgs), _i32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp],
 }
 EXPORTS = sorted(list(_SIGS) + ["eg_last_error_string", "eg_version", "eg_device_count",

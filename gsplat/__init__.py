@@ -13,14 +13,20 @@ The stage-by-stage API -- ``fully_fused_projection`` (from ``quats`` + ``scales`
 ``rasterize_to_indices_in_range``, ``accumulate``, ``world_to_cam``, ``persp_proj``, ``proj`` -- is
 edgegaussians_amd/functional.py: the same kernels, for callers that change something between the stages
 (``packed=False`` only; see that module for the unsupported corners); ``fully_fused_projection`` and ``proj`` take
-``camera_model`` as well."""
+``camera_model`` as well.
+
+The densification strategies of gsplat's training scripts -- ``Strategy``, ``DefaultStrategy``, ``MCMCStrategy`` (also
+``gsplat.strategy``, with ``gsplat.strategy.ops``) and ``compute_relocation`` (also ``gsplat.relocation``) -- are
+edgegaussians_amd/strategy and edgegaussians_amd/relocation.py; the optimizers are ``gsplat.optimizers``."""
 from edgegaussians_amd.rasterizer import rasterization  # noqa: F401
 from edgegaussians_amd.sh import spherical_harmonics  # noqa: F401
 from edgegaussians_amd.functional import (  # noqa: F401
     accumulate, fully_fused_projection, isect_offset_encode, isect_tiles, persp_proj, proj, quat_scale_to_covar_preci,
     rasterize_to_indices_in_range, rasterize_to_pixels, world_to_cam)
+from edgegaussians_amd.relocation import compute_relocation  # noqa: F401
+from edgegaussians_amd.strategy import DefaultStrategy, MCMCStrategy, Strategy  # noqa: F401
 
 __version__ = "1.0.0+edgegaussians_amd"
 __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "quat_scale_to_covar_preci", "isect_tiles",
            "isect_offset_encode", "rasterize_to_pixels", "rasterize_to_indices_in_range", "accumulate", "world_to_cam",
-           "persp_proj", "proj"]
+           "persp_proj", "proj", "Strategy", "DefaultStrategy", "MCMCStrategy", "compute_relocation"]

@@ -1025,6 +1025,33 @@ int eg_accumulate_bwd(const float *alpha /*[M]*/, const float *feat, int32_t fea
                       const float *v_alphas /*[P] or NULL*/, float *v_alpha /*[M]*/, int32_t add, float *v_feat,
                       eg_stream_t stream);
 
+/* ---- gsplat's densification strategies (csrc/strategy.hip; edgegaussians_amd/strategy, edgegaussians_amd/relocation.py).
+ * One lane per Gaussian, no atomics: the same bits every run.  Sizes are checked first (EG_ERR_ARG), an empty call is
+ * EG_OK without a launch, then null pointers are refused by name.
+ * eg_compute_relocation: gsplat `compute_relocation`.  r = clamp(ratios, 1, n_max), x = 1 - (1 - o)^(1/r),
+ *   den = sum_{i=1..r} sum_{k=0..i-1} binoms[i-1, k] (-1)^k x^(k+1) / sqrt(k+1) in fp32 in that order;
+ *   new_opacities = x, new_scales = (o / den) scales.  binoms is the row-major [n_max, n_max] table.
+ * eg_inject_noise: means += R diag(s^2) R^T (noise * gate * scaler), s = exp(log_scales), R from the normalised quats
+ *   (w, x, y, z), gate = 1 / (1 + exp(-100 ((1 - sigmoid(logit_opacities)) - 0.995))).  All [N, k] fp32.
+ * eg_strategy_update / eg_strategy_update_packed: DefaultStrategy's running statistics over the visible pairs
+ *   (radii > 0): grad2d[n] += |(gx width/2 C, gy height/2 C)|, count[n] += 1, radii_state[n] (or NULL) =
+ *   max(radii_state[n], radii / max(width, height)), cameras in ascending order.  Dense: grads [C,N,2], radii [C,N].
+ *   Packed: grads [nnz,2], radii [nnz], gaussian_ids [nnz], indptr [C+1] (unused and may be NULL when C == 1) over pairs
+ *   in camera * N + gaussian order -- NOT checked: any other order gives wrong sums, never an access outside the
+ *   tensors (segment bounds are clamped to [0, nnz], ids outside [0, N) match no lane). */
+int eg_compute_relocation(const float *opacities /*[N]*/, const float *scales /*[N,3]*/, const int32_t *ratios /*[N]*/,
+                          const float *binoms /*[n_max,n_max]*/, int32_t N, int32_t n_max, float *new_opacities /*[N]*/,
+                          float *new_scales /*[N,3]*/, eg_stream_t stream);
+int eg_inject_noise(float *means /*[N,3] in/out*/, const float *quats /*[N,4]*/, const float *log_scales /*[N,3]*/,
+                    const float *logit_opacities /*[N]*/, const float *noise /*[N,3]*/, float scaler, int32_t N,
+                    eg_stream_t stream);
+int eg_strategy_update(const float *grads, const int32_t *radii, int32_t C, int32_t N, int32_t width, int32_t height,
+                       float *grad2d /*[N]*/, float *count /*[N]*/, float *radii_state /*[N] or NULL*/,
+                       eg_stream_t stream);
+int eg_strategy_update_packed(const float *grads, const int32_t *radii, const int64_t *gaussian_ids,
+                              const int64_t *indptr, int64_t nnz, int32_t C, int32_t N, int32_t width, int32_t height,
+                              float *grad2d, float *count, float *radii_state, eg_stream_t stream);
+
 /* ---- measurement aid: between eg_timing_begin(n) and eg_timing_end(), the next n eg_train_step
  * calls record HIP events between their stages on the launch stream; eg_timing_end synchronises
  * once and returns the average microseconds per stage (eg_timing_stage_count() entries, names by
