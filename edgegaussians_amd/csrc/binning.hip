@@ -106,8 +106,10 @@ tile_offsets_kernel(const int *__restrict__ counts, int T, long long capacity, i
   for (int base = 0; base < T; base += 1024) {
     const int i = base + tid;
     const int c = (i < T) ? counts[i] : 0;
-    const int it = max(1, (c + 127) >> 7);  // 128-Gaussian slices (kSlice in composite.hip); an empty tile owns one
-                                            // (empty) item: the forward finalises its pixels there
+    // 128-Gaussian slices (kSlice in composite.hip); an empty tile owns one (empty) item: the forward finalises its
+    // pixels there.  The threads past T own none: counted as one each they inflated item_offsets[T] and total[2] by
+    // 1024 - T % 1024 idle items behind the last tile.
+    const int it = (i < T) ? max(1, (c + 127) >> 7) : 0;
     int tot, itot;
     const int e = block_excl_scan_1024(c, wave_sums, tot);
     const int ie = block_excl_scan_1024(it, wave_sums, itot);

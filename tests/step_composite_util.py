@@ -374,6 +374,42 @@ def shear_records(W, H):
     return rec
 
 
+GRAZE_QUADRANTS = (   # (quadrant origin, which of its corners, k, side): eight thin diagonals with disjoint supports on CU.W x CU.H
+    ((8, 8), (0, 0), 2, -1), ((24, 8), (0, 0), 2, 1), ((32, 8), (1, 0), 3, -1), ((8, 16), (0, 1), 3, 1),
+    ((16, 16), (1, 1), 4, -1), ((32, 16), (1, 1), 4, 1), ((16, 8), (0, 1), 5, -1), ((32, 8), (0, 1), 5, 1))
+
+
+def grazing_quadrant_records():
+    """The quadrant cull's grazing case (quad_hit / quad_hit_staged / hitq[] of the compositing kernels): thin diagonal
+    ellipses (sigmas 2 and 0.5 px) whose flank touches an 8 x 8 quadrant only at a corner pixel centre, the float64 alpha
+    there (1/255)(1 - side 10^-k) ... i.e. side -1: just visible, side +1: just invisible.  o is solved at the record
+    level, from the fp32 record's own sigma at that pixel.  The supports are disjoint (asserted by
+    tests/test_cull_host.py), so the alpha image is the single Gaussian's alpha."""
+    rows = []
+    for (qx, qy), (cx, cy), _k, _side in GRAZE_QUADRANTS:
+        px, py = qx + 0.5 + 7.0 * cx, qy + 0.5 + 7.0 * cy
+        nx, ny = (1.0 if cx else -1.0) * math.sqrt(0.5), (1.0 if cy else -1.0) * math.sqrt(0.5)
+        rows.append((px + 1.12 * nx, py + 1.12 * ny, math.atan2(nx, -ny)))   # the major axis is perpendicular to the approach
+    n = len(rows)
+    rec = ellipse_records(np.array([(r[0], r[1]) for r in rows]), np.full(n, 2.0), np.full(n, 4.0), np.array([r[2] for r in rows]),
+                          np.full(n, 0.5), 1.0 + 0.1 * np.arange(n))
+    for i, ((qx, qy), (cx, cy), k, side) in enumerate(GRAZE_QUADRANTS):
+        x, y, a, b, c = (float(v) for v in rec[i, 0:5])
+        dx, dy = x - (qx + 0.5 + 7.0 * cx), y - (qy + 0.5 + 7.0 * cy)
+        sigma = 0.5 * (a * dx * dx + c * dy * dy) + b * dx * dy
+        rec[i, 5] = np.float32(math.exp(sigma) * (1.0 - side * 10.0 ** -k) / 255.0)
+    return rec
+
+
+def single_alphas(rec, W, H):
+    """float64 [N, H, W]: o exp(-sigma) of every Gaussian on its own, uncapped"""
+    p = np.asarray(rec[:, 0:6], np.float64)
+    dx = p[:, 0, None, None] - (np.arange(W) + 0.5)[None, None, :]
+    dy = p[:, 1, None, None] - (np.arange(H) + 0.5)[None, :, None]
+    sigma = 0.5 * (p[:, 2, None, None] * dx * dx + p[:, 4, None, None] * dy * dy) + p[:, 3, None, None] * dx * dy
+    return p[:, 5, None, None] * np.exp(-sigma)
+
+
 def stop_records(W, H):
     """48 rows.  Wave 0-1: ordinary Gaussians with twins at bit-equal depth (rows 0 / 5 / 11 share one depth, 2 / 9
     another) and rows one ulp either side of row 5's depth (rows 6, 7).  Wave 2: depths no record ever names (the
@@ -519,7 +555,10 @@ def forward_case(lengths_name, regime, with_loss=True):
     """records, lists, gt in {0, 1} and random values, a weight map, the float64 forward and the borderline mask (the
     weight map is zero on it) -- computed once, shared, never modified"""
     name = f"{lengths_name}-{regime}"
-    rec = tile_records(FWD_LENGTHS[lengths_name], regime, 700 + 10 * FWD_REGIMES.index(regime) + len(lengths_name))
+    if lengths_name == "grazing":   # (regime "nostop": eight Gaussians, no pixel stops)
+        rec = grazing_quadrant_records()
+    else:
+        rec = tile_records(FWD_LENGTHS[lengths_name], regime, 700 + 10 * FWD_REGIMES.index(regime) + len(lengths_name))
     lst = lists_of(rec, CU.W, CU.H)
     if not with_loss:
         f = ref_forward(rec, lst, CU.W, CU.H)

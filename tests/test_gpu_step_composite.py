@@ -22,6 +22,9 @@ Which test runs which kernel:
   composite_wave_fwd_kernel, batched (gridDim.y = C)        test_batched_step_records_and_rows
   ... on a grid above kPrefixHereMaxTiles (2704 tiles)      test_step_records_and_rows[large_grid]
   ... after another view's step on the same trainer         test_second_step_ignores_the_records_an_earlier_view_left
+  the quadrant cull (hitq[] / quad_hit) at a grazing corner  test_forward_tile_kernel | _sliced | _segments[grazing-nostop]: eight
+                                                             thin diagonals touching an 8 x 8 quadrant at one corner pixel
+                                                             (SU.grazing_quadrant_records; tests/test_cull_host.py)
 
 The one-kernel backward (backward_fused.hip) keeps g2d in LDS and runs only inside a run of whole training steps; grad_step
 always runs footprint_bwd_kernel.  No test here reaches it: it is tied to the footprint kernel by the bit-identity test of
@@ -197,6 +200,9 @@ def _check_forward(c, out, name, d32, speculative=False):
     ref = SU.fwd_ref_dict(f)
     ref["render"] = ref["render"].expand(1, CU.H, CU.W, ch)
     figs = CU.fwd_check(out["render"][None], out["alphas"][None], None, ref, torch.from_numpy(keep)[None], name)
+    if c.name.startswith("grazing"):   # disjoint supports: a pixel one Gaussian reaches with alpha >= (1/255)(1 + 1e-4) is not dropped
+        seen = (SU.single_alphas(c.rec, CU.W, CU.H) >= SU.AMIN * (1.0 + 1e-4)).any(axis=0)
+        assert not (seen & ~keep).any() and (out["alphas"].numpy()[seen] > 0).all(), f"{name}: a quadrant dropped a Gaussian that reaches it"
     touched = keep & (f.last_idx >= 0)
     want_last = f.last_idx if "pos" not in out else out["pos"][np.maximum(f.last_idx, 0)]
     bad = touched & (out["last"] != want_last)
@@ -220,7 +226,7 @@ def _check_forward(c, out, name, d32, speculative=False):
     return res
 
 
-FWD_CASES = [(l, r) for l in SU.FWD_LENGTHS for r in SU.FWD_REGIMES]
+FWD_CASES = [(l, r) for l in SU.FWD_LENGTHS for r in SU.FWD_REGIMES] + [("grazing", "nostop")]   # (the quadrant cull's case)
 
 
 @pytest.mark.parametrize("channels", [1, 3])
