@@ -13,7 +13,7 @@
 // 8 lanes that walk its footprint would multiply the ISSUED instructions by the idle lanes (the chain parallelises ~3x,
 // not 8x), and the footprint walk is issue-bound: the chain stays one lane per Gaussian, and what changes is WHEN it runs.
 // A workgroup here is 8 waves = 64 Gaussians.  Phase 1: every wave walks the footprints of its 8 Gaussians
-// (footprint_dev.h, unchanged) and leaves their g2d records in LDS.  One barrier.  Phase 2: seven waves leave, the first
+// (footprint_dev.h: the home phase and the walk of footprint_bwd_kernel) and leaves their g2d records in LDS.  One barrier.  Phase 2: seven waves leave, the first
 // one runs the projection backward, Adam and the next view's projection + binning of the workgroup's 64 Gaussians, one
 // per lane, while the OTHER workgroups' footprint walks fill the SIMD's issue slots: the chain is exposed once, at the
 // launch's tail, instead of in a launch of its own; the g2d record never leaves the CU; one kernel boundary is gone.
@@ -214,8 +214,8 @@ gaussian_bwd_fused_kernel(const FusedBwdArgs a) {
   // on phase-2 stragglers).  So phase 2 REUSES phase 1's storage: the histogram and the segment bases take the place of
   // the partial-record exchange (which moves 4 components at a time: 8 KB instead of 16), the touched list the place of
   // the footprint sizes.  13.3 KB at T <= 1024: twelve workgroups per CU.
-  extern __shared__ __attribute__((aligned(16))) int s_dyn[];  // max(kBFWaves * 256 floats, 2 T ints)
-  __shared__ __attribute__((aligned(16))) int s_walk[kBFGauss * 12];  // per Gaussian: i0 fh pw jlo | jhi cells thr xoff | shear - - -
+  extern __shared__ __attribute__((aligned(16))) int s_dyn[];  // max(kBFWaves * 256 floats + footprint_fold's pad, 2 T ints)
+  __shared__ __attribute__((aligned(16))) int s_walk[kBFGauss * kHomeRow];  // per Gaussian: i0 fh pw jlo | jhi cells thr xoff | shear - n first
   __shared__ __attribute__((aligned(16))) float s_g2d[kBFGauss * 8];
   float *red = (float *)s_dyn;               // phase 1: [kBFWaves][64 * 4]
   int *s_touched = s_walk;                  // phase 2: kBFTouched entries + the counter behind them
@@ -256,77 +256,33 @@ gaussian_bwd_fused_kernel(const FusedBwdArgs a) {
     if (lane == 63 && v != 0.f) unsafeAtomicAdd(a.loss_out, v);
   }
   const int gbase = blockIdx.x * kBFGauss + wv * 8;
-  if (threadIdx.x < kBFGauss) {  // the workgroup's footprints are sized once, one Gaussian per lane of the first wave
-    const int hg = blockIdx.x * kBFGauss + (int)threadIdx.x;
-    Walk w = walk_of(make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), width, height);
-    if (hg < N) w = walk_of(splat[2 * hg], splat[2 * hg + 1], width, height);
-    int4 *dst = (int4 *)&s_walk[12 * threadIdx.x];
-    dst[0] = make_int4(w.i0, w.fh, w.pw, w.jlo);
-    dst[1] = make_int4(w.jhi, w.cells, __float_as_int(w.thr), __float_as_int(w.xoff));
-    dst[2] = make_int4(__float_as_int(w.shear), 0, 0, 0);
+  if (threadIdx.x < kBFGauss) {
+    // the workgroup's footprints are sized, its waves' lanes dealt and its Gaussians' records staged once, one Gaussian
+    // per lane of the first wave (footprint_dev.h: the home phase; a wave's inbox is the front of its slice of `red`)
+    const int t = (int)threadIdx.x;
+    footprint_size_and_deal(splat, blockIdx.x * kBFGauss + t, N, width, height, t, &s_walk[kHomeRow * t],
+                            &s_walk[kHomeRow * (t & ~7)], red + (t >> 3) * 256);
   }
   __syncthreads();
   if (gbase < N) {  // (wave-uniform; a wave beyond N has nothing to walk but still meets the barrier below)
     const __amdgpu_buffer_rsrc_t rec_rsrc =
         __builtin_amdgcn_make_buffer_rsrc((void *)a.gtstop, 0, width * height * (int)sizeof(StopRec), 0x00020000);
-    Walk h;
-    {
-      const int4 *src = (const int4 *)&s_walk[12 * (wv * 8 + (lane >> 3))];
-      const int4 p = src[0], q = src[1];
-      h.i0 = p.x; h.fh = p.y; h.pw = p.z; h.jlo = p.w; h.jhi = q.x; h.cells = q.y;
-      h.thr = __int_as_float(q.z); h.xoff = __int_as_float(q.w); h.shear = __int_as_float(src[2].x);
-    }
-    // lanes per Gaussian in proportion to the cell counts: see footprint_bwd_kernel
-    int total = h.cells, live = h.cells > 0 ? 1 : 0;
-#pragma unroll
-    for (int d = 8; d < 64; d <<= 1) {
-      total += __shfl_xor(total, d, 64);
-      live += __shfl_xor(live, d, 64);
-    }
-    int h_n = 0, h_first = 0;
+    float *slice = red + wv * 256;
     Moments m = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-    if (total > 0) {
-      const float share = (float)(64 - live) * (1.f - 1e-5f) * __builtin_amdgcn_rcpf((float)total);
-      h_n = h.cells > 0 ? 1 + (int)((float)h.cells * share) : 0;
-      int incl = h_n + (h.cells > 0 ? 1 << 16 : 0);
-#pragma unroll
-      for (int d = 8; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-      }
-      const int slack = 64 - (__builtin_amdgcn_readlane(incl, 63) & 0xffff);
-      const int rank = (incl >> 16) - (h.cells > 0 ? 1 : 0);
-      h_first = (incl & 0xffff) - h_n + min(rank, slack);
-      if (h.cells > 0 && rank < slack) ++h_n;
-      int k = 0;
-#pragma unroll
-      for (int q = 1; q < 8; ++q) k += lane >= __builtin_amdgcn_readlane(h_first, 8 * q);
-      const int src = 8 * k;
-      const int n = max(__shfl(h_n, src, 64), 1);
-      const int r = lane - __shfl(h_first, src, 64);
-      const int g = min(gbase + k, N - 1);
-      const int cells = r < n ? __shfl(h.cells, src, 64) : 0;
-      s0 = splat[2 * g];
-      s1 = splat[2 * g + 1];
-      const int4 *wk = (const int4 *)&s_walk[12 * (wv * 8 + k)];
-      const int4 p = wk[0], q = wk[1];
-      const float shear_k = __int_as_float(wk[2].x);
-      footprint_walk(s0, s1, g, r, n, p.x, cells > 0 ? p.y : 0, max(p.z, 1), p.w, q.x, __int_as_float(q.z),
-                     __int_as_float(q.w), shear_k, width, rec_rsrc, m);
-    }
+    float4 s0, s1;
+    footprint_home_walk(&s_walk[kHomeRow * wv * 8], slice, lane, gbase, N, width, rec_rsrc, s0, s1, m);
     // partial g2d records through LDS, lane (k, component) adds the partials of Gaussian k's lanes in lane order (as
     // footprint_bwd_kernel does) -- four components at a time: vx vy |vx| |vy|, then va vb vc vo
-    float *mine = red + wv * 256 + lane * 4;
+    float *mine = slice + lane * 4;
     const int comp = lane & 7;
+    const int2 nf = *(const int2 *)&s_walk[kHomeRow * (wv * 8 + (lane >> 3)) + 10];  // n, first
+    const float *theirs = slice + nf.y * 4 + (comp & 3);
     float sum = 0.f;
-    *(float4 *)mine = make_float4(s0.z * m.w_x + s0.w * m.w_y, s0.w * m.w_x + s1.x * m.w_y, (2.f / kLog2e) * m.abs_x,
-                                  (2.f / kLog2e) * m.abs_y);
+    *(float4 *)mine = footprint_partial_means(s0, s1, m);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (comp < 4)
-      for (int t = 0; t < h_n; ++t) sum += red[wv * 256 + (h_first + t) * 4 + comp];
+    if (comp < 4) sum = footprint_fold<4>(theirs, nf.x);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -334,8 +290,7 @@ gaussian_bwd_fused_kernel(const FusedBwdArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (comp >= 4)
-      for (int t = 0; t < h_n; ++t) sum += red[wv * 256 + (h_first + t) * 4 + comp - 4];
+    if (comp >= 4) sum = footprint_fold<4>(theirs, nf.x);
     s_g2d[wv * 64 + lane] = sum;  // record of Gaussian gbase + (lane >> 3), component lane & 7
 #ifndef EG_BF_PROF
     if (a.g2d && gbase + (lane >> 3) < N) a.g2d[(size_t)gbase * 8 + lane] = sum;
@@ -385,7 +340,7 @@ int launch_gaussian_bwd_fused(float *means, float *quats, float *scales, float *
   a.cursor = tile_cursor; a.seg_cap = seg_cap; a.keys = (unsigned long long *)keys;
   a.loss_part = nullptr; a.loss_out = loss_out;
   if (workspace && loss_out) a.loss_part = carve_workspace(workspace, max_items, T).loss_part;
-  gaussian_bwd_fused_kernel<<<cdiv((int64_t)N, kBFGauss), 64 * kBFWaves, sizeof(int) * max(2 * T, kBFWaves * 256), st>>>(a);
+  gaussian_bwd_fused_kernel<<<cdiv((int64_t)N, kBFGauss), 64 * kBFWaves, sizeof(int) * max(2 * T, kBFWaves * 256 + kHomeFoldPad * 4), st>>>(a);
   timing_mark(kMarkFootprint, st);
   return check_launch("backward_fused");
 }

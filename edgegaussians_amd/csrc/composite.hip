@@ -897,7 +897,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
 footprint_bwd_kernel(const float4 *__restrict__ splat, int N, int width, int height,
                      const StopRec *__restrict__ gtstop, float *__restrict__ g2d, const Batch bt,
                      float *__restrict__ loss_part, float *__restrict__ loss_out) {
-  __shared__ float red[4][64 * 8];
+  // (the exchange of the partial records, one slice per wave -- whose front is the wave's inbox until its walk is over;
+  // the pad: footprint_fold reads up to kHomeFoldPad records behind the last wave's)
+  __shared__ __attribute__((aligned(16))) float red[4 * 64 * 8 + kHomeFoldPad * 8];
+  static_assert(kHomeInbox <= 64 * 8, "a wave's inbox lies in its slice of the exchange");
   splat += blockIdx.y * bt.splat4; gtstop += blockIdx.y * bt.pixels; g2d += blockIdx.y * bt.splat4 * 4;  // view
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (loss_part && blockIdx.x == 0 && wv == 0) {
@@ -913,17 +916,15 @@ footprint_bwd_kernel(const float4 *__restrict__ splat, int N, int width, int hei
   const int gbase = wave * 8;
   // Round 5: the workgroup's 32 footprints are sized ONCE, one Gaussian per lane of the first wave's lower half, and handed
   // to the four waves through LDS -- sized in the home phase of every wave, eight lanes per Gaussian, the same arithmetic
-  // ran four times per workgroup: ~150 of the ~1000 vector instructions a wave of this kernel issues at config 2
-  // (round 5, same box: 8.78 / 20.67 / 158.1 / 188.4 -> 8.24 / 19.7 / 157.7 / 186.3 us at configs 1-4).
-  __shared__ __attribute__((aligned(16))) int s_walk[32][12];  // i0 fh pw jlo | jhi cells thr xoff | shear - - -
+  // ran four times per workgroup: ~150 of the ~1000 vector instructions a wave of this kernel issued at config 2
+  // (round 5, same box: 8.78 / 20.67 / 158.1 / 188.4 -> 8.24 / 19.7 / 157.7 / 186.3 us at configs 1-4).  The same lanes
+  // now deal the waves' lanes and stage the Gaussians' records as well (footprint_dev.h: the home phase;
+  // profiles/footprint_home_phase_ab.txt).
+  __shared__ __attribute__((aligned(16))) int s_walk[32][kHomeRow];
   if (threadIdx.x < 32) {
-    const int hg = blockIdx.x * 32 + (int)threadIdx.x;
-    Walk w = walk_of(make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), width, height);
-    if (hg < N) w = walk_of(splat[2 * hg], splat[2 * hg + 1], width, height);
-    int4 *dst = (int4 *)s_walk[threadIdx.x];
-    dst[0] = make_int4(w.i0, w.fh, w.pw, w.jlo);
-    dst[1] = make_int4(w.jhi, w.cells, __float_as_int(w.thr), __float_as_int(w.xoff));
-    dst[2] = make_int4(__float_as_int(w.shear), 0, 0, 0);
+    const int t = (int)threadIdx.x;
+    footprint_size_and_deal(splat, blockIdx.x * 32 + t, N, width, height, t, s_walk[t], s_walk[t & ~7],
+                            red + (t >> 3) * 512);
   }
   __syncthreads();  // (the only barrier of the kernel: in front of the whole-wave exits)
   if (gbase >= N) return;  // whole waves leave; there is no workgroup barrier below
@@ -931,76 +932,29 @@ footprint_bwd_kernel(const float4 *__restrict__ splat, int N, int width, int hei
   const __amdgpu_buffer_rsrc_t rec_rsrc =
       __builtin_amdgcn_make_buffer_rsrc((void *)gtstop, 0, width * height * (int)sizeof(StopRec), 0x00020000);
 
-  // (Eight Gaussians per wave is the measured optimum at the reference's sizes: what precedes and follows the walk cost
-  // a wave ~400 VALU instructions whatever it holds -- a third of the kernel's issue slots at config 2 -- but sixteen
-  // Gaussians per wave lose more to the coarser lane dealing than they save, +13 % at config 2 and +47 % at
-  // 1600 x 1200; four per wave gain 8 % at 1600 x 1200 and lose 15 % at config 2.)
-  // home phase: the 8 lanes of group k all read the footprint of Gaussian gbase + k
-  Walk h;
-  {
-    const int4 *src = (const int4 *)s_walk[wv * 8 + (lane >> 3)];
-    const int4 a = src[0], b = src[1];
-    h.i0 = a.x; h.fh = a.y; h.pw = a.z; h.jlo = a.w; h.jhi = b.x; h.cells = b.y;
-    h.thr = __int_as_float(b.z); h.xoff = __int_as_float(b.w); h.shear = __int_as_float(src[2].x);
-  }
-  // Lanes per Gaussian, computed group-parallel: one lane for every live footprint, the other
-  // 64 - live in proportion to the cell counts (rounded down), the slack (<= live) one each to the
-  // first live groups.  A footprint of any size is handled here: a screen-filling Gaussian simply
-  // takes (nearly) all lanes of its wave.
-  int total = h.cells, live = h.cells > 0 ? 1 : 0;
-#pragma unroll
-  for (int d = 8; d < 64; d <<= 1) {
-    total += __shfl_xor(total, d, 64);
-    live += __shfl_xor(live, d, 64);
-  }
-  int h_n = 0, h_first = 0;
+  // (Eight Gaussians per wave is the measured optimum at the reference's sizes: what precedes and follows the walk costs
+  // a wave a fixed number of VALU instructions whatever it holds -- ~400 before the lanes were dealt once per workgroup, a
+  // third of the kernel's issue slots at config 2 -- but sixteen Gaussians per wave lose more to the coarser lane dealing
+  // than they save, +13 % at config 2 and +47 % at 1600 x 1200; four per wave gain 8 % at 1600 x 1200 and lose 15 % at
+  // config 2.)
+  // Lanes per Gaussian: one lane for every live footprint, the other 64 - live in proportion to the cell counts
+  // (rounded down), the slack (<= live) one each to the first live groups (deal_rule.h).  A footprint of any size is
+  // handled: a screen-filling Gaussian simply takes (nearly) all lanes of its wave.
+  float *slice = red + wv * 512;
   Moments m = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-  if (total > 0) {
-    const float share = (float)(64 - live) * (1.f - 1e-5f) * __builtin_amdgcn_rcpf((float)total);
-    h_n = h.cells > 0 ? 1 + (int)((float)h.cells * share) : 0;
-    int incl = h_n + (h.cells > 0 ? 1 << 16 : 0);  // inclusive scan over the groups of (lanes, live flag)
-#pragma unroll
-    for (int d = 8; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += up;
-    }
-    const int slack = 64 - (__builtin_amdgcn_readlane(incl, 63) & 0xffff);
-    const int rank = (incl >> 16) - (h.cells > 0 ? 1 : 0);  // live groups before this one
-    h_first = (incl & 0xffff) - h_n + min(rank, slack);
-    if (h.cells > 0 && rank < slack) ++h_n;
-    // lane -> Gaussian: the group whose lane range holds this lane (a lane past the last range idles)
-    int k = 0;
-#pragma unroll
-    for (int q = 1; q < 8; ++q) k += lane >= __builtin_amdgcn_readlane(h_first, 8 * q);
-    const int src = 8 * k;
-    const int n = max(__shfl(h_n, src, 64), 1);
-    const int r = lane - __shfl(h_first, src, 64);
-    const int g = min(gbase + k, N - 1);
-    const int cells = r < n ? __shfl(h.cells, src, 64) : 0;
-    s0 = splat[2 * g];
-    s1 = splat[2 * g + 1];
-    {  // (the walk of the lane's Gaussian: three 16-byte LDS reads instead of nine lane shuffles)
-      const int4 *wk = (const int4 *)s_walk[wv * 8 + k];
-      const int4 a = wk[0], b = wk[1];
-      const float shear_k = __int_as_float(wk[2].x);
-      footprint_walk(s0, s1, g, r, n, a.x, cells > 0 ? a.y : 0, max(a.z, 1), a.w, b.x, __int_as_float(b.z),
-                     __int_as_float(b.w), shear_k, width, rec_rsrc, m);
-    }
-  }
+  float4 s0, s1;
+  footprint_home_walk(s_walk[wv * 8], slice, lane, gbase, N, width, rec_rsrc, s0, s1, m);
   // partial g2d record of this lane: vx vy |vx| |vy| va vb vc vo
-  float *mine = &red[wv][lane * 8];
-  // (the absgrad sums were taken over |w| |h|, h = log2(e) / 2 times the gradient of sigma: footprint_visit)
-  *(float4 *)mine = make_float4(s0.z * m.w_x + s0.w * m.w_y, s0.w * m.w_x + s1.x * m.w_y, (2.f / kLog2e) * m.abs_x,
-                                (2.f / kLog2e) * m.abs_y);
+  float *mine = slice + lane * 8;
+  *(float4 *)mine = footprint_partial_means(s0, s1, m);
   *(float4 *)(mine + 4) = make_float4(0.5f * m.w_xx, m.w_xy, 0.5f * m.w_yy, m.v_o);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   // lane (k, component) adds the partial records of Gaussian k's lanes in lane order
   const int comp = lane & 7;
-  float sum = 0.f;
-  for (int t = 0; t < h_n; ++t) sum += red[wv][(h_first + t) * 8 + comp];
+  const int2 nf = *(const int2 *)&s_walk[wv * 8 + (lane >> 3)][10];  // n, first
+  const float sum = footprint_fold<8>(slice + nf.y * 8 + comp, nf.x);
   if (gbase + (lane >> 3) < N) g2d[(size_t)gbase * 8 + lane] = sum;
 }
 

@@ -1,8 +1,10 @@
 // Device code of the footprint backward (G8, order-independent form: DESIGN.md section 5) shared by composite.hip
-// (footprint_bwd_kernel) and backward_fused.hip.  Moved out of composite.hip in round 6, unchanged; the derivation and
-// the description of the walk sit in front of footprint_bwd_kernel in composite.hip.
+// (footprint_bwd_kernel) and backward_fused.hip: the walk (moved out of composite.hip in round 6, unchanged) and the
+// home phase around it (one copy since the lanes are dealt once per workgroup).  The derivation and the description of
+// the walk sit in front of footprint_bwd_kernel in composite.hip.
 #pragma once
 #include "composite.h"
+#include "deal_rule.h"
 
 namespace eg {
 
@@ -197,6 +199,103 @@ __device__ __forceinline__ void footprint_walk(const float4 s0, const float4 s1,
     p0 = fetch(ia, ca, left - 1);
     footprint_visit(qd, ug, dg, p1, m);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The home phase: what a wave does around the walk.  Everything in it that is a function of the workgroup's Gaussians
+// alone -- the sizes of the footprints (round 5), how each wave's 64 lanes are dealt to its 8 Gaussians, the Gaussians'
+// splat records -- is worked out ONCE, by the sizing lanes (one Gaussian per lane of the workgroup's first wave) in front
+// of the workgroup's barrier, and handed to the waves through LDS:
+//   the Gaussian's row of s_walk, 12 words:  i0 fh pw jlo | jhi cells thr xoff | shear - n first
+//   the wave's INBOX, 72 words at the front of the wave's slice of the partial-record exchange (which the wave
+//   overwrites only after its walk):  8 x {s0, s1} | total first[1] .. first[7]
+// Behind the barrier a lane finds its Gaussian k with seven compares against the broadcast firsts, takes n, first, the
+// walk and the record from row / inbox entry k, and walks.  (Before, every wave dealt its own lanes -- two three-round
+// shuffle butterflies, a three-round shuffle scan, seven readlanes, three more shuffles -- and every lane gathered its
+// Gaussian's record from global memory a second time, behind the barrier and the dealing.)
+constexpr int kHomeRow = 12;     // words of a Gaussian's s_walk row
+constexpr int kHomeInbox = 72;   // words of a wave's inbox
+constexpr int kHomeFoldPad = 3;  // partial records footprint_fold may read (and discard) behind a wave's last one
+
+// Sizing lane t (of the workgroup's first wave; the lanes t & ~7 .. t | 7 take part together) and Gaussian hg: `row` is
+// hg's s_walk row, `rows8` the row of the first Gaussian of hg's wave, `inbox` that wave's inbox.
+__device__ __forceinline__ void footprint_size_and_deal(const float4 *__restrict__ splat, int hg, int N, int width,
+                                                        int height, int t, int *row, const int *rows8, float *inbox) {
+  // (a Gaussian behind the last one has no footprint; its inbox entry is the LAST Gaussian's record, which is what the
+  // idle lanes of a ragged wave walk with: footprint_home_walk clamps g the same way)
+  const int gc = min(hg, N - 1);
+  const float4 s0 = splat[2 * gc], s1 = splat[2 * gc + 1];
+  Walk w = walk_of(make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), width, height);
+  if (hg < N) w = walk_of(s0, s1, width, height);
+  int4 *dst = (int4 *)row;
+  dst[0] = make_int4(w.i0, w.fh, w.pw, w.jlo);
+  dst[1] = make_int4(w.jhi, w.cells, __float_as_int(w.thr), __float_as_int(w.xoff));
+  const int i = t & 7;
+  *(float4 *)(inbox + 8 * i) = s0;
+  *(float4 *)(inbox + 8 * i + 4) = s1;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  int cells[kDealGroups];
+#pragma unroll
+  for (int j = 0; j < kDealGroups; ++j) cells[j] = rows8[kHomeRow * j + 5];
+  int total, live;
+  deal_totals(cells, total, live);
+  Deal d = {0, 0};
+  if (total > 0) d = deal_lanes(cells, live, __builtin_amdgcn_rcpf((float)total), i);
+  dst[2] = make_int4(__float_as_int(w.shear), 0, d.n, d.first);
+  inbox[64 + i] = __int_as_float(i == 0 ? total : d.first);  // (first[0] is 0 whatever the wave holds)
+}
+
+// A wave behind the barrier: lane -> (Gaussian k, lane r of n), the walk.  rows8: the s_walk row of the wave's first
+// Gaussian, gbase.  s0, s1 come back for the caller's partial record (zeros if the wave holds no footprint at all).
+__device__ __forceinline__ void footprint_home_walk(const int *rows8, const float *inbox, int lane, int gbase, int N,
+                                                    int width, const __amdgpu_buffer_rsrc_t rec_rsrc, float4 &s0,
+                                                    float4 &s1, Moments &m) {
+  const float4 f0 = *(const float4 *)(inbox + 64), f1 = *(const float4 *)(inbox + 68);
+  s0 = s1 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (__float_as_int(f0.x) <= 0) return;  // (total: wave-uniform)
+  // lane -> Gaussian: the group whose lane range holds this lane (a lane past the last range idles)
+  const int k = (lane >= __float_as_int(f0.y)) + (lane >= __float_as_int(f0.z)) + (lane >= __float_as_int(f0.w)) +
+                (lane >= __float_as_int(f1.x)) + (lane >= __float_as_int(f1.y)) + (lane >= __float_as_int(f1.z)) +
+                (lane >= __float_as_int(f1.w));
+  const int4 *wk = (const int4 *)(rows8 + kHomeRow * k);
+  const int4 a = wk[0], b = wk[1], c = wk[2];
+  const int n = max(c.z, 1);
+  const int r = lane - c.w;
+  const int g = min(gbase + k, N - 1);
+  const int cells = r < n ? b.y : 0;
+  s0 = *(const float4 *)(inbox + 8 * k);
+  s1 = *(const float4 *)(inbox + 8 * k + 4);
+  footprint_walk(s0, s1, g, r, n, a.x, cells > 0 ? a.y : 0, max(a.z, 1), a.w, b.x, __int_as_float(b.z),
+                 __int_as_float(b.w), __int_as_float(c.x), width, rec_rsrc, m);
+}
+
+// The first half of a lane's partial g2d record, vx vy |vx| |vy|, from its moments (the absgrad sums were taken over
+// |w| |h|, h = log2(e) / 2 times the gradient of sigma: footprint_visit).  vx = a w_x + b w_y and vy = b w_x + c w_y are
+// a product and a multiply-add each, and WHICH product is the rounded one is written out: left to the compiler's
+// contraction of a * b + c * d it changed with the code around the expression, and with it the last bits of every
+// gradient.  (These are the forms the kernels were compiled to while they carried the expression themselves.)
+__device__ __forceinline__ float4 footprint_partial_means(const float4 s0, const float4 s1, const Moments &m) {
+  return make_float4(fmaf(s0.z, m.w_x, s0.w * m.w_y), fmaf(s1.x, m.w_y, s0.w * m.w_x), (2.f / kLog2e) * m.abs_x,
+                     (2.f / kLog2e) * m.abs_y);
+}
+
+// Lane (k, component) adds component `p[0]` of the partial records of Gaussian k's n lanes in lane order: a left fold,
+// p[0] + p[STRIDE] + ...  Four records are requested together in front of the dependent adds (one read, one wait, one
+// add and one branch per record before); a read behind the n-th record is discarded -- the running sum is never -0, so
+// adding +0 leaves its bits alone -- and may reach kHomeFoldPad records behind the wave's last one.
+template <int STRIDE>
+__device__ __forceinline__ float footprint_fold(const float *p, int n) {
+  float sum = 0.f;
+  for (int t = 0; t < n; t += 4, p += 4 * STRIDE) {
+    const float v0 = p[0], v1 = p[STRIDE], v2 = p[2 * STRIDE], v3 = p[3 * STRIDE];
+    sum += v0;
+    sum += t + 1 < n ? v1 : 0.f;
+    sum += t + 2 < n ? v2 : 0.f;
+    sum += t + 3 < n ? v3 : 0.f;
+  }
+  return sum;
 }
 
 }  // namespace eg
