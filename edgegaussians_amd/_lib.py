@@ -160,6 +160,12 @@ _SIGS = {
     "eg_packed_bwd_sparse": [_vp] * 6 + [_i32, _i32, _i32, _i32, _f, _u32, _i64] + [_vp] * 8 + [_vp],
     "eg_project_bwd_viewmats": [_vp] * 6 + [_i32, _i32, _i32, _i32, _f, _u32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32,
                                 _vp, _vp],
+    "eg_packed_count_covars": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _f, _f, _f, _u32, _vp, _vp, _vp],
+    "eg_packed_write_covars": [_vp] * 5 + [_i32, _i32, _i32, _i32, _f, _f, _f, _f, _u32, _vp, _i64] + [_vp] * 10 + [_vp],
+    "eg_packed_bwd_covars": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _u32, _vp, _i64] + [_vp] * 6 + [_vp],
+    "eg_packed_bwd_sparse_covars": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _u32, _i64] + [_vp] * 7 + [_vp],
+    "eg_project_covars_bwd_viewmats": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _u32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                       _i32, _vp, _vp],
     "eg_sh_fwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp],
     "eg_sh_bwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "eg_quat_scale_to_covar_preci_fwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp],

@@ -44,7 +44,7 @@ def _stale() -> bool:
     if not os.path.exists(STAMP) or open(STAMP).read() != " ".join(FLAGS):
         return True  # (built with other flags, e.g. a development build with EG_EXTRA_HIPCC_FLAGS)
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + ["common.h", "composite.h", "project_dev.h", "footprint_dev.h", "deal_rule.h", "wide_dev.h"]]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + ["common.h", "composite.h", "project_dev.h", "footprint_dev.h", "deal_rule.h", "wide_dev.h", "covar_dev.h"]]
     deps.append(os.path.join(HERE, "..", "include", "edgegs.h"))
     return any(os.path.getmtime(d) > t for d in deps)
 

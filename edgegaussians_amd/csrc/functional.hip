@@ -16,6 +16,7 @@
 // symmetric entries of the matrix -- the gradient autograd gives through "build the matrix, select the upper triangle"
 // (outputs) and through "place the six numbers into the symmetric matrix" (inputs).
 #include "common.h"
+#include "covar_dev.h"
 #include "project_dev.h"
 
 namespace eg {
@@ -230,76 +231,18 @@ project_covars_bwd_kernel(const float *__restrict__ means, const float *__restri
     float cc[6], q0[3], q1[3];
     // near / far already passed in the forward (the radius is positive), so pass open limits
     if (!forward_geom_covar<CM>(cam, m, cv, width, height, -3.0e38f, 3.0e38f, eps2d, f, cc, q0, q1)) continue;
-    const float vx = v_means2d[2 * p], vy = v_means2d[2 * p + 1];
-    const float va = v_conics[3 * p], vb = v_conics[3 * p + 1], vc = v_conics[3 * p + 2];
-    // conic = B^-1  =>  G = -A V A with V = [[va, vb/2],[vb/2, vc]] (b is stored once): backward_geom's sweep
-    const float hb = 0.5f * vb;
-    const float av00 = f.a * va + f.b * hb, av01 = f.a * hb + f.b * vc;
-    const float av10 = f.b * va + f.c * hb, av11 = f.b * hb + f.c * vc;
-    float G00 = -(av00 * f.a + av01 * f.b);
-    float G01 = -(av00 * f.b + av01 * f.c);
-    float G11 = -(av10 * f.b + av11 * f.c);
-    if (v_comps) {
-      // gsplat's 0.5 v / (comp + 1e-6); nothing where the determinant ratio is negative (comp is clamped to 0 there)
-      const float det_conic = f.a * f.c - f.b * f.b;
-      const float vs = (f.det0 / f.det1 >= 0.f) ? v_comps[p] * 0.5f / (f.comp + 1e-6f) : 0.f;
-      const float omc = 1.f - f.comp * f.comp;
-      G00 += vs * (omc * f.a - eps2d * det_conic);
-      G01 += vs * (omc * f.b);
-      G11 += vs * (omc * f.c - eps2d * det_conic);
-    }
-    float vcc[9];
-    float vtx, vty, vtz;
-    if constexpr (CM == kOrtho) {
-      // cov2d = J cc J^T with the constant J = [[fx, 0, 0], [0, fy, 0]]: v_cc = J^T G J has the upper-left block only;
-      // camera-space mean: through mean2d and the depth
-      vcc[0] = f.J00 * f.J00 * G00;
-      vcc[1] = vcc[3] = f.J00 * f.J11 * G01;
-      vcc[4] = f.J11 * f.J11 * G11;
-      vcc[2] = vcc[6] = vcc[5] = vcc[7] = vcc[8] = 0.f;
-      vtx = cam.fx * vx;
-      vty = cam.fy * vy;
-      vtz = v_depths ? v_depths[p] : 0.f;
-    } else {
-      // cov2d = J cc J^T (cc symmetric)  =>  v_J = 2 G Q with Q = J cc, v_cc = J^T G J
-      const float vJ00 = 2.f * (G00 * q0[0] + G01 * q1[0]);
-      const float vJ02 = 2.f * (G00 * q0[2] + G01 * q1[2]);
-      const float vJ11 = 2.f * (G01 * q0[1] + G11 * q1[1]);
-      const float vJ12 = 2.f * (G01 * q0[2] + G11 * q1[2]);
-      const float g0 = G00 * f.J02 + G01 * f.J12, g1 = G01 * f.J02 + G11 * f.J12;  // G J[:, 2]
-      vcc[0] = f.J00 * f.J00 * G00;
-      vcc[1] = vcc[3] = f.J00 * f.J11 * G01;
-      vcc[2] = vcc[6] = f.J00 * g0;
-      vcc[4] = f.J11 * f.J11 * G11;
-      vcc[5] = vcc[7] = f.J11 * g1;
-      vcc[8] = f.J02 * g0 + f.J12 * g1;
-      // camera-space mean: through mean2d, the depth and J (fov clamp freezes tx = +-lim z)
-      const float rz3 = f.rz2 * f.rz;
-      vtx = cam.fx * f.rz * vx;
-      vty = cam.fy * f.rz * vy;
-      vtz = -(cam.fx * f.x * vx + cam.fy * f.y * vy) * f.rz2 + (v_depths ? v_depths[p] : 0.f);
-      vtz += -cam.fx * f.rz2 * vJ00 - cam.fy * f.rz2 * vJ11;
-      if (f.in_x) { vtx += -cam.fx * f.rz2 * vJ02; vtz += 2.f * cam.fx * f.tx * rz3 * vJ02; }
-      else        { vtz += cam.fx * f.tx * rz3 * vJ02; }
-      if (f.in_y) { vty += -cam.fy * f.rz2 * vJ12; vtz += 2.f * cam.fy * f.ty * rz3 * vJ12; }
-      else        { vtz += cam.fy * f.ty * rz3 * vJ12; }
-    }
-    am[0] += cam.R[0] * vtx + cam.R[3] * vty + cam.R[6] * vtz;
-    am[1] += cam.R[1] * vtx + cam.R[4] * vty + cam.R[7] * vtz;
-    am[2] += cam.R[2] * vtx + cam.R[5] * vty + cam.R[8] * vtz;
-    // cc = Rv S Rv^T  =>  v_S = Rv^T v_cc Rv; an off-diagonal of the six stands for both symmetric entries
-    float B[9];  // v_cc Rv
+    CovarCot ct;
+    ct.vx = v_means2d[2 * p]; ct.vy = v_means2d[2 * p + 1];
+    ct.va = v_conics[3 * p]; ct.vb = v_conics[3 * p + 1]; ct.vc = v_conics[3 * p + 2];
+    ct.v_depth = v_depths ? v_depths[p] : 0.f;
+    ct.has_comp = v_comps != nullptr;
+    ct.v_comp = v_comps ? v_comps[p] : 0.f;
+    float gm[3], gc[6];
+    covar_pair_vjp<false, CM>(cam, m, cv, f, q0, q1, eps2d, ct, gm, gc);  // (csrc/covar_dev.h)
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int k = 0; k < 3; ++k) am[k] += gm[k];
 #pragma unroll
-      for (int k = 0; k < 3; ++k)
-        B[3 * i + k] = vcc[3 * i] * cam.R[k] + vcc[3 * i + 1] * cam.R[3 + k] + vcc[3 * i + 2] * cam.R[6 + k];
-    constexpr int ui[6] = {0, 0, 0, 1, 1, 2}, uj[6] = {0, 1, 2, 1, 2, 2};
-#pragma unroll
-    for (int e = 0; e < 6; ++e) {
-      const float vS = cam.R[ui[e]] * B[uj[e]] + cam.R[3 + ui[e]] * B[3 + uj[e]] + cam.R[6 + ui[e]] * B[6 + uj[e]];
-      ac[e] += (ui[e] == uj[e]) ? vS : 2.f * vS;
-    }
+    for (int k = 0; k < 6; ++k) ac[k] += gc[k];
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) v_means[3 * (size_t)g + k] = am[k];

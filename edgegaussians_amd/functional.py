@@ -156,7 +156,8 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Optio
     Exactly one of ``covars`` [N,6] (upper triangle) and ``quats`` [N,4] + ``scales`` [N,3] must be given (ValueError).
     With ``quats`` + ``scales`` this is the projection node of ``rasterization`` -- the same kernels, the same bits, and
     ``viewmats`` receives its gradient when it requires one.  With ``covars`` a kernel pair of its own; ``viewmats``
-    must not require grad there (NotImplementedError).
+    must not require grad there (NotImplementedError): the pose gradient of the covariance form is reachable through
+    ``rasterization(covars=[N, 3, 3])``, as are ``packed=True`` and ``sparse_grad``.
 
     ``camera_model``: "pinhole" or "ortho" (``means2d = (fx x + cx, fy y + cy)``, the constant Jacobian ``[[fx, 0, 0],
     [0, fy, 0]]``, no fov clamp; see ``rasterization``), in both forms; checked before any tensor is looked at."""

@@ -46,6 +46,19 @@ def _is_ortho(camera_model) -> bool:
     return camera_model == "ortho"
 
 
+def _check_covars(covars, N: int) -> None:
+    """``covars`` of ``rasterization``: a fp32 [N, 3, 3] device tensor.  The `_check` conventions (TypeError for the
+    dtype, ValueError for shape or device), dtype and shape first: a wrong one is refused whatever device it is on."""
+    if not isinstance(covars, Tensor):
+        raise TypeError(f"covars must be a tensor or None, got {type(covars).__name__} (covars stands in front of "
+                        "channel_chunk and camera_model: pass those two by keyword)")
+    if covars.dtype != torch.float32:
+        raise TypeError(f"covars must be {torch.float32}, got {covars.dtype}")
+    if tuple(covars.shape) != (N, 3, 3):
+        raise ValueError(f"covars must have shape {(N, 3, 3)}, got {tuple(covars.shape)}")
+    _check(covars, (N, 3, 3), "covars")
+
+
 def _check(t: Tensor, shape, name: str, dtype=torch.float32):
     if not t.is_cuda:
         raise ValueError(f"{name} must be a device tensor (got {t.device}); edgegaussians_amd has no CPU path")
@@ -239,6 +252,190 @@ class _PackedProjection(torch.autograd.Function):
                  height, eps2d, flags, None, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d),
                  ptr(vcomp), ptr(vdep), ptr(scratch), blocks, ptr(v_viewmats), stream())
         return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 12
+
+
+_TRIU = (0, 1, 2, 4, 5, 8)  # the upper triangle (00, 01, 02, 11, 12, 22) inside a row-major 3 x 3 block
+
+
+def _covars6(covars: Tensor) -> Tensor:
+    """[N, 3, 3] -> the [N, 6] upper triangle the kernels take (only the entries i <= j are read)."""
+    return covars.reshape(covars.shape[0], 9)[:, _TRIU].contiguous()
+
+
+def _covars_grad33(v6: Tensor) -> Tensor:
+    """The kernels' [rows, 6] gradient (an off-diagonal entry carries both symmetric cotangents) scattered to the upper
+    triangle of [rows, 3, 3], zeros below the diagonal: what autograd gives through ``sym_from6(covars[:, iu, ju])``."""
+    out = torch.zeros(v6.shape[0], 9, device=v6.device)
+    out[:, _TRIU] = v6
+    return out.view(-1, 3, 3)
+
+
+def _g2d_record(v_means2d, v_conics, lead, dev) -> Tensor:
+    """The [..., 8] record layout of the compositing backward (words 0-1 v_means2d, 4-6 v_conics) from two cotangents."""
+    z2 = torch.zeros(*lead, 2, device=dev)
+    vm2d = v_means2d if v_means2d is not None else z2
+    vcon = v_conics if v_conics is not None else torch.zeros(*lead, 3, device=dev)
+    return torch.cat([vm2d, z2, vcon, torch.zeros(*lead, 1, device=dev)], dim=-1).contiguous()
+
+
+class _CovarProjection(torch.autograd.Function):
+    """`_Projection` from covariances [N, 3, 3] (gsplat ``rasterization(covars=...)``, packed=False): the projection of
+    ``functional.fully_fused_projection(covars=[N, 6])`` -- eg_project_covars_{fwd,bwd}_cams_flags, the same bits -- and
+    around it what the general path needs: the record of the compositing kernels (built here: that entry writes none),
+    the tile counts of the asked tile size, and, when ``viewmats`` requires grad, eg_project_covars_bwd_viewmats.  The
+    compensation and its cotangent are read only with `antialiased`."""
+
+    @staticmethod
+    def forward(ctx, means, covars, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
+                radius_clip, antialiased, tile_size=TILE, ortho=False):
+        Cn, N = viewmats.shape[0], means.shape[0]
+        dev = means.device
+        tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
+        means_c, cv, vm, Kc = means.contiguous(), _covars6(covars), viewmats.contiguous(), Ks.contiguous()
+        radii = torch.empty(Cn, N, dtype=torch.int32, device=dev)
+        means2d = torch.empty(Cn, N, 2, device=dev)
+        depths = torch.empty(Cn, N, device=dev)
+        conics = torch.empty(Cn, N, 3, device=dev)
+        comps = torch.empty(Cn, N, device=dev)
+        tpg = torch.zeros(Cn, N, dtype=torch.int32, device=dev)
+        counts = torch.zeros(Cn, tw * th, dtype=torch.int32, device=dev)
+        flags = _lib.FLAG_ORTHO if ortho else 0
+        call("eg_project_covars_fwd_cams_flags", ptr(means_c), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane,
+             far_plane, eps2d, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps), flags, stream())
+        # the record (x y a b c opacity[* compensation] depth radius) of the compositing kernels
+        o = opac_for_splat[None, :].expand(Cn, N)
+        splat = torch.cat([means2d, conics, (o * comps if antialiased else o)[..., None], depths[..., None],
+                           radii.view(torch.float32)[..., None]], dim=-1).contiguous()
+        if N > 0:
+            if tile_size == TILE:
+                for c in range(Cn):
+                    call("eg_tile_count", ptr(means2d[c]), ptr(radii[c]), N, width, height, ptr(tpg[c]), ptr(counts[c]), stream())
+            else:
+                call("eg_tile_count_ts", ptr(means2d), ptr(radii), (C.c_int64 * (Cn + 1))(*[c * N for c in range(Cn + 1)]), Cn,
+                     width, height, tile_size, ptr(tpg), ptr(counts), stream())
+        ctx.save_for_backward(means_c, cv, vm, Kc, radii)
+        ctx.cfg = (width, height, eps2d, flags, bool(antialiased))
+        ctx.mark_non_differentiable(radii, tpg, counts, splat)
+        return radii, means2d, depths, conics, comps, tpg, counts, splat
+
+    @staticmethod
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, _a, _b, _c):
+        means, cv, vm, Kc, radii = ctx.saved_tensors
+        width, height, eps2d, flags, antialiased = ctx.cfg
+        Cn, N = vm.shape[0], means.shape[0]
+        dev = means.device
+        vm2d = v_means2d.contiguous() if v_means2d is not None else torch.zeros(Cn, N, 2, device=dev)
+        vcon = v_conics.contiguous() if v_conics is not None else torch.zeros(Cn, N, 3, device=dev)
+        vdep = v_depths.contiguous() if v_depths is not None else None
+        vcomp = None
+        if antialiased:
+            vcomp = (v_comps if v_comps is not None else torch.zeros(Cn, N, device=dev)).contiguous()
+        v_means = torch.empty(N, 3, device=dev)
+        v_cv = torch.empty(N, 6, device=dev)
+        call("eg_project_covars_bwd_cams_flags", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, ptr(radii),
+             ptr(vm2d), ptr(vdep), ptr(vcon), ptr(vcomp), ptr(v_means), ptr(v_cv), flags, stream())
+        v_viewmats = None
+        if ctx.needs_input_grad[3]:  # (a pose optimiser: nobody else pays for these two kernels)
+            v_viewmats = torch.zeros(Cn, 4, 4, device=dev)
+            if N > 0:  # (the entry tells the dense layout by its radii, and without Gaussians there are none: zeros)
+                blocks = math.ceil(N / 256)
+                scratch = torch.empty(Cn, blocks, 12, device=dev)
+                g2d = _g2d_record(vm2d, vcon, (Cn, N), dev)
+                call("eg_project_covars_bwd_viewmats", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d,
+                     flags | (_lib.FLAG_ANTIALIASED if antialiased else 0), ptr(radii), None, 0, None, ptr(g2d), ptr(vcomp),
+                     ptr(vdep), ptr(scratch), blocks, ptr(v_viewmats), stream())
+        return (v_means, _covars_grad33(v_cv), None, v_viewmats) + (None,) * 10
+
+
+class _PackedCovarProjection(torch.autograd.Function):
+    """`_PackedProjection` from covariances [N, 3, 3] (csrc/packed.hip, the eg_packed_*_covars entries): the same outputs,
+    read-back and `holder`.  Backward: eg_packed_bwd_covars (dense ``means.grad`` [N, 3], ``covars.grad`` [N, 3, 3]) or,
+    with `sparse_grad`, eg_packed_bwd_sparse_covars (sparse COO gradients with indices gaussian_ids[None] and values
+    [nnz, 3] / [nnz, 3, 3], coalesced iff C == 1); ``viewmats`` through eg_project_covars_bwd_viewmats."""
+
+    @staticmethod
+    def forward(ctx, means, covars, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
+                radius_clip, antialiased, sparse_grad, holder, tile_size=TILE, ortho=False):
+        Cn, N = viewmats.shape[0], means.shape[0]
+        dev = means.device
+        tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
+        means_c, cv, opac_c = means.contiguous(), _covars6(covars), opac_for_splat.contiguous()
+        vm, Kc = viewmats.contiguous(), Ks.contiguous()
+        flags = (_lib.FLAG_ANTIALIASED if antialiased else 0) | (_lib.FLAG_ORTHO if ortho else 0)
+        block_base = torch.empty(Cn * math.ceil(N / 256), dtype=torch.int32, device=dev)
+        indptr = torch.empty(Cn + 1, dtype=torch.int64, device=dev)
+        call("eg_packed_count_covars", ptr(means_c), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane, far_plane,
+             eps2d, radius_clip, flags, ptr(block_base), ptr(indptr), stream())
+        indptr_host = indptr.tolist()  # the first of the call's two read-backs (the second: the M_c of the binning)
+        nnz = indptr_host[-1]
+        if nnz >= 2 ** 31:
+            raise RuntimeError(f"rasterization(packed=True): {nnz} visible (camera, Gaussian) pairs; the limit is 2^31 - 1")
+        i32 = dict(dtype=torch.int32, device=dev)
+        splat = torch.empty(nnz, 8, device=dev)
+        radii = torch.empty(nnz, **i32)
+        means2d = torch.empty(nnz, 2, device=dev)
+        depths = torch.empty(nnz, device=dev)
+        conics = torch.empty(nnz, 3, device=dev)
+        comps = torch.empty(nnz, device=dev)
+        tpg = torch.empty(nnz, **i32)
+        camera_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
+        gaussian_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
+        counts = torch.zeros(Cn, tw * th, **i32)
+        counts16 = counts if tile_size == TILE else torch.zeros(Cn, math.ceil(width / TILE) * math.ceil(height / TILE), **i32)
+        call("eg_packed_write_covars", ptr(means_c), ptr(cv), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane,
+             far_plane, eps2d, radius_clip, flags, ptr(block_base), nnz, ptr(splat), ptr(radii), ptr(means2d), ptr(depths),
+             ptr(conics), ptr(comps), ptr(tpg), ptr(camera_ids), ptr(gaussian_ids), ptr(counts16), stream())
+        if tile_size != TILE:  # (tiles_per_gauss is written again, for this tile size)
+            call("eg_tile_count_ts", ptr(means2d), ptr(radii), (C.c_int64 * (Cn + 1))(*indptr_host), Cn, width, height,
+                 tile_size, ptr(tpg), ptr(counts), stream())
+        holder["indptr"] = indptr_host
+        ctx.save_for_backward(means_c, cv, vm, Kc, indptr, camera_ids, gaussian_ids)
+        ctx.cfg = (width, height, eps2d, flags, bool(sparse_grad))
+        ctx.mark_non_differentiable(radii, tpg, counts, splat, camera_ids, gaussian_ids)
+        return radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids
+
+    @staticmethod
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, *_rest):
+        means, cv, vm, Kc, indptr, camera_ids, gaussian_ids = ctx.saved_tensors
+        width, height, eps2d, flags, sparse_grad = ctx.cfg
+        Cn, N, nnz = vm.shape[0], means.shape[0], gaussian_ids.shape[0]
+        dev = means.device
+        g2d = _g2d_record(v_means2d, v_conics, (nnz,), dev)
+        vcomp = (v_comps if v_comps is not None else torch.zeros(nnz, device=dev)).contiguous()
+        vdep = v_depths.contiguous() if v_depths is not None else None
+        rows = nnz if sparse_grad else N
+        v_means = torch.empty(rows, 3, device=dev)
+        v_cv = torch.empty(rows, 6, device=dev)
+        if sparse_grad:
+            call("eg_packed_bwd_sparse_covars", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, flags, nnz,
+                 ptr(camera_ids), ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means), ptr(v_cv), stream())
+            idx = gaussian_ids[None]
+            v_means = torch.sparse_coo_tensor(idx, v_means, size=(N, 3), is_coalesced=(Cn == 1))
+            v_covars = torch.sparse_coo_tensor(idx, _covars_grad33(v_cv), size=(N, 3, 3), is_coalesced=(Cn == 1))
+            ctx.sparse_grads = (v_means, v_covars)  # (a second owner: see _PackedProjection.backward)
+        else:
+            call("eg_packed_bwd_covars", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, flags, ptr(indptr),
+                 nnz, ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means), ptr(v_cv), stream())
+            v_covars = _covars_grad33(v_cv)
+        v_viewmats = None
+        if ctx.needs_input_grad[3]:  # (always dense [C, 4, 4], with `sparse_grad` as well)
+            blocks = math.ceil(min(nnz, N) / 256)
+            scratch = torch.empty(Cn, blocks, 12, device=dev)
+            v_viewmats = torch.empty(Cn, 4, 4, device=dev)
+            call("eg_project_covars_bwd_viewmats", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, flags,
+                 None, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(scratch), blocks,
+                 ptr(v_viewmats), stream())
+        return (v_means, v_covars, None, v_viewmats) + (None,) * 12
+
+
+def _dense_projection(means, quats, scales, covars, opacities, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
+                      radius_clip, antialiased, tile_size, ortho):
+    """The projection node of the general path: `_Projection`, or with ``covars`` `_CovarProjection` (same outputs)."""
+    if covars is None:
+        return _Projection.apply(means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
+                                 float(near_plane), float(far_plane), float(radius_clip), antialiased, tile_size, ortho)
+    return _CovarProjection.apply(means, covars, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
+                                  float(near_plane), float(far_plane), float(radius_clip), antialiased, tile_size, ortho)
 
 
 class _Compositing(torch.autograd.Function):
@@ -956,21 +1153,22 @@ RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
 
 def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
                         radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree=None, chunk=None,
-                        tile_size=TILE, ortho=False):
+                        tile_size=TILE, ortho=False, covars=None):
     """`rasterization` with a depth channel and / or backgrounds: the general two-node path (projection -> compositing)
     with the compositing of eg_composite_{fwd,bwd}_modes_cams, which takes `depths` as an input.  With `sh_degree`,
     `colors` holds the coefficients and the colours are evaluated behind the projection (its radii are their mask).
     With `chunk` (colours of a channel count other than 1 or 3, in any mode that renders them): the same projection,
     binning and sort, then the compositing of eg_composite_{fwd,bwd}_wide_cams in chunks of `chunk` channels.
     With a `tile_size` of 8 or 32 (always with `chunk`): counting, emission and compositing by csrc/tiles.hip.
-    `ortho`: the orthographic projection; everything behind the projection is the same."""
+    `ortho`: the orthographic projection; everything behind the projection is the same.  `covars` [N, 3, 3]: the
+    projection from covariances (`_CovarProjection`; `quats` and `scales` are not read)."""
     N, Cn = means.shape[0], viewmats.shape[0]
     depth = render_mode != "RGB"
     if render_mode in ("D", "ED"):
         colors, backgrounds = None, None  # (gsplat: the depth is the only channel, its background is 0)
-    radii, means2d, depths, conics, comps, tpg, counts, _splat = _Projection.apply(
-        means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
-        float(near_plane), float(far_plane), float(radius_clip), antialiased, tile_size, ortho)
+    radii, means2d, depths, conics, comps, tpg, counts, _splat = _dense_projection(
+        means, quats, scales, covars, opacities, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip,
+        antialiased, tile_size, ortho)
     if sh_degree is not None and colors is not None:
         colors = _sh.view_colors(means, viewmats, colors, radii, sh_degree)
     opac = opacities[None, :].expand(Cn, N)
@@ -1025,21 +1223,27 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
 
 def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
                           radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree, chunk,
-                          sparse_grad, tile_size=TILE, ortho=False):
+                          sparse_grad, tile_size=TILE, ortho=False, covars=None):
     """`rasterization(packed=True)`: the packed projection (_PackedProjection), the colours / opacities gathered per pair
     in torch (dense gradients of the caller's shapes, as in gsplat), every camera's range binned as a single-camera
     problem (eg_packed_bin), and the mode / wide compositing kernels on the packed records (record stride
     _lib.PACKED_STRIDE).  Never the unit-colour fast path.  Two host read-backs: indptr, then the M_c.  With a
-    `tile_size` of 8 or 32 (always with `chunk`): counting, emission and compositing by csrc/tiles.hip."""
+    `tile_size` of 8 or 32 (always with `chunk`): counting, emission and compositing by csrc/tiles.hip.  `covars`
+    [N, 3, 3]: the packed projection from covariances (`_PackedCovarProjection`; `quats` and `scales` are not read)."""
     N, Cn = means.shape[0], viewmats.shape[0]
     dev = means.device
     depth = render_mode != "RGB"
     if render_mode in ("D", "ED"):
         colors, backgrounds = None, None  # (gsplat: the depth is the only channel, its background is 0)
     holder: Dict = {}
-    radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids = _PackedProjection.apply(
-        means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
-        float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder, tile_size, ortho)
+    if covars is None:
+        radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids = _PackedProjection.apply(
+            means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
+            float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder, tile_size, ortho)
+    else:
+        radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids = _PackedCovarProjection.apply(
+            means, covars, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
+            float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder, tile_size, ortho)
     indptr = holder["indptr"]
     nnz = indptr[-1]
     if colors is not None:
@@ -1117,8 +1321,8 @@ def rasterization(
     near_plane: float = 0.01, far_plane: float = 1e10, radius_clip: float = 0.0, eps2d: float = 0.3,
     sh_degree: Optional[int] = None, packed: bool = True, tile_size: int = 16,
     backgrounds: Optional[Tensor] = None, render_mode: str = "RGB", sparse_grad: bool = False,
-    absgrad: bool = False, rasterize_mode: str = "classic", channel_chunk: int = 32,
-    camera_model: str = "pinhole",
+    absgrad: bool = False, rasterize_mode: str = "classic", covars: Optional[Tensor] = None,
+    channel_chunk: int = 32, camera_model: str = "pinhole",
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Same names, argument meaning and defaults as gsplat 1.0.0 ``rasterization``, for tile_size 8, 16 or 32 and
     colours of any channel count D >= 1 (the reference's call, edge_gs.py:250-268, is packed=False, render_mode='RGB'
@@ -1194,16 +1398,39 @@ def rasterization(
     described above -- ``packed``, ``sparse_grad``, every ``render_mode``, ``backgrounds``, ``sh_degree`` (the view
     directions stay ``means - campos``, as in gsplat), any D, ``rasterize_mode``, ``absgrad``, the cull arguments,
     ``tile_size`` 8 / 16 / 32 and the ``viewmats`` gradient -- through orthographic instantiations of the projection
-    kernels (EG_FLAG_ORTHO); an "ortho" call never takes the unit-colour fast path."""
+    kernels (EG_FLAG_ORTHO); an "ortho" call never takes the unit-colour fast path.
+
+    ``covars`` (its semantics are restated from memory of gsplat >= 1.3, like the rest of this signature; pass it by
+    keyword.  It stands in front of ``channel_chunk``, because ``camera_model`` is pinned as the last parameter: a call
+    that passes ``channel_chunk`` as its 22nd positional argument now gets a TypeError that says so, never another
+    result; the first 21 positions and every keyword keep their meaning): the Gaussians' full 3-D covariances, [N, 3, 3] fp32 on the device (TypeError for the
+    dtype, ValueError for shape or device), in place of ``quats`` + ``scales``, which are then ignored, may be None and
+    receive no gradient.  Only the upper triangle (``i <= j``) is read; the six numbers go to the kernels as the [N, 6]
+    upper triangle that ``functional.fully_fused_projection(covars=...)`` takes.  ``covars.grad`` is [N, 3, 3] with
+    zeros below the diagonal, an off-diagonal entry carrying the cotangents of both symmetric entries -- what autograd
+    gives for ``sym_from6(covars[:, iu, ju])``.  With ``packed=False`` the projection is that stage call's kernel pair,
+    bit for bit; with ``packed=True`` count / write / backward kernels of their own keep exactly its ``radii > 0`` pairs
+    with its values (csrc/packed.hip); with ``sparse_grad`` ``means.grad`` and ``covars.grad`` are sparse COO tensors
+    with indices ``gaussian_ids[None]`` and values [nnz, 3] / [nnz, 3, 3], coalesced exactly when there is one camera.
+    Everything behind the projection is unchanged: ``packed``, every ``render_mode``, ``backgrounds``, ``sh_degree``
+    (directions ``means - campos``), any D, ``rasterize_mode``, ``absgrad``, the cull arguments, ``tile_size`` 8 / 16 /
+    32 and both camera models work as described above, and ``info`` has the keys, shapes and dtypes of the quats +
+    scales call.  ``viewmats`` receives its gradient here too (the pose gradient of the covariance form is reachable
+    through this call only: the stage function refuses it), leaving the gradients of ``means`` and ``covars`` bit for bit
+    what they are without it.  A ``covars`` call never takes the unit-colour fast path; a call without ``covars`` runs
+    exactly the code it ran before the argument existed."""
     ortho = _is_ortho(camera_model)
     if isinstance(tile_size, bool) or tile_size not in TILE_SIZES:
         raise NotImplementedError(f"tile_size must be 8, 16 or 32, got {tile_size!r} (the reference passes 16, edge_gs.py:232)")
     tile_size = int(tile_size)
     N = means.shape[0]
     Cn = viewmats.shape[0]
+    if covars is not None:
+        _check_covars(covars, N)
     _check(means, (N, 3), "means")
-    _check(quats, (N, 4), "quats")
-    _check(scales, (N, 3), "scales")
+    if covars is None:
+        _check(quats, (N, 4), "quats")
+        _check(scales, (N, 3), "scales")
     _check(opacities, (N,), "opacities")
     _check(viewmats, (Cn, 4, 4), "viewmats")
     _check(Ks, (Cn, 3, 3), "Ks")
@@ -1235,21 +1462,21 @@ def rasterization(
         return _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                      far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
                                      sh_degree, min(channel_chunk, 32) if (wide or tile_size != TILE) else None,
-                                     sparse_grad, tile_size, ortho)
+                                     sparse_grad, tile_size, ortho, covars)
     if tile_size != TILE:  # (every channel count and mode: one kernel family, csrc/tiles.hip; never the fast path)
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                    far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
-                                   sh_degree, min(channel_chunk, 32), tile_size, ortho)
+                                   sh_degree, min(channel_chunk, 32), tile_size, ortho, covars)
     if D not in (1, 3) and render_mode not in ("D", "ED"):  # (the depth-only modes do not read the colours)
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                    far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased,
-                                   chunk=min(channel_chunk, 32), ortho=ortho)
+                                   chunk=min(channel_chunk, 32), ortho=ortho, covars=covars)
     if render_mode != "RGB" or backgrounds is not None:
         return _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane,
                                    far_plane, radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree,
-                                   ortho=ortho)
+                                   ortho=ortho, covars=covars)
 
-    if (not ortho and sh_degree is None and Cn == 1 and colors.dim() == 2 and not colors.requires_grad and float(eps2d) == 0.3 and float(near_plane) == 0.01
+    if (covars is None and not ortho and sh_degree is None and Cn == 1 and colors.dim() == 2 and not colors.requires_grad and float(eps2d) == 0.3 and float(near_plane) == 0.01
             and float(far_plane) == 1e10 and float(radius_clip) == 0.0 and N > 0 and _FAST_ENABLED and not viewmats.requires_grad):
         # the reference's own call (edge_gs.py:247-268): colours torch.ones(N, 3) without grad, one camera (and a fixed
         # one: the fast path's single node has no pose gradient, a camera that requires grad takes the general path)
@@ -1257,9 +1484,9 @@ def rasterization(
         if out is not None:
             return out
 
-    radii, means2d, depths, conics, comps, tpg, counts, _splat = _Projection.apply(
-        means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
-        float(near_plane), float(far_plane), float(radius_clip), antialiased, TILE, ortho)
+    radii, means2d, depths, conics, comps, tpg, counts, _splat = _dense_projection(
+        means, quats, scales, covars, opacities, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip,
+        antialiased, TILE, ortho)
     if sh_degree is not None:
         colors = _sh.view_colors(means, viewmats, colors, radii, sh_degree)
     opac = opacities[None, :].expand(Cn, N)
@@ -1273,7 +1500,8 @@ def rasterization(
     info_offsets = []
     # the reference always passes torch.ones(N,3) without grad (edge_gs.py:247, a fresh tensor every step): decide
     # "unit colours" on the device and read the verdict back with M (the one host sync gsplat also has)
-    unit_flag = None if colors.requires_grad else (colors == 1).all()
+    # (never with `covars`: that call takes the general compositing kernels whatever its colours are)
+    unit_flag = None if (colors.requires_grad or covars is not None) else (colors == 1).all()
     with torch.no_grad():
         o_l, f_l, i_l, Ms, item_l, tot_l, nit_l, extra = isect_tiles_and_sort_cams(
             means2d.contiguous(), radii, depths.contiguous(), counts, width, height, extra_flag=unit_flag)

@@ -6,7 +6,11 @@ The reference imports ``rasterization`` alone; ``spherical_harmonics`` is there 
 included (only the visible (camera, Gaussian) pairs are kept; ``info["camera_ids"]`` / ``info["gaussian_ids"]`` name
 them), and ``sparse_grad=True`` on top of it; ``viewmats`` that require grad receive their ``[C, 4, 4]`` gradient (pose
 optimisation); ``tile_size`` may be 8, 16 or 32 (16 is the reference's); ``camera_model`` (gsplat 1.4's argument, appended
-last) may be "pinhole" or "ortho" (the orthographic camera of CAD views).
+last) may be "pinhole" or "ortho" (the orthographic camera of CAD views); ``covars`` [N, 3, 3] (a keyword in front of
+``channel_chunk``; restated from memory of gsplat >= 1.3) gives the full 3-D covariances in place of ``quats`` +
+``scales``, which may then be None: only the upper triangle is read, ``covars.grad`` is [N, 3, 3] with zeros below the diagonal (sparse with
+``sparse_grad``), and every other argument -- ``packed``, the render modes, ``sh_degree``, both camera models, the
+``viewmats`` gradient -- works with it.
 
 The stage-by-stage API -- ``fully_fused_projection`` (from ``quats`` + ``scales`` or from ``covars``),
 ``quat_scale_to_covar_preci``, ``isect_tiles``, ``isect_offset_encode``, ``rasterize_to_pixels``,

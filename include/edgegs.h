@@ -60,7 +60,8 @@ typedef void *eg_stream_t; /* hipStream_t */
                                       cameras of eg_project_bwd_cams) */
 #define EG_FLAG_ORTHO 128u           /* orthographic camera (gsplat camera_model="ortho") on the operator path -- eg_project_fwd /       \
                                       _bwd and their _cams forms, eg_project_bwd_viewmats, eg_packed_count / _write / _bwd /        \
-                                      _bwd_sparse, eg_project_covars_{fwd,bwd}_cams_flags: mean2d = (fx x + cx, fy y + cy), J =      \
+                                      _bwd_sparse and their _covars forms, eg_project_covars_{fwd,bwd}_cams_flags,                  \
+                                      eg_project_covars_bwd_viewmats: mean2d = (fx x + cx, fy y + cy), J =                          \
                                       [[fx, 0, 0], [0, fy, 0]] (no division by z, no fov clamp; Ks in pixels per world unit), culls,  \
                                       depth = z and everything behind cov2d as under the pinhole.  The same bit goes to the forward   \
                                       and its backward.  Every other entry that takes caller flags refuses it with EG_ERR_ARG */
@@ -765,6 +766,37 @@ int eg_packed_bwd_sparse(const float *means, const float *quats, const float *sc
                          const float *g2d /*[nnz,8]*/, const float *v_comps /*[nnz]*/, const float *v_depths /*[nnz] or NULL*/,
                          float *v_means /*[nnz,3]*/, float *v_quats /*[nnz,4]*/, float *v_scales /*[nnz,3]*/,
                          eg_stream_t stream);
+/* The covariance form (rasterization(covars=[N,3,3], packed=True)): covars [N,6], the upper triangle (00, 01, 02, 11, 12,
+ * 22) of the world covariance, in place of quats + scales.  The kept pairs are exactly the set radii[c, n] > 0 of
+ * eg_project_covars_fwd_cams_flags with the same arguments, with its values bit for bit; flags: EG_FLAG_ANTIALIASED
+ * (the record's opacity is opacities[n] * compensation, and v_comps is read) and EG_FLAG_ORTHO.  Arguments, layouts,
+ * scratch, order and NULL rules as the four entries above; eg_packed_bin serves both forms.
+ * eg_packed_bwd_covars: v_means [N, 3] and v_covars [N, 6] (an off-diagonal entry stands for both symmetric entries, as
+ *   eg_project_covars_bwd_cams writes it), summed over the cameras in camera order in registers, every row written.
+ * eg_packed_bwd_sparse_covars: the same VJP per pair: v_means [nnz, 3], v_covars [nnz, 6]. */
+int eg_packed_count_covars(const float *means, const float *covars /*[N,6]*/, const float *viewmats /*[C,4,4]*/,
+                           const float *Ks /*[C,3,3]*/, int32_t N, int32_t C, int32_t width, int32_t height,
+                           float near_plane, float far_plane, float eps2d, float radius_clip, uint32_t flags,
+                           int32_t *block_base /*[C*ceil(N/256)]*/, int64_t *indptr /*[C+1]*/, eg_stream_t stream);
+int eg_packed_write_covars(const float *means, const float *covars /*[N,6]*/, const float *opacities,
+                           const float *viewmats, const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height,
+                           float near_plane, float far_plane, float eps2d, float radius_clip, uint32_t flags,
+                           const int32_t *block_base, int64_t nnz, float *splat /*[nnz,8]*/, int32_t *radii,
+                           float *means2d, float *depths, float *conics, float *compensations,
+                           int32_t *tiles_per_gauss, int64_t *camera_ids, int64_t *gaussian_ids,
+                           int32_t *tile_counts /*[C,T]*/, eg_stream_t stream);
+int eg_packed_bwd_covars(const float *means, const float *covars /*[N,6]*/, const float *viewmats, const float *Ks,
+                         int32_t N, int32_t C, int32_t width, int32_t height, float eps2d, uint32_t flags,
+                         const int64_t *indptr /*[C+1], device*/, int64_t nnz, const int64_t *gaussian_ids,
+                         const float *g2d /*[nnz,8]*/, const float *v_comps /*[nnz]*/,
+                         const float *v_depths /*[nnz] or NULL*/, float *v_means /*[N,3]*/, float *v_covars /*[N,6]*/,
+                         eg_stream_t stream);
+int eg_packed_bwd_sparse_covars(const float *means, const float *covars /*[N,6]*/, const float *viewmats,
+                                const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height, float eps2d,
+                                uint32_t flags, int64_t nnz, const int64_t *camera_ids, const int64_t *gaussian_ids,
+                                const float *g2d /*[nnz,8]*/, const float *v_comps /*[nnz]*/,
+                                const float *v_depths /*[nnz] or NULL*/, float *v_means /*[nnz,3]*/,
+                                float *v_covars /*[nnz,6]*/, eg_stream_t stream);
 
 /* ---- tile sizes 8 and 32 (rasterization(tile_size=8 | 32)), csrc/tiles.hip.  Every entry above works on 16 x 16 pixel
  * tiles (EG_TILE); these take the tile size as an argument, with gsplat's meaning: tile_width = ceil(width / tile_size),
@@ -835,6 +867,21 @@ int eg_project_bwd_viewmats(const float *means, const float *quats, const float 
                             const float *g2d, const float *v_comps, const float *v_depths /*NULL ok*/,
                             float *scratch /*[C,scratch_blocks,12]*/, int32_t scratch_blocks,
                             float *v_viewmats /*[C,4,4]*/, eg_stream_t stream);
+/* The covariance form: covars [N,6] (upper triangle) in place of quats + scales.  With cc = R_c S R_c^T the
+ * camera-space covariance and v_cc its cotangent:  v_R[c] += v_t mean^T + (v_cc + v_cc^T) R_c S,  v_tr[c] += v_t.
+ *   dense   radii [C, N] (eg_project_covars_fwd_cams_flags: the pair is visible when its radius is positive), g2d
+ *           [C, N, 8] (words 0-1 v_means2d, 4-6 v_conics), v_comps [C, N], v_depths [C, N] or NULL; indptr and
+ *           gaussian_ids NULL, nnz 0;
+ *   packed  radii NULL; indptr, nnz, gaussian_ids, g2d, v_comps, v_depths as eg_packed_bwd_covars takes them.
+ * flags: EG_FLAG_ANTIALIASED (v_comps is read; it may be NULL without) and EG_FLAG_ORTHO.  Scratch, sums, the zero bottom
+ * row and the refusals as above; the fold kernel is the same. */
+int eg_project_covars_bwd_viewmats(const float *means, const float *covars /*[N,6]*/, const float *viewmats,
+                                   const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height, float eps2d,
+                                   uint32_t flags, const int32_t *radii /*[C,N] or NULL = packed*/,
+                                   const int64_t *indptr /*[C+1], device*/, int64_t nnz, const int64_t *gaussian_ids,
+                                   const float *g2d, const float *v_comps, const float *v_depths /*NULL ok*/,
+                                   float *scratch /*[C,scratch_blocks,12]*/, int32_t scratch_blocks,
+                                   float *v_viewmats /*[C,4,4]*/, eg_stream_t stream);
 
 /* ---- the drop-in operator's fast path in two calls (edgegaussians_amd/rasterizer.py: the reference's own call of
  * gsplat.rasterization -- one camera, colours == 1 without grad, edge_gs.py:247-279 -- and its autograd backward).
