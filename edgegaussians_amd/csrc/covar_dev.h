@@ -1,10 +1,21 @@
 // Device code of the projection from covariances shared by functional.hip (the dense backward), packed.hip (the packed
 // backwards) and viewmat_grad.hip (the camera-pose gradient): the reverse sweep of ONE visible (camera, Gaussian) pair
-// behind forward_geom_covar (csrc/project_dev.h).  Every kernel that inlines it forms the same rounding sequence.
+// behind forward_geom_covar (csrc/project_dev.h), built from the steps it shares with backward_geom.  Every kernel that
+// inlines it forms the same rounding sequence.  CovarForm (bottom) is what the kernels written once for both shape forms
+// (packed.hip, viewmat_grad.hip) know of this one.
 #pragma once
 #include "project_dev.h"
 
 namespace eg {
+
+// world mean m[3] and covariance cv[6] (upper triangle) of Gaussian g
+__device__ __forceinline__ void load_mean_covar(const float *__restrict__ means, const float *__restrict__ covars, int g,
+                                                float (&m)[3], float (&cv)[6]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) m[k] = means[3 * (size_t)g + k];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) cv[k] = covars[6 * (size_t)g + k];
+}
 
 // the cotangents of one pair's projection outputs (has_comp: the compensation has a cotangent at all)
 struct CovarCot {
@@ -42,58 +53,30 @@ __device__ __forceinline__ void covar_pair_vjp(const Cam &cam, const float *m, c
 #pragma clang fp contract(off)  // (the same bits whatever the compiler makes of the caller's camera loop)
   const float vx = ct.vx, vy = ct.vy;
   const float va = ct.va, vb = ct.vb, vc = ct.vc;
-  // conic = B^-1  =>  G = -A V A with V = [[va, vb/2],[vb/2, vc]] (b is stored once): backward_geom's sweep
-  const float hb = 0.5f * vb;
-  const float av00 = f.a * va + f.b * hb, av01 = f.a * hb + f.b * vc;
-  const float av10 = f.b * va + f.c * hb, av11 = f.b * hb + f.c * vc;
-  float G00 = -(av00 * f.a + av01 * f.b);
-  float G01 = -(av00 * f.b + av01 * f.c);
-  float G11 = -(av10 * f.b + av11 * f.c);
-  if (ct.has_comp) {
-    // gsplat's 0.5 v / (comp + 1e-6); nothing where the determinant ratio is negative (comp is clamped to 0 there)
-    const float det_conic = f.a * f.c - f.b * f.b;
-    const float vs = (f.det0 / f.det1 >= 0.f) ? ct.v_comp * 0.5f / (f.comp + 1e-6f) : 0.f;
-    const float omc = 1.f - f.comp * f.comp;
-    G00 += vs * (omc * f.a - eps2d * det_conic);
-    G01 += vs * (omc * f.b);
-    G11 += vs * (omc * f.c - eps2d * det_conic);
-  }
+  float G00, G01, G11;
+  conic_vjp(f, va, vb, vc, G00, G01, G11);
+  if (ct.has_comp) comp_vjp<true>(f, eps2d, ct.v_comp, G00, G01, G11);
+  // cov2d = J cc J^T (cc symmetric)  =>  v_cc = J^T G J and -- pinhole -- v_J = 2 G Q with Q = J cc.  Ortho: the
+  // constant J = [[fx, 0, 0], [0, fy, 0]] has no cotangent and v_cc the upper-left block only.
   float vcc[9];
-  float vtx, vty, vtz;
+  float vJ00 = 0.f, vJ02 = 0.f, vJ11 = 0.f, vJ12 = 0.f;
+  vcc[0] = f.J00 * f.J00 * G00;
+  vcc[1] = vcc[3] = f.J00 * f.J11 * G01;
+  vcc[4] = f.J11 * f.J11 * G11;
   if constexpr (CM == kOrtho) {
-    // cov2d = J cc J^T with the constant J = [[fx, 0, 0], [0, fy, 0]]: v_cc = J^T G J has the upper-left block only;
-    // camera-space mean: through mean2d and the depth
-    vcc[0] = f.J00 * f.J00 * G00;
-    vcc[1] = vcc[3] = f.J00 * f.J11 * G01;
-    vcc[4] = f.J11 * f.J11 * G11;
     vcc[2] = vcc[6] = vcc[5] = vcc[7] = vcc[8] = 0.f;
-    vtx = cam.fx * vx;
-    vty = cam.fy * vy;
-    vtz = ct.v_depth;
   } else {
-    // cov2d = J cc J^T (cc symmetric)  =>  v_J = 2 G Q with Q = J cc, v_cc = J^T G J
-    const float vJ00 = 2.f * (G00 * q0[0] + G01 * q1[0]);
-    const float vJ02 = 2.f * (G00 * q0[2] + G01 * q1[2]);
-    const float vJ11 = 2.f * (G01 * q0[1] + G11 * q1[1]);
-    const float vJ12 = 2.f * (G01 * q0[2] + G11 * q1[2]);
+    vJ00 = 2.f * (G00 * q0[0] + G01 * q1[0]);
+    vJ02 = 2.f * (G00 * q0[2] + G01 * q1[2]);
+    vJ11 = 2.f * (G01 * q0[1] + G11 * q1[1]);
+    vJ12 = 2.f * (G01 * q0[2] + G11 * q1[2]);
     const float g0 = G00 * f.J02 + G01 * f.J12, g1 = G01 * f.J02 + G11 * f.J12;  // G J[:, 2]
-    vcc[0] = f.J00 * f.J00 * G00;
-    vcc[1] = vcc[3] = f.J00 * f.J11 * G01;
     vcc[2] = vcc[6] = f.J00 * g0;
-    vcc[4] = f.J11 * f.J11 * G11;
     vcc[5] = vcc[7] = f.J11 * g1;
     vcc[8] = f.J02 * g0 + f.J12 * g1;
-    // camera-space mean: through mean2d, the depth and J (fov clamp freezes tx = +-lim z)
-    const float rz3 = f.rz2 * f.rz;
-    vtx = cam.fx * f.rz * vx;
-    vty = cam.fy * f.rz * vy;
-    vtz = -(cam.fx * f.x * vx + cam.fy * f.y * vy) * f.rz2 + ct.v_depth;
-    vtz += -cam.fx * f.rz2 * vJ00 - cam.fy * f.rz2 * vJ11;
-    if (f.in_x) { vtx += -cam.fx * f.rz2 * vJ02; vtz += 2.f * cam.fx * f.tx * rz3 * vJ02; }
-    else        { vtz += cam.fx * f.tx * rz3 * vJ02; }
-    if (f.in_y) { vty += -cam.fy * f.rz2 * vJ12; vtz += 2.f * cam.fy * f.ty * rz3 * vJ12; }
-    else        { vtz += cam.fy * f.ty * rz3 * vJ12; }
   }
+  float vtx, vty, vtz;
+  camera_mean_vjp<CM>(cam, f, vx, vy, ct.v_depth, vJ00, vJ02, vJ11, vJ12, vtx, vty, vtz);
   if constexpr (CAM) {
     // A = Rv S (forward_geom_covar's first product); v_cc is symmetric as built, so v_cc + v_cc^T = 2 v_cc
     const float S[9] = {cv[0], cv[1], cv[2], cv[1], cv[3], cv[4], cv[2], cv[4], cv[5]};
@@ -130,5 +113,68 @@ __device__ __forceinline__ void covar_pair_vjp(const Cam &cam, const float *m, c
     v_cov[e] = (ui[e] == uj[e]) ? vS : 2.f * vS;
   }
 }
+
+// ---------------------------------------------------------------------------------------------
+// The covariance form of a Gaussian's shape (covars [N, 6]), member for member QuatScaleForm's counterpart
+// (csrc/project_dev.h).  The host fills the three pointers (opacities: the write pass only); m, cv, q0, q1 are the
+// kernel's (forward() fills them, pair_vjp reads them).
+struct CovarForm {
+  const float *means, *covars, *opacities;
+  float m[3], cv[6], q0[3], q1[3];
+
+  using Visible = int;  // the dense layout's radii [C, N]
+  static __device__ __forceinline__ bool visible(const int *radii, long long q) { return radii[q] > 0; }
+
+  template <int CM>
+  __device__ __forceinline__ bool forward(const Cam &cam, int g, int width, int height, float near_plane,
+                                          float far_plane, float eps2d, uint32_t, Fwd &f) {
+    load_mean_covar(means, covars, g, m, cv);
+    float cc[6];
+    return forward_geom_covar<CM>(cam, m, cv, width, height, near_plane, far_plane, eps2d, f, cc, q0, q1);
+  }
+  // (forward_geom_covar does not fill f.o: the record's opacity comes straight from opacities[g])
+  __device__ __forceinline__ float opacity(const Fwd &, int g) const { return opacities[g]; }
+
+  // one row of v_means [*, 3], v_covars [*, 6]
+  struct Out {
+    float *v_means, *v_covars;
+  };
+  struct Grad {
+    float mean[3], cov[6];
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) mean[k] = 0.f;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) cov[k] = 0.f;
+    }
+    __device__ __forceinline__ void operator+=(const Grad &o) {
+#pragma clang fp contract(off)  // (the same bits whatever the compiler makes of the caller's camera loop)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) mean[k] += o.mean[k];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) cov[k] += o.cov[k];
+    }
+    __device__ __forceinline__ void store(const Out &out, long long row) const {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) out.v_means[3 * row + k] = mean[k];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) out.v_covars[6 * row + k] = cov[k];
+    }
+  };
+
+  // pair p = (cam, g) of a visible list: its share of the row's gradient, or (CAM) the camera's share in v_cam[12].
+  // Near / far passed in the forward, so the recomputation runs with open limits; should its det cull strike, `gr` and
+  // `v_cam` stay as the caller zeroed them.  The compensation has a cotangent under EG_FLAG_ANTIALIASED only.
+  template <bool CAM, int CM>
+  __device__ __forceinline__ void pair_vjp(const Cam &cam, int g, long long p, int width, int height, float eps2d,
+                                           uint32_t flags, const float4 *__restrict__ g2d,
+                                           const float *__restrict__ v_comps, const float *__restrict__ v_depths,
+                                           Grad &gr, float *v_cam = nullptr) {
+    Fwd f;
+    if (!forward<CM>(cam, g, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f)) return;
+    const CovarCot ct = load_covar_cot(g2d, v_comps, v_depths, p, flags & EG_FLAG_ANTIALIASED);
+    covar_pair_vjp<CAM, CM>(cam, m, cv, f, q0, q1, eps2d, ct, gr.mean, gr.cov, v_cam);
+  }
+};
 
 }  // namespace eg

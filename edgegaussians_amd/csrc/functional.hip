@@ -186,10 +186,7 @@ project_covars_fwd_kernel(const float *__restrict__ means, const float *__restri
   const int c = blockIdx.y;
   const Cam cam = load_cam(viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c);
   float m[3], cv[6], cc[6], q0[3], q1[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) m[k] = means[3 * (size_t)g + k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) cv[k] = covars[6 * (size_t)g + k];
+  load_mean_covar(means, covars, g, m, cv);
   Fwd f;
   int radius = 0;
   if (forward_geom_covar<CM>(cam, m, cv, width, height, near_plane, far_plane, eps2d, f, cc, q0, q1))
@@ -218,10 +215,7 @@ project_covars_bwd_kernel(const float *__restrict__ means, const float *__restri
   const int g = blockIdx.x * kFn + threadIdx.x;
   if (g >= N) return;
   float m[3], cv[6];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) m[k] = means[3 * (size_t)g + k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) cv[k] = covars[6 * (size_t)g + k];
+  load_mean_covar(means, covars, g, m, cv);
   float am[3] = {0.f, 0.f, 0.f}, ac[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int c = 0; c < C; ++c) {
     const size_t p = (size_t)c * N + g;
@@ -301,6 +295,31 @@ extern "C" int eg_quat_scale_to_covar_preci_bwd(const float *quats, const float 
   return check_launch("quat_scale_to_covar_preci_bwd");
 }
 
+// the two launches behind both entry pairs; the camera model comes from the flags (0 = pinhole)
+static void launch_project_covars_fwd(const float *means, const float *covars, const float *viewmats, const float *Ks,
+                                      int32_t N, int32_t C, int32_t width, int32_t height, float near_plane,
+                                      float far_plane, float eps2d, float radius_clip, int32_t *radii, float *means2d,
+                                      float *depths, float *conics, float *compensations, uint32_t flags,
+                                      eg_stream_t stream) {
+  with_cam_model(flags, [&](auto cm) {
+    project_covars_fwd_kernel<decltype(cm)::value><<<dim3(cdiv(N, kFn), C), kFn, 0, as_stream(stream)>>>(
+        means, covars, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip, radii, means2d, depths,
+        conics, compensations);
+  });
+}
+
+static void launch_project_covars_bwd(const float *means, const float *covars, const float *viewmats, const float *Ks,
+                                      int32_t N, int32_t C, int32_t width, int32_t height, float eps2d,
+                                      const int32_t *radii, const float *v_means2d, const float *v_depths,
+                                      const float *v_conics, const float *v_compensations, float *v_means,
+                                      float *v_covars, uint32_t flags, eg_stream_t stream) {
+  with_cam_model(flags, [&](auto cm) {
+    project_covars_bwd_kernel<decltype(cm)::value><<<cdiv(N, kFn), kFn, 0, as_stream(stream)>>>(
+        means, covars, viewmats, Ks, N, C, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_compensations,
+        v_means, v_covars);
+  });
+}
+
 extern "C" int eg_project_covars_fwd_cams(const float *means, const float *covars, const float *viewmats,
                                           const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height,
                                           float near_plane, float far_plane, float eps2d, float radius_clip,
@@ -309,13 +328,12 @@ extern "C" int eg_project_covars_fwd_cams(const float *means, const float *covar
   EG_REQUIRE(N >= 0 && C >= 1 && C <= 65535 && width > 0 && height > 0, "bad sizes");
   if (N == 0) return EG_OK;
   EG_REQUIRE(means && covars && viewmats && Ks && radii && means2d && depths && conics, "null pointer");
-  project_covars_fwd_kernel<kPinhole><<<dim3(cdiv(N, kFn), C), kFn, 0, as_stream(stream)>>>(
-      means, covars, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip, radii, means2d, depths,
-      conics, compensations);
+  launch_project_covars_fwd(means, covars, viewmats, Ks, N, C, width, height, near_plane, far_plane, eps2d, radius_clip,
+                            radii, means2d, depths, conics, compensations, 0, stream);
   return check_launch("project_covars_fwd_cams");
 }
 
-// the same projection with a camera model: flags = 0 (pinhole, the kernels above) or EG_FLAG_ORTHO
+// the same projection with a camera model: flags = 0 (pinhole) or EG_FLAG_ORTHO
 extern "C" int eg_project_covars_fwd_cams_flags(const float *means, const float *covars, const float *viewmats,
                                                 const float *Ks, int32_t N, int32_t C, int32_t width, int32_t height,
                                                 float near_plane, float far_plane, float eps2d, float radius_clip,
@@ -325,15 +343,8 @@ extern "C" int eg_project_covars_fwd_cams_flags(const float *means, const float 
   EG_REQUIRE(!(flags & ~EG_FLAG_ORTHO), "flags: EG_FLAG_ORTHO or 0");
   if (N == 0) return EG_OK;
   EG_REQUIRE(means && covars && viewmats && Ks && radii && means2d && depths && conics, "null pointer");
-  const dim3 grid(cdiv(N, kFn), C);
-  if (flags & EG_FLAG_ORTHO)
-    project_covars_fwd_kernel<kOrtho><<<grid, kFn, 0, as_stream(stream)>>>(
-        means, covars, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip, radii, means2d, depths,
-        conics, compensations);
-  else
-    project_covars_fwd_kernel<kPinhole><<<grid, kFn, 0, as_stream(stream)>>>(
-        means, covars, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip, radii, means2d, depths,
-        conics, compensations);
+  launch_project_covars_fwd(means, covars, viewmats, Ks, N, C, width, height, near_plane, far_plane, eps2d, radius_clip,
+                            radii, means2d, depths, conics, compensations, flags, stream);
   return check_launch("project_covars_fwd_cams_flags");
 }
 
@@ -345,9 +356,8 @@ extern "C" int eg_project_covars_bwd_cams(const float *means, const float *covar
   EG_REQUIRE(N >= 0 && C >= 1 && width > 0 && height > 0, "bad sizes");
   if (N == 0) return EG_OK;
   EG_REQUIRE(means && covars && viewmats && Ks && radii && v_means2d && v_conics && v_means && v_covars, "null pointer");
-  project_covars_bwd_kernel<kPinhole><<<cdiv(N, kFn), kFn, 0, as_stream(stream)>>>(
-      means, covars, viewmats, Ks, N, C, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_compensations,
-      v_means, v_covars);
+  launch_project_covars_bwd(means, covars, viewmats, Ks, N, C, width, height, eps2d, radii, v_means2d, v_depths, v_conics,
+                            v_compensations, v_means, v_covars, 0, stream);
   return check_launch("project_covars_bwd_cams");
 }
 
@@ -361,14 +371,8 @@ extern "C" int eg_project_covars_bwd_cams_flags(const float *means, const float 
   EG_REQUIRE(!(flags & ~EG_FLAG_ORTHO), "flags: EG_FLAG_ORTHO or 0");
   if (N == 0) return EG_OK;
   EG_REQUIRE(means && covars && viewmats && Ks && radii && v_means2d && v_conics && v_means && v_covars, "null pointer");
-  if (flags & EG_FLAG_ORTHO)
-    project_covars_bwd_kernel<kOrtho><<<cdiv(N, kFn), kFn, 0, as_stream(stream)>>>(
-        means, covars, viewmats, Ks, N, C, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_compensations,
-        v_means, v_covars);
-  else
-    project_covars_bwd_kernel<kPinhole><<<cdiv(N, kFn), kFn, 0, as_stream(stream)>>>(
-        means, covars, viewmats, Ks, N, C, width, height, eps2d, radii, v_means2d, v_depths, v_conics, v_compensations,
-        v_means, v_covars);
+  launch_project_covars_bwd(means, covars, viewmats, Ks, N, C, width, height, eps2d, radii, v_means2d, v_depths, v_conics,
+                            v_compensations, v_means, v_covars, flags, stream);
   return check_launch("project_covars_bwd_cams_flags");
 }
 

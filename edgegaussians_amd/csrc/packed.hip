@@ -21,7 +21,13 @@
 //
 // Scratch: 4 bytes per 256 pairs (the workgroup counts).  Nothing of size C * N is allocated.
 //
-// Every pass but scan / bin exists in a second form for covariances (eg_packed_*_covars, below the quats + scales kernels).
+// Count, write and the two backwards are templates over the form the Gaussian's shape arrives in: QuatScaleForm
+// (csrc/project_dev.h) behind eg_packed_*, CovarForm (csrc/covar_dev.h; gsplat `rasterization(covars=[N, 3, 3])`, the
+// upper triangle covars [N, 6]) behind eg_packed_*_covars.  A form brings its inputs, the forward of a pair, the
+// record's opacity, its gradient row and the pair's reverse sweep; everything else -- grids, ranking, histogram, guards,
+// the order of the sums -- is written once.  The covariance form's keep decision is forward_geom_covar + radius_of with
+// the arguments of project_covars_fwd_kernel (csrc/functional.hip): its kept set is the set radii > 0 of
+// eg_project_covars_fwd_cams_flags, every kept value bit for bit.
 #include "common.h"
 #include "covar_dev.h"
 #include "project_dev.h"
@@ -30,32 +36,31 @@ namespace eg {
 
 constexpr int kPk = 256;  // threads (= Gaussians) per workgroup of the count and write passes
 
+// the cameras and the projection's scalars, as every kernel here takes them (the backwards read no cull limit)
+struct PackedView {
+  const float *viewmats, *Ks;
+  int N, C, width, height;
+  float near_plane, far_plane, eps2d, radius_clip;
+  uint32_t flags;
+};
+
 // this thread's Gaussian in camera blockIdx.y: radius after every cull (0 = not kept).  CM: the camera model
 // (csrc/project_dev.h) of every kernel here, kOrtho with EG_FLAG_ORTHO.
-template <int CM>
-__device__ __forceinline__ int packed_project(const float *__restrict__ means, const float *__restrict__ quats,
-                                              const float *__restrict__ scales, const float *__restrict__ opacities,
-                                              const float *__restrict__ viewmats, const float *__restrict__ Ks, int N,
-                                              int width, int height, float near_plane, float far_plane, float eps2d,
-                                              float radius_clip, uint32_t flags, int g, Fwd &f) {
-  if (g >= N) return 0;
-  const Cam cam = load_cam(viewmats + 16 * (size_t)blockIdx.y, Ks + 9 * (size_t)blockIdx.y);
-  if (!forward_geom<CM>(cam, means, quats, scales, opacities, g, width, height, near_plane, far_plane, eps2d, flags, f))
-    return 0;
-  return radius_of(f, width, height, radius_clip);
+template <class Form, int CM>
+__device__ __forceinline__ int packed_project(Form &form, const PackedView &v, int g, Fwd &f) {
+  if (g >= v.N) return 0;
+  const Cam cam = load_cam(v.viewmats + 16 * (size_t)blockIdx.y, v.Ks + 9 * (size_t)blockIdx.y);
+  if (!form.template forward<CM>(cam, g, v.width, v.height, v.near_plane, v.far_plane, v.eps2d, v.flags, f)) return 0;
+  return radius_of(f, v.width, v.height, v.radius_clip);
 }
 
-template <int CM>
+template <class Form, int CM>
 __global__ void __launch_bounds__(kPk)
-packed_count_kernel(const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
-                    const float *__restrict__ opacities, const float *__restrict__ viewmats,
-                    const float *__restrict__ Ks, int N, int width, int height, float near_plane, float far_plane,
-                    float eps2d, float radius_clip, uint32_t flags, int *__restrict__ block_counts) {
+packed_count_kernel(Form form, const PackedView v, int *__restrict__ block_counts) {
   __shared__ int s_wave[kPk / 64];
   const int g = blockIdx.x * kPk + threadIdx.x;
   Fwd f;
-  const int radius = packed_project<CM>(means, quats, scales, opacities, viewmats, Ks, N, width, height, near_plane,
-                                        far_plane, eps2d, radius_clip, flags, g, f);
+  const int radius = packed_project<Form, CM>(form, v, g, f);
   const unsigned long long vote = __ballot(radius > 0);
   if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(vote);
   __syncthreads();
@@ -87,27 +92,30 @@ packed_scan_kernel(int *__restrict__ block_counts, int nb, int C, long long *__r
   if (threadIdx.x == 0) indptr[C] = carry;
 }
 
-template <bool LDS_COUNT, int CM>
+// the outputs of the write pass, one row per kept pair (tile_counts: [C, T])
+struct PackedOut {
+  float4 *splat;
+  int *radii;
+  float *means2d, *depths, *conics, *comps;
+  int *tiles_per_gauss;
+  long long *camera_ids, *gaussian_ids;
+  int *tile_counts;
+};
+
+template <class Form, bool LDS_COUNT, int CM>
 __global__ void __launch_bounds__(kPk)
-packed_write_kernel(const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
-                    const float *__restrict__ opacities, const float *__restrict__ viewmats,
-                    const float *__restrict__ Ks, int N, int width, int height, float near_plane, float far_plane,
-                    float eps2d, float radius_clip, uint32_t flags, const int *__restrict__ block_base, long long nnz,
-                    float4 *__restrict__ splat, int *__restrict__ radii, float *__restrict__ means2d,
-                    float *__restrict__ depths, float *__restrict__ conics, float *__restrict__ comps,
-                    int *__restrict__ tiles_per_gauss, long long *__restrict__ camera_ids,
-                    long long *__restrict__ gaussian_ids, int *__restrict__ tile_counts) {
+packed_write_kernel(Form form, const PackedView v, const int *__restrict__ block_base, long long nnz,
+                    const PackedOut o) {
   extern __shared__ __attribute__((aligned(16))) int s_hist[];
   __shared__ int s_wave[kPk / 64];
-  const int tw = (width + kTile - 1) / kTile, th = (height + kTile - 1) / kTile, T = tw * th;
-  tile_counts += (size_t)blockIdx.y * T;
+  const int tw = (v.width + kTile - 1) / kTile, th = (v.height + kTile - 1) / kTile, T = tw * th;
+  int *tile_counts = o.tile_counts + (size_t)blockIdx.y * T;
   if (LDS_COUNT) {
     for (int t = threadIdx.x; t < T; t += kPk) s_hist[t] = 0;
   }
   const int g = blockIdx.x * kPk + threadIdx.x;
   Fwd f;
-  const int radius = packed_project<CM>(means, quats, scales, opacities, viewmats, Ks, N, width, height, near_plane,
-                                        far_plane, eps2d, radius_clip, flags, g, f);
+  const int radius = packed_project<Form, CM>(form, v, g, f);
   const bool keep = radius > 0;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const unsigned long long vote = __ballot(keep);
@@ -119,19 +127,20 @@ packed_write_kernel(const float *__restrict__ means, const float *__restrict__ q
     long long p = block_base[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + __popcll(vote & ((1ull << lane) - 1ull));
     for (int w = 0; w < wv; ++w) p += s_wave[w];
     if (p >= 0 && p < nnz) {  // (always: nnz is the sum the bases were scanned from -- a guard against a caller's stale scratch)
-      const bool aa = flags & EG_FLAG_ANTIALIASED;
-      splat[2 * p] = make_float4(f.u, f.v, f.a, f.b);
-      splat[2 * p + 1] = make_float4(f.c, aa ? f.o * f.comp : f.o, f.z, __int_as_float(radius));
-      radii[p] = radius;
-      means2d[2 * p] = f.u; means2d[2 * p + 1] = f.v;
-      depths[p] = f.z;
-      conics[3 * p] = f.a; conics[3 * p + 1] = f.b; conics[3 * p + 2] = f.c;
-      comps[p] = f.comp;
-      camera_ids[p] = blockIdx.y;
-      gaussian_ids[p] = g;
+      const bool aa = v.flags & EG_FLAG_ANTIALIASED;
+      const float op = form.opacity(f, g);
+      o.splat[2 * p] = make_float4(f.u, f.v, f.a, f.b);
+      o.splat[2 * p + 1] = make_float4(f.c, aa ? op * f.comp : op, f.z, __int_as_float(radius));
+      o.radii[p] = radius;
+      o.means2d[2 * p] = f.u; o.means2d[2 * p + 1] = f.v;
+      o.depths[p] = f.z;
+      o.conics[3 * p] = f.a; o.conics[3 * p + 1] = f.b; o.conics[3 * p + 2] = f.c;
+      o.comps[p] = f.comp;
+      o.camera_ids[p] = blockIdx.y;
+      o.gaussian_ids[p] = g;
       int x0, y0, x1, y1;
       tile_box(f.u, f.v, radius, tw, th, x0, y0, x1, y1);
-      tiles_per_gauss[p] = (y1 - y0) * (x1 - x0);
+      o.tiles_per_gauss[p] = (y1 - y0) * (x1 - x0);
       for (int ty = y0; ty < y1; ++ty)
         for (int tx = x0; tx < x1; ++tx) atomicAdd(LDS_COUNT ? &s_hist[ty * tw + tx] : &tile_counts[ty * tw + tx], 1);
     }
@@ -155,242 +164,30 @@ packed_rebase_kernel(int *__restrict__ flatten_ids, long long *__restrict__ isec
   if (isect_ids) isect_ids[i] |= camera_bits;
 }
 
-template <int CM>
-__device__ __forceinline__ void packed_pair_vjp(const float *__restrict__ means, const float *__restrict__ quats,
-                                                const float *__restrict__ scales, const float *__restrict__ opacities,
-                                                const float *__restrict__ viewmats, const float *__restrict__ Ks,
-                                                int cam_id, int g, long long p, int width, int height, float eps2d,
-                                                uint32_t flags, const float4 *__restrict__ g2d,
-                                                const float *__restrict__ v_comps, const float *__restrict__ v_depths,
-                                                Grads &gr) {
-  const Cam cam = load_cam(viewmats + 16 * (size_t)cam_id, Ks + 9 * (size_t)cam_id);
-  const float4 ga = g2d[2 * p], gb = g2d[2 * p + 1];
-  Fwd f;
-  // near / far and det culls already passed in the forward (the pair exists), so pass open limits
-  forward_geom<CM>(cam, means, quats, scales, opacities, g, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f);
-  backward_geom<false, CM>(cam, f, eps2d, flags, ga, gb, true, v_comps[p], v_depths ? v_depths[p] : 0.f, gr);
-}
-
-template <int CM>
-__global__ void __launch_bounds__(256)
-packed_bwd_dense_kernel(const float *__restrict__ means, const float *__restrict__ quats,
-                        const float *__restrict__ scales, const float *__restrict__ opacities,
-                        const float *__restrict__ viewmats, const float *__restrict__ Ks, int N, int C, int width,
-                        int height, float eps2d, uint32_t flags, const long long *__restrict__ indptr, long long nnz,
-                        const long long *__restrict__ gaussian_ids, const float4 *__restrict__ g2d,
-                        const float *__restrict__ v_comps, const float *__restrict__ v_depths,
-                        float *__restrict__ v_means, float *__restrict__ v_quats, float *__restrict__ v_scales) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= N) return;
-  Grads acc;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) acc.mean[k] = acc.scale[k] = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) acc.quat[k] = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const long long end = min(indptr[c + 1], nnz);  // (indptr is the scan's: a guard against a caller's stale array)
-    long long lo = max(0ll, indptr[c]);
-    long long hi = end;
-    while (lo < hi) {  // first position whose id is >= g
-      const long long mid = lo + ((hi - lo) >> 1);
-      if (gaussian_ids[mid] < g) lo = mid + 1; else hi = mid;
-    }
-    if (lo >= end || gaussian_ids[lo] != g) continue;
-    Grads gr;
-    packed_pair_vjp<CM>(means, quats, scales, opacities, viewmats, Ks, c, g, lo, width, height, eps2d, flags, g2d, v_comps,
-                        v_depths, gr);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { acc.mean[k] += gr.mean[k]; acc.scale[k] += gr.scale[k]; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc.quat[k] += gr.quat[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { v_means[3 * g + k] = acc.mean[k]; v_scales[3 * g + k] = acc.scale[k]; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v_quats[4 * g + k] = acc.quat[k];
-}
-
-template <int CM>
-__global__ void __launch_bounds__(256)
-packed_bwd_sparse_kernel(const float *__restrict__ means, const float *__restrict__ quats,
-                         const float *__restrict__ scales, const float *__restrict__ opacities,
-                         const float *__restrict__ viewmats, const float *__restrict__ Ks, int N, int C, int width,
-                         int height, float eps2d, uint32_t flags, long long nnz,
-                         const long long *__restrict__ camera_ids, const long long *__restrict__ gaussian_ids,
-                         const float4 *__restrict__ g2d, const float *__restrict__ v_comps,
-                         const float *__restrict__ v_depths, float *__restrict__ v_means, float *__restrict__ v_quats,
-                         float *__restrict__ v_scales) {
-  const long long p = blockIdx.x * 256ll + threadIdx.x;
-  if (p >= nnz) return;
-  const long long c = camera_ids[p], g = gaussian_ids[p];
-  Grads gr;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) gr.mean[k] = gr.scale[k] = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) gr.quat[k] = 0.f;
-  if (c >= 0 && c < C && g >= 0 && g < N)  // (ids written by packed_write_kernel: a guard against a caller's stale arrays)
-    packed_pair_vjp<CM>(means, quats, scales, opacities, viewmats, Ks, (int)c, (int)g, p, width, height, eps2d, flags, g2d,
-                        v_comps, v_depths, gr);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { v_means[3 * p + k] = gr.mean[k]; v_scales[3 * p + k] = gr.scale[k]; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v_quats[4 * p + k] = gr.quat[k];
-}
-
-// ---------------------------------------------------------------------------------------------
-// The covariance form (gsplat `rasterization(covars=[N, 3, 3])`): the world covariance arrives as its upper triangle
-// covars [N, 6] instead of quats + scales.  The keep decision is forward_geom_covar + radius_of with the arguments of
-// project_covars_fwd_kernel (csrc/functional.hip), so the kept set is the set radii > 0 of eg_project_covars_fwd_cams_flags
-// and every kept value is its value, bit for bit.  Same grids, ranking, histogram and order of sums as the kernels above.
-struct CovarGeom {
-  float m[3], cv[6], q0[3], q1[3];
+// the cotangents of the pairs: the [nnz, 8] record of the compositing backwards, v_comps [nnz], v_depths [nnz] (NULL ok)
+struct PackedCot {
+  const float4 *g2d;
+  const float *v_comps, *v_depths;
 };
 
-// Gaussian g in camera `cam_id`: the forward of the pair (false = culled); m and cv are loaded on the way
-template <int CM>
-__device__ __forceinline__ bool packed_geom_covar(const float *__restrict__ means, const float *__restrict__ covars,
-                                                  const float *__restrict__ viewmats, const float *__restrict__ Ks,
-                                                  int cam_id, int g, int width, int height, float near_plane,
-                                                  float far_plane, float eps2d, Cam &cam, CovarGeom &cg, Fwd &f) {
-  cam = load_cam(viewmats + 16 * (size_t)cam_id, Ks + 9 * (size_t)cam_id);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) cg.m[k] = means[3 * (size_t)g + k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) cg.cv[k] = covars[6 * (size_t)g + k];
-  float cc[6];
-  return forward_geom_covar<CM>(cam, cg.m, cg.cv, width, height, near_plane, far_plane, eps2d, f, cc, cg.q0, cg.q1);
+// pair p = (cam_id, g): its share of row g's gradient (zero on entry)
+template <class Form, int CM>
+__device__ __forceinline__ void packed_pair_vjp(Form &form, const PackedView &v, int cam_id, int g, long long p,
+                                                const PackedCot &ct, typename Form::Grad &gr) {
+  const Cam cam = load_cam(v.viewmats + 16 * (size_t)cam_id, v.Ks + 9 * (size_t)cam_id);
+  form.template pair_vjp<false, CM>(cam, g, p, v.width, v.height, v.eps2d, v.flags, ct.g2d, ct.v_comps, ct.v_depths, gr);
 }
 
-// radius after every cull (0 = not kept) of this thread's Gaussian in camera blockIdx.y
-template <int CM>
-__device__ __forceinline__ int packed_project_covar(const float *__restrict__ means, const float *__restrict__ covars,
-                                                    const float *__restrict__ viewmats, const float *__restrict__ Ks,
-                                                    int N, int width, int height, float near_plane, float far_plane,
-                                                    float eps2d, float radius_clip, int g, Fwd &f) {
-  if (g >= N) return 0;
-  Cam cam;
-  CovarGeom cg;
-  if (!packed_geom_covar<CM>(means, covars, viewmats, Ks, blockIdx.y, g, width, height, near_plane, far_plane, eps2d, cam,
-                             cg, f))
-    return 0;
-  return radius_of(f, width, height, radius_clip);
-}
-
-template <int CM>
-__global__ void __launch_bounds__(kPk)
-packed_count_covars_kernel(const float *__restrict__ means, const float *__restrict__ covars,
-                           const float *__restrict__ viewmats, const float *__restrict__ Ks, int N, int width,
-                           int height, float near_plane, float far_plane, float eps2d, float radius_clip,
-                           int *__restrict__ block_counts) {
-  __shared__ int s_wave[kPk / 64];
-  const int g = blockIdx.x * kPk + threadIdx.x;
-  Fwd f;
-  const int radius = packed_project_covar<CM>(means, covars, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d,
-                                              radius_clip, g, f);
-  const unsigned long long vote = __ballot(radius > 0);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(vote);
-  __syncthreads();
-  if (threadIdx.x == 0)
-    block_counts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-}
-
-// (forward_geom_covar does not fill f.o: the record's opacity comes straight from opacities[g])
-template <bool LDS_COUNT, int CM>
-__global__ void __launch_bounds__(kPk)
-packed_write_covars_kernel(const float *__restrict__ means, const float *__restrict__ covars,
-                           const float *__restrict__ opacities, const float *__restrict__ viewmats,
-                           const float *__restrict__ Ks, int N, int width, int height, float near_plane,
-                           float far_plane, float eps2d, float radius_clip, uint32_t flags,
-                           const int *__restrict__ block_base, long long nnz, float4 *__restrict__ splat,
-                           int *__restrict__ radii, float *__restrict__ means2d, float *__restrict__ depths,
-                           float *__restrict__ conics, float *__restrict__ comps, int *__restrict__ tiles_per_gauss,
-                           long long *__restrict__ camera_ids, long long *__restrict__ gaussian_ids,
-                           int *__restrict__ tile_counts) {
-  extern __shared__ __attribute__((aligned(16))) int s_hist[];
-  __shared__ int s_wave[kPk / 64];
-  const int tw = (width + kTile - 1) / kTile, th = (height + kTile - 1) / kTile, T = tw * th;
-  tile_counts += (size_t)blockIdx.y * T;
-  if (LDS_COUNT) {
-    for (int t = threadIdx.x; t < T; t += kPk) s_hist[t] = 0;
-  }
-  const int g = blockIdx.x * kPk + threadIdx.x;
-  Fwd f;
-  const int radius = packed_project_covar<CM>(means, covars, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d,
-                                              radius_clip, g, f);
-  const bool keep = radius > 0;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const unsigned long long vote = __ballot(keep);
-  if (lane == 0) s_wave[wv] = __popcll(vote);
-  __syncthreads();  // (also: the histogram is zero)
-  if (!keep) {
-    if (!LDS_COUNT) return;
-  } else {
-    long long p = block_base[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + __popcll(vote & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wv; ++w) p += s_wave[w];
-    if (p >= 0 && p < nnz) {  // (always: nnz is the sum the bases were scanned from -- a guard against a caller's stale scratch)
-      const bool aa = flags & EG_FLAG_ANTIALIASED;
-      const float o = opacities[g];
-      splat[2 * p] = make_float4(f.u, f.v, f.a, f.b);
-      splat[2 * p + 1] = make_float4(f.c, aa ? o * f.comp : o, f.z, __int_as_float(radius));
-      radii[p] = radius;
-      means2d[2 * p] = f.u; means2d[2 * p + 1] = f.v;
-      depths[p] = f.z;
-      conics[3 * p] = f.a; conics[3 * p + 1] = f.b; conics[3 * p + 2] = f.c;
-      comps[p] = f.comp;
-      camera_ids[p] = blockIdx.y;
-      gaussian_ids[p] = g;
-      int x0, y0, x1, y1;
-      tile_box(f.u, f.v, radius, tw, th, x0, y0, x1, y1);
-      tiles_per_gauss[p] = (y1 - y0) * (x1 - x0);
-      for (int ty = y0; ty < y1; ++ty)
-        for (int tx = x0; tx < x1; ++tx) atomicAdd(LDS_COUNT ? &s_hist[ty * tw + tx] : &tile_counts[ty * tw + tx], 1);
-    }
-  }
-  if (LDS_COUNT) {
-    __syncthreads();
-    for (int t = threadIdx.x; t < T; t += kPk) {
-      const int c = s_hist[t];
-      if (c) atomicAdd(&tile_counts[t], c);
-    }
-  }
-}
-
-// one pair's share of v_means [3] and v_covars [6] (csrc/covar_dev.h); zeros should the recomputed forward cull it
-template <int CM>
-__device__ __forceinline__ void packed_pair_vjp_covar(const float *__restrict__ means, const float *__restrict__ covars,
-                                                      const float *__restrict__ viewmats, const float *__restrict__ Ks,
-                                                      int cam_id, int g, long long p, int width, int height, float eps2d,
-                                                      uint32_t flags, const float4 *__restrict__ g2d,
-                                                      const float *__restrict__ v_comps,
-                                                      const float *__restrict__ v_depths, float (&gm)[3], float (&gc)[6]) {
-  Cam cam;
-  CovarGeom cg;
-  Fwd f;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) gm[k] = 0.f;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) gc[k] = 0.f;
-  // near / far already passed in the forward (the pair exists), so pass open limits
-  if (!packed_geom_covar<CM>(means, covars, viewmats, Ks, cam_id, g, width, height, -3.0e38f, 3.0e38f, eps2d, cam, cg, f))
-    return;
-  const CovarCot ct = load_covar_cot(g2d, v_comps, v_depths, p, flags & EG_FLAG_ANTIALIASED);
-  covar_pair_vjp<false, CM>(cam, cg.m, cg.cv, f, cg.q0, cg.q1, eps2d, ct, gm, gc);
-}
-
-template <int CM>
+template <class Form, int CM>
 __global__ void __launch_bounds__(256)
-packed_bwd_dense_covars_kernel(const float *__restrict__ means, const float *__restrict__ covars,
-                               const float *__restrict__ viewmats, const float *__restrict__ Ks, int N, int C, int width,
-                               int height, float eps2d, uint32_t flags, const long long *__restrict__ indptr,
-                               long long nnz, const long long *__restrict__ gaussian_ids,
-                               const float4 *__restrict__ g2d, const float *__restrict__ v_comps,
-                               const float *__restrict__ v_depths, float *__restrict__ v_means,
-                               float *__restrict__ v_covars) {
-#pragma clang fp contract(off)  // (the same bits whatever the compiler makes of the camera loop)
+packed_bwd_dense_kernel(Form form, const PackedView v, const long long *__restrict__ indptr, long long nnz,
+                        const long long *__restrict__ gaussian_ids, const PackedCot ct,
+                        const typename Form::Out out) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= N) return;
-  float am[3] = {0.f, 0.f, 0.f}, ac[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int c = 0; c < C; ++c) {
+  if (g >= v.N) return;
+  typename Form::Grad acc;
+  acc.zero();
+  for (int c = 0; c < v.C; ++c) {
     const long long end = min(indptr[c + 1], nnz);  // (indptr is the scan's: a guard against a caller's stale array)
     long long lo = max(0ll, indptr[c]);
     long long hi = end;
@@ -399,45 +196,78 @@ packed_bwd_dense_covars_kernel(const float *__restrict__ means, const float *__r
       if (gaussian_ids[mid] < g) lo = mid + 1; else hi = mid;
     }
     if (lo >= end || gaussian_ids[lo] != g) continue;
-    float gm[3], gc[6];
-    packed_pair_vjp_covar<CM>(means, covars, viewmats, Ks, c, g, lo, width, height, eps2d, flags, g2d, v_comps, v_depths,
-                              gm, gc);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) am[k] += gm[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) ac[k] += gc[k];
+    typename Form::Grad gr;
+    gr.zero();
+    packed_pair_vjp<Form, CM>(form, v, c, g, lo, ct, gr);
+    acc += gr;
   }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) v_means[3 * (size_t)g + k] = am[k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) v_covars[6 * (size_t)g + k] = ac[k];
+  acc.store(out, g);
 }
 
-template <int CM>
+template <class Form, int CM>
 __global__ void __launch_bounds__(256)
-packed_bwd_sparse_covars_kernel(const float *__restrict__ means, const float *__restrict__ covars,
-                                const float *__restrict__ viewmats, const float *__restrict__ Ks, int N, int C,
-                                int width, int height, float eps2d, uint32_t flags, long long nnz,
-                                const long long *__restrict__ camera_ids, const long long *__restrict__ gaussian_ids,
-                                const float4 *__restrict__ g2d, const float *__restrict__ v_comps,
-                                const float *__restrict__ v_depths, float *__restrict__ v_means,
-                                float *__restrict__ v_covars) {
+packed_bwd_sparse_kernel(Form form, const PackedView v, long long nnz, const long long *__restrict__ camera_ids,
+                         const long long *__restrict__ gaussian_ids, const PackedCot ct,
+                         const typename Form::Out out) {
   const long long p = blockIdx.x * 256ll + threadIdx.x;
   if (p >= nnz) return;
   const long long c = camera_ids[p], g = gaussian_ids[p];
-  float gm[3] = {0.f, 0.f, 0.f}, gc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (c >= 0 && c < C && g >= 0 && g < N)  // (ids written by packed_write_covars_kernel: a guard against a caller's stale arrays)
-    packed_pair_vjp_covar<CM>(means, covars, viewmats, Ks, (int)c, (int)g, p, width, height, eps2d, flags, g2d, v_comps,
-                              v_depths, gm, gc);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) v_means[3 * p + k] = gm[k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) v_covars[6 * p + k] = gc[k];
+  typename Form::Grad gr;
+  gr.zero();
+  if (c >= 0 && c < v.C && g >= 0 && g < v.N)  // (ids written by packed_write_kernel: a guard against a caller's stale arrays)
+    packed_pair_vjp<Form, CM>(form, v, (int)c, (int)g, p, ct, gr);
+  gr.store(out, p);
 }
 
 }  // namespace eg
 
 using namespace eg;
+
+// ---- one host launcher per pass: it owns the camera-model (and, write, the histogram) dispatch; the entries below
+// check their own arguments and name themselves to check_launch
+template <class Form>
+static void launch_count(const Form &form, const PackedView &v, int32_t *block_base, int64_t *indptr, hipStream_t s) {
+  const int nb = cdiv(v.N, kPk);
+  if (v.N > 0)
+    with_cam_model(v.flags, [&](auto cm) {
+      packed_count_kernel<Form, decltype(cm)::value><<<dim3(nb, v.C), kPk, 0, s>>>(form, v, block_base);
+    });
+  packed_scan_kernel<<<1, 256, 0, s>>>(block_base, nb, v.C, (long long *)indptr);
+}
+
+template <class Form>
+static void launch_write(const Form &form, const PackedView &v, const int32_t *block_base, int64_t nnz,
+                         const PackedOut &o, hipStream_t s) {
+  const int T = cdiv(v.width, kTile) * cdiv(v.height, kTile);
+  const dim3 grid(cdiv(v.N, kPk), v.C);
+  with_cam_model(v.flags, [&](auto cm) {
+    constexpr int CM = decltype(cm)::value;
+    if (T <= 16384)
+      packed_write_kernel<Form, true, CM><<<grid, kPk, sizeof(int) * T, s>>>(form, v, block_base, (long long)nnz, o);
+    else
+      packed_write_kernel<Form, false, CM><<<grid, kPk, 0, s>>>(form, v, block_base, (long long)nnz, o);
+  });
+}
+
+template <class Form>
+static void launch_bwd_dense(const Form &form, const PackedView &v, const int64_t *indptr, int64_t nnz,
+                             const int64_t *gaussian_ids, const PackedCot &ct, const typename Form::Out &out,
+                             hipStream_t s) {
+  with_cam_model(v.flags, [&](auto cm) {
+    packed_bwd_dense_kernel<Form, decltype(cm)::value><<<cdiv(v.N, 256), 256, 0, s>>>(
+        form, v, (const long long *)indptr, (long long)nnz, (const long long *)gaussian_ids, ct, out);
+  });
+}
+
+template <class Form>
+static void launch_bwd_sparse(const Form &form, const PackedView &v, int64_t nnz, const int64_t *camera_ids,
+                              const int64_t *gaussian_ids, const PackedCot &ct, const typename Form::Out &out,
+                              hipStream_t s) {
+  with_cam_model(v.flags, [&](auto cm) {
+    packed_bwd_sparse_kernel<Form, decltype(cm)::value><<<cdiv(nnz, 256), 256, 0, s>>>(
+        form, v, (long long)nnz, (const long long *)camera_ids, (const long long *)gaussian_ids, ct, out);
+  });
+}
 
 #define EG_PACKED_SIZES(N, C, width, height)                                                        \
   EG_REQUIRE(N >= 0 && C >= 1 && C <= 65535 && width > 0 && height > 0, "bad sizes")
@@ -449,16 +279,9 @@ extern "C" int eg_packed_count(const float *means, const float *quats, const flo
   EG_PACKED_SIZES(N, C, width, height);
   EG_REQUIRE(viewmats && Ks && indptr, "null pointer");
   EG_REQUIRE(N == 0 || (means && quats && scales && opacities && block_base), "null pointer");
-  hipStream_t s = as_stream(stream);
-  const int nb = cdiv(N, kPk);
-#define EG_PACKED_COUNT(CM_)                                                                                       \
-  packed_count_kernel<CM_><<<dim3(nb, C), kPk, 0, s>>>(means, quats, scales, opacities, viewmats, Ks, N, width, height, \
-                                                       near_plane, far_plane, eps2d, radius_clip, flags, block_base)
-  if (N > 0) {
-    if (flags & EG_FLAG_ORTHO) EG_PACKED_COUNT(kOrtho); else EG_PACKED_COUNT(kPinhole);
-  }
-#undef EG_PACKED_COUNT
-  packed_scan_kernel<<<1, 256, 0, s>>>(block_base, nb, C, (long long *)indptr);
+  launch_count(QuatScaleForm{means, quats, scales, opacities},
+               PackedView{viewmats, Ks, N, C, width, height, near_plane, far_plane, eps2d, radius_clip, flags},
+               block_base, indptr, as_stream(stream));
   return check_launch("packed_count");
 }
 
@@ -475,19 +298,12 @@ extern "C" int eg_packed_write(const float *means, const float *quats, const flo
   EG_REQUIRE(means && quats && scales && opacities && viewmats && Ks && block_base && splat && radii && means2d &&
                  depths && conics && compensations && tiles_per_gauss && camera_ids && gaussian_ids && tile_counts,
              "null pointer");
-  hipStream_t s = as_stream(stream);
-  const int T = cdiv(width, kTile) * cdiv(height, kTile);
-#define EG_PACKED_WRITE(LDS, CM_, SMEM)                                                                              \
-  packed_write_kernel<LDS, CM_><<<dim3(cdiv(N, kPk), C), kPk, SMEM, s>>>(                                            \
-      means, quats, scales, opacities, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip,    \
-      flags, block_base, (long long)nnz, (float4 *)splat, radii, means2d, depths, conics, compensations,             \
-      tiles_per_gauss, (long long *)camera_ids, (long long *)gaussian_ids, tile_counts)
-  if (flags & EG_FLAG_ORTHO) {
-    if (T <= 16384) EG_PACKED_WRITE(true, kOrtho, sizeof(int) * T); else EG_PACKED_WRITE(false, kOrtho, 0);
-  } else {
-    if (T <= 16384) EG_PACKED_WRITE(true, kPinhole, sizeof(int) * T); else EG_PACKED_WRITE(false, kPinhole, 0);
-  }
-#undef EG_PACKED_WRITE
+  launch_write(QuatScaleForm{means, quats, scales, opacities},
+               PackedView{viewmats, Ks, N, C, width, height, near_plane, far_plane, eps2d, radius_clip, flags},
+               block_base, nnz,
+               PackedOut{(float4 *)splat, radii, means2d, depths, conics, compensations, tiles_per_gauss,
+                         (long long *)camera_ids, (long long *)gaussian_ids, tile_counts},
+               as_stream(stream));
   return check_launch("packed_write");
 }
 
@@ -547,12 +363,10 @@ extern "C" int eg_packed_bwd(const float *means, const float *quats, const float
   EG_REQUIRE(means && quats && scales && opacities && viewmats && Ks && indptr && v_means && v_quats && v_scales,
              "null pointer");
   EG_REQUIRE(nnz == 0 || (gaussian_ids && g2d && v_comps), "null pointer");
-#define EG_PACKED_BWD(CM_)                                                                                           \
-  packed_bwd_dense_kernel<CM_><<<cdiv(N, 256), 256, 0, as_stream(stream)>>>(                                         \
-      means, quats, scales, opacities, viewmats, Ks, N, C, width, height, eps2d, flags, (const long long *)indptr,   \
-      (long long)nnz, (const long long *)gaussian_ids, (const float4 *)g2d, v_comps, v_depths, v_means, v_quats, v_scales)
-  if (flags & EG_FLAG_ORTHO) EG_PACKED_BWD(kOrtho); else EG_PACKED_BWD(kPinhole);
-#undef EG_PACKED_BWD
+  launch_bwd_dense(QuatScaleForm{means, quats, scales, opacities},
+                   PackedView{viewmats, Ks, N, C, width, height, 0.f, 0.f, eps2d, 0.f, flags}, indptr, nnz, gaussian_ids,
+                   PackedCot{(const float4 *)g2d, v_comps, v_depths}, QuatScaleForm::Out{v_means, v_quats, v_scales},
+                   as_stream(stream));
   return check_launch("packed_bwd");
 }
 
@@ -569,18 +383,14 @@ extern "C" int eg_packed_bwd_sparse(const float *means, const float *quats, cons
   EG_REQUIRE(means && quats && scales && opacities && viewmats && Ks && camera_ids && gaussian_ids && g2d && v_comps &&
                  v_means && v_quats && v_scales,
              "null pointer");
-#define EG_PACKED_BWD_SPARSE(CM_)                                                                                    \
-  packed_bwd_sparse_kernel<CM_><<<cdiv(nnz, 256), 256, 0, as_stream(stream)>>>(                                      \
-      means, quats, scales, opacities, viewmats, Ks, N, C, width, height, eps2d, flags, (long long)nnz,              \
-      (const long long *)camera_ids, (const long long *)gaussian_ids, (const float4 *)g2d, v_comps, v_depths, v_means, \
-      v_quats, v_scales)
-  if (flags & EG_FLAG_ORTHO) EG_PACKED_BWD_SPARSE(kOrtho); else EG_PACKED_BWD_SPARSE(kPinhole);
-#undef EG_PACKED_BWD_SPARSE
+  launch_bwd_sparse(QuatScaleForm{means, quats, scales, opacities},
+                    PackedView{viewmats, Ks, N, C, width, height, 0.f, 0.f, eps2d, 0.f, flags}, nnz, camera_ids,
+                    gaussian_ids, PackedCot{(const float4 *)g2d, v_comps, v_depths},
+                    QuatScaleForm::Out{v_means, v_quats, v_scales}, as_stream(stream));
   return check_launch("packed_bwd_sparse");
 }
 
-// ---- the covariance form: covars [N, 6] (upper triangle) in place of quats + scales; scan, eg_packed_bin and the rebase
-// are the ones above
+// ---- the covariance form: covars [N, 6] (upper triangle) in place of quats + scales
 extern "C" int eg_packed_count_covars(const float *means, const float *covars, const float *viewmats, const float *Ks,
                                       int32_t N, int32_t C, int32_t width, int32_t height, float near_plane,
                                       float far_plane, float eps2d, float radius_clip, uint32_t flags,
@@ -588,16 +398,9 @@ extern "C" int eg_packed_count_covars(const float *means, const float *covars, c
   EG_PACKED_SIZES(N, C, width, height);
   EG_REQUIRE(viewmats && Ks && indptr, "null pointer");
   EG_REQUIRE(N == 0 || (means && covars && block_base), "null pointer");
-  hipStream_t s = as_stream(stream);
-  const int nb = cdiv(N, kPk);
-#define EG_PACKED_COUNT(CM_)                                                                                       \
-  packed_count_covars_kernel<CM_><<<dim3(nb, C), kPk, 0, s>>>(means, covars, viewmats, Ks, N, width, height, near_plane, \
-                                                              far_plane, eps2d, radius_clip, block_base)
-  if (N > 0) {
-    if (flags & EG_FLAG_ORTHO) EG_PACKED_COUNT(kOrtho); else EG_PACKED_COUNT(kPinhole);
-  }
-#undef EG_PACKED_COUNT
-  packed_scan_kernel<<<1, 256, 0, s>>>(block_base, nb, C, (long long *)indptr);
+  launch_count(CovarForm{means, covars, nullptr},
+               PackedView{viewmats, Ks, N, C, width, height, near_plane, far_plane, eps2d, radius_clip, flags},
+               block_base, indptr, as_stream(stream));
   return check_launch("packed_count_covars");
 }
 
@@ -614,19 +417,12 @@ extern "C" int eg_packed_write_covars(const float *means, const float *covars, c
   EG_REQUIRE(means && covars && opacities && viewmats && Ks && block_base && splat && radii && means2d && depths &&
                  conics && compensations && tiles_per_gauss && camera_ids && gaussian_ids && tile_counts,
              "null pointer");
-  hipStream_t s = as_stream(stream);
-  const int T = cdiv(width, kTile) * cdiv(height, kTile);
-#define EG_PACKED_WRITE(LDS, CM_, SMEM)                                                                              \
-  packed_write_covars_kernel<LDS, CM_><<<dim3(cdiv(N, kPk), C), kPk, SMEM, s>>>(                                     \
-      means, covars, opacities, viewmats, Ks, N, width, height, near_plane, far_plane, eps2d, radius_clip, flags,    \
-      block_base, (long long)nnz, (float4 *)splat, radii, means2d, depths, conics, compensations, tiles_per_gauss,   \
-      (long long *)camera_ids, (long long *)gaussian_ids, tile_counts)
-  if (flags & EG_FLAG_ORTHO) {
-    if (T <= 16384) EG_PACKED_WRITE(true, kOrtho, sizeof(int) * T); else EG_PACKED_WRITE(false, kOrtho, 0);
-  } else {
-    if (T <= 16384) EG_PACKED_WRITE(true, kPinhole, sizeof(int) * T); else EG_PACKED_WRITE(false, kPinhole, 0);
-  }
-#undef EG_PACKED_WRITE
+  launch_write(CovarForm{means, covars, opacities},
+               PackedView{viewmats, Ks, N, C, width, height, near_plane, far_plane, eps2d, radius_clip, flags},
+               block_base, nnz,
+               PackedOut{(float4 *)splat, radii, means2d, depths, conics, compensations, tiles_per_gauss,
+                         (long long *)camera_ids, (long long *)gaussian_ids, tile_counts},
+               as_stream(stream));
   return check_launch("packed_write_covars");
 }
 
@@ -641,12 +437,10 @@ extern "C" int eg_packed_bwd_covars(const float *means, const float *covars, con
   if (N == 0) return EG_OK;
   EG_REQUIRE(means && covars && viewmats && Ks && indptr && v_means && v_covars, "null pointer");
   EG_REQUIRE(nnz == 0 || (gaussian_ids && g2d && v_comps), "null pointer");
-#define EG_PACKED_BWD(CM_)                                                                                           \
-  packed_bwd_dense_covars_kernel<CM_><<<cdiv(N, 256), 256, 0, as_stream(stream)>>>(                                  \
-      means, covars, viewmats, Ks, N, C, width, height, eps2d, flags, (const long long *)indptr, (long long)nnz,     \
-      (const long long *)gaussian_ids, (const float4 *)g2d, v_comps, v_depths, v_means, v_covars)
-  if (flags & EG_FLAG_ORTHO) EG_PACKED_BWD(kOrtho); else EG_PACKED_BWD(kPinhole);
-#undef EG_PACKED_BWD
+  launch_bwd_dense(CovarForm{means, covars, nullptr},
+                   PackedView{viewmats, Ks, N, C, width, height, 0.f, 0.f, eps2d, 0.f, flags}, indptr, nnz, gaussian_ids,
+                   PackedCot{(const float4 *)g2d, v_comps, v_depths}, CovarForm::Out{v_means, v_covars},
+                   as_stream(stream));
   return check_launch("packed_bwd_covars");
 }
 
@@ -662,11 +456,9 @@ extern "C" int eg_packed_bwd_sparse_covars(const float *means, const float *cova
   if (nnz == 0) return EG_OK;
   EG_REQUIRE(means && covars && viewmats && Ks && camera_ids && gaussian_ids && g2d && v_comps && v_means && v_covars,
              "null pointer");
-#define EG_PACKED_BWD_SPARSE(CM_)                                                                                    \
-  packed_bwd_sparse_covars_kernel<CM_><<<cdiv(nnz, 256), 256, 0, as_stream(stream)>>>(                               \
-      means, covars, viewmats, Ks, N, C, width, height, eps2d, flags, (long long)nnz, (const long long *)camera_ids, \
-      (const long long *)gaussian_ids, (const float4 *)g2d, v_comps, v_depths, v_means, v_covars)
-  if (flags & EG_FLAG_ORTHO) EG_PACKED_BWD_SPARSE(kOrtho); else EG_PACKED_BWD_SPARSE(kPinhole);
-#undef EG_PACKED_BWD_SPARSE
+  launch_bwd_sparse(CovarForm{means, covars, nullptr},
+                    PackedView{viewmats, Ks, N, C, width, height, 0.f, 0.f, eps2d, 0.f, flags}, nnz, camera_ids,
+                    gaussian_ids, PackedCot{(const float4 *)g2d, v_comps, v_depths}, CovarForm::Out{v_means, v_covars},
+                    as_stream(stream));
   return check_launch("packed_bwd_sparse_covars");
 }

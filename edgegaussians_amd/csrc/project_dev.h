@@ -1,8 +1,14 @@
-// Device code of the projection (G1 / G9) shared by project.hip and backward_fused.hip: camera, the forward
-// geometry of one Gaussian, its reverse sweep, Adam.  (Moved out of project.hip in round 6, unchanged: every kernel
-// that inlines forward_geom forms the SAME rounding sequence -- see the comment inside it.)
+// Device code of the projection (G1 / G9) shared by every kernel that projects: camera, the forward geometry of one
+// Gaussian from quats + scales (forward_geom) or from a covariance (forward_geom_covar), the reverse sweep
+// (backward_geom; the covariance's is csrc/covar_dev.h), Adam.  The halves the two forms have in common -- camera-space
+// mean and near / far cull, the camera model's J and mean2d, cov2d -> conic, and their reverse steps -- are helpers
+// written once; each carries its own `fp contract(off)` (the pragma is lexical, it does not follow an inlined call), so
+// every kernel that inlines them forms the SAME rounding sequence -- see the comment inside forward_geom.
+// QuatScaleForm (bottom) is what the kernels written once for both forms (packed.hip, viewmat_grad.hip) know of this one.
 #pragma once
 #include <math.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -17,6 +23,13 @@ struct Cam {
 // mean2d = (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]] -- no division by z, no fov clamp, cov2d independent of
 // the mean; culls, depth and everything behind cov2d are the pinhole's.
 enum CamModel : int { kPinhole = 0, kOrtho = 1 };
+
+// host: the camera model of a launch as a compile-time value -- fn(cm) with decltype(cm)::value = kOrtho under
+// EG_FLAG_ORTHO, kPinhole otherwise
+template <class F>
+inline void with_cam_model(uint32_t flags, F &&fn) {
+  if (flags & EG_FLAG_ORTHO) fn(std::integral_constant<int, kOrtho>{}); else fn(std::integral_constant<int, kPinhole>{});
+}
 
 __device__ __forceinline__ Cam load_cam(const float *__restrict__ vm, const float *__restrict__ K) {
   Cam c;
@@ -60,6 +73,65 @@ __device__ __forceinline__ Raw load_raw(const float *__restrict__ means, const f
   return r;
 }
 
+// The three steps of the forward that both shape forms share.  (No FMA contraction: see forward_geom.)
+// camera-space mean of the world mean m[3]; false = outside [near_plane, far_plane]
+__device__ __forceinline__ bool camera_mean(const Cam &cam, const float *m, float near_plane, float far_plane, Fwd &f) {
+#pragma clang fp contract(off)
+  const float mx = m[0], my = m[1], mz = m[2];
+  f.x = cam.R[0] * mx + cam.R[1] * my + cam.R[2] * mz + cam.t[0];
+  f.y = cam.R[3] * mx + cam.R[4] * my + cam.R[5] * mz + cam.t[1];
+  f.z = cam.R[6] * mx + cam.R[7] * my + cam.R[8] * mz + cam.t[2];
+  return !(f.z < near_plane || f.z > far_plane);
+}
+
+// the camera model at the camera-space mean: 1/z, the fov clamp, the Jacobian J and mean2d
+template <int CM>
+__device__ __forceinline__ void camera_jacobian(const Cam &cam, int width, int height, Fwd &f) {
+#pragma clang fp contract(off)
+  if constexpr (CM == kOrtho) {
+    // J = [[fx, 0, 0], [0, fy, 0]]; the pinhole-only fields read as "no clamp"
+    f.rz = 0.f; f.rz2 = 0.f;
+    f.in_x = true; f.in_y = true;
+    f.tx = f.x; f.ty = f.y;
+    f.J00 = cam.fx; f.J11 = cam.fy;
+    f.J02 = 0.f; f.J12 = 0.f;
+    f.u = cam.fx * f.x + cam.cx;
+    f.v = cam.fy * f.y + cam.cy;
+  } else {
+    const float lim_x = kFovClamp * (0.5f * (float)width / cam.fx);
+    const float lim_y = kFovClamp * (0.5f * (float)height / cam.fy);
+    f.rz = 1.f / f.z;
+    f.rz2 = f.rz * f.rz;
+    const float xr = f.x * f.rz, yr = f.y * f.rz;
+    f.in_x = (xr <= lim_x) && (xr >= -lim_x);
+    f.in_y = (yr <= lim_y) && (yr >= -lim_y);
+    f.tx = f.z * fminf(lim_x, fmaxf(-lim_x, xr));
+    f.ty = f.z * fminf(lim_y, fmaxf(-lim_y, yr));
+    f.J00 = cam.fx * f.rz;
+    f.J11 = cam.fy * f.rz;
+    f.J02 = -cam.fx * f.tx * f.rz2;
+    f.J12 = -cam.fy * f.ty * f.rz2;
+    f.u = cam.fx * f.x * f.rz + cam.cx;
+    f.v = cam.fy * f.y * f.rz + cam.cy;
+  }
+}
+
+// cov2d (c00, c01, c11) -> determinants, blurred diagonal, compensation, conic; false = the det cull
+__device__ __forceinline__ bool conic_of_cov2d(float eps2d, Fwd &f) {
+#pragma clang fp contract(off)
+  f.det0 = f.c00 * f.c11 - f.c01 * f.c01;
+  f.b00 = f.c00 + eps2d;
+  f.b11 = f.c11 + eps2d;
+  f.det1 = f.b00 * f.b11 - f.c01 * f.c01;
+  if (f.det1 <= 0.f) return false;
+  f.comp = sqrtf(fmaxf(0.f, f.det0 / f.det1));
+  const float inv = 1.f / f.det1;
+  f.a = f.b11 * inv;
+  f.b = -f.c01 * inv;
+  f.c = f.b00 * inv;
+  return true;
+}
+
 template <int CM = kPinhole>
 __device__ __forceinline__ bool forward_geom(const Cam &cam, const Raw &raw, int width, int height,
                                              float near_plane, float far_plane, float eps2d, uint32_t flags,
@@ -71,11 +143,7 @@ __device__ __forceinline__ bool forward_geom(const Cam &cam, const Raw &raw, int
   // or alpha threshold here and there (1600 x 1200, 200 k Gaussians: one Gaussian's gradient off by 4e-4 of the
   // maximum between the two paths).  Separate multiplies and adds are also what the C oracle (gcc, x86-64) does.
 #pragma clang fp contract(off)
-  const float mx = raw.m[0], my = raw.m[1], mz = raw.m[2];
-  f.x = cam.R[0] * mx + cam.R[1] * my + cam.R[2] * mz + cam.t[0];
-  f.y = cam.R[3] * mx + cam.R[4] * my + cam.R[5] * mz + cam.t[1];
-  f.z = cam.R[6] * mx + cam.R[7] * my + cam.R[8] * mz + cam.t[2];
-  if (f.z < near_plane || f.z > far_plane) return false;
+  if (!camera_mean(cam, raw.m, near_plane, far_plane, f)) return false;
 
   float w = raw.q[0], x = raw.q[1], y = raw.q[2], z = raw.q[3];
   f.qinv = rsqrtf(w * w + x * x + y * y + z * z);
@@ -103,57 +171,22 @@ __device__ __forceinline__ bool forward_geom(const Cam &cam, const Raw &raw, int
       f.W[3 * i + k] =
           (cam.R[3 * i] * f.Rq[k] + cam.R[3 * i + 1] * f.Rq[3 + k] + cam.R[3 * i + 2] * f.Rq[6 + k]) * f.s[k];
 
-  if constexpr (CM == kOrtho) {
-    // J = [[fx, 0, 0], [0, fy, 0]]: P = J W takes the first two rows of W; the pinhole-only fields read as "no clamp"
-    f.rz = 0.f; f.rz2 = 0.f;
-    f.in_x = true; f.in_y = true;
-    f.tx = f.x; f.ty = f.y;
-    f.J00 = cam.fx; f.J11 = cam.fy;
-    f.J02 = 0.f; f.J12 = 0.f;
+  // P = J W (ortho: J = [[fx, 0, 0], [0, fy, 0]] takes the first two rows of W)
+  camera_jacobian<CM>(cam, width, height, f);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < 3; ++k) {
+    if constexpr (CM == kOrtho) {
       f.p0[k] = f.J00 * f.W[k];
       f.p1[k] = f.J11 * f.W[3 + k];
-    }
-    f.u = cam.fx * f.x + cam.cx;
-    f.v = cam.fy * f.y + cam.cy;
-  } else {
-    const float lim_x = kFovClamp * (0.5f * (float)width / cam.fx);
-    const float lim_y = kFovClamp * (0.5f * (float)height / cam.fy);
-    f.rz = 1.f / f.z;
-    f.rz2 = f.rz * f.rz;
-    const float xr = f.x * f.rz, yr = f.y * f.rz;
-    f.in_x = (xr <= lim_x) && (xr >= -lim_x);
-    f.in_y = (yr <= lim_y) && (yr >= -lim_y);
-    f.tx = f.z * fminf(lim_x, fmaxf(-lim_x, xr));
-    f.ty = f.z * fminf(lim_y, fmaxf(-lim_y, yr));
-    f.J00 = cam.fx * f.rz;
-    f.J11 = cam.fy * f.rz;
-    f.J02 = -cam.fx * f.tx * f.rz2;
-    f.J12 = -cam.fy * f.ty * f.rz2;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    } else {
       f.p0[k] = f.J00 * f.W[k] + f.J02 * f.W[6 + k];
       f.p1[k] = f.J11 * f.W[3 + k] + f.J12 * f.W[6 + k];
     }
-    f.u = cam.fx * f.x * f.rz + cam.cx;
-    f.v = cam.fy * f.y * f.rz + cam.cy;
   }
   f.c00 = f.p0[0] * f.p0[0] + f.p0[1] * f.p0[1] + f.p0[2] * f.p0[2];
   f.c01 = f.p0[0] * f.p1[0] + f.p0[1] * f.p1[1] + f.p0[2] * f.p1[2];
   f.c11 = f.p1[0] * f.p1[0] + f.p1[1] * f.p1[1] + f.p1[2] * f.p1[2];
-
-  f.det0 = f.c00 * f.c11 - f.c01 * f.c01;
-  f.b00 = f.c00 + eps2d;
-  f.b11 = f.c11 + eps2d;
-  f.det1 = f.b00 * f.b11 - f.c01 * f.c01;
-  if (f.det1 <= 0.f) return false;
-  f.comp = sqrtf(fmaxf(0.f, f.det0 / f.det1));
-  const float inv = 1.f / f.det1;
-  f.a = f.b11 * inv;
-  f.b = -f.c01 * inv;
-  f.c = f.b00 * inv;
-  return true;
+  return conic_of_cov2d(eps2d, f);
 }
 
 template <int CM = kPinhole>
@@ -177,11 +210,7 @@ __device__ __forceinline__ bool forward_geom_covar(const Cam &cam, const float *
                                                    float near_plane, float far_plane, float eps2d, Fwd &f,
                                                    float (&cc)[6], float (&q0)[3], float (&q1)[3]) {
 #pragma clang fp contract(off)  // (one rounding sequence in every kernel: see forward_geom)
-  const float mx = m[0], my = m[1], mz = m[2];
-  f.x = cam.R[0] * mx + cam.R[1] * my + cam.R[2] * mz + cam.t[0];
-  f.y = cam.R[3] * mx + cam.R[4] * my + cam.R[5] * mz + cam.t[1];
-  f.z = cam.R[6] * mx + cam.R[7] * my + cam.R[8] * mz + cam.t[2];
-  if (f.z < near_plane || f.z > far_plane) return false;
+  if (!camera_mean(cam, m, near_plane, far_plane, f)) return false;
 
   // cc = Rv S Rv^T, S symmetric: A = Rv S, then the upper triangle of A Rv^T
   const float S[9] = {cv[0], cv[1], cv[2], cv[1], cv[3], cv[4], cv[2], cv[4], cv[5]};
@@ -196,35 +225,16 @@ __device__ __forceinline__ bool forward_geom_covar(const Cam &cam, const float *
   for (int e = 0; e < 6; ++e)
     cc[e] = A[3 * ui[e]] * cam.R[3 * uj[e]] + A[3 * ui[e] + 1] * cam.R[3 * uj[e] + 1] + A[3 * ui[e] + 2] * cam.R[3 * uj[e] + 2];
 
+  // Q = J cc, cov2d = Q J^T (ortho: J = [[fx, 0, 0], [0, fy, 0]] scales the first two rows of cc, cov2d is the
+  // upper-left block of Q J^T)
+  camera_jacobian<CM>(cam, width, height, f);
   if constexpr (CM == kOrtho) {
-    // J = [[fx, 0, 0], [0, fy, 0]]: Q = J cc scales the first two rows of cc, cov2d = Q J^T its upper-left block
-    f.rz = 0.f; f.rz2 = 0.f;
-    f.in_x = true; f.in_y = true;
-    f.tx = f.x; f.ty = f.y;
-    f.J00 = cam.fx; f.J11 = cam.fy;
-    f.J02 = 0.f; f.J12 = 0.f;
     q0[0] = f.J00 * cc[0]; q0[1] = f.J00 * cc[1]; q0[2] = f.J00 * cc[2];
     q1[0] = f.J11 * cc[1]; q1[1] = f.J11 * cc[3]; q1[2] = f.J11 * cc[4];
     f.c00 = q0[0] * f.J00;
     f.c01 = q0[1] * f.J11;
     f.c11 = q1[1] * f.J11;
-    f.u = cam.fx * f.x + cam.cx;
-    f.v = cam.fy * f.y + cam.cy;
   } else {
-    const float lim_x = kFovClamp * (0.5f * (float)width / cam.fx);
-    const float lim_y = kFovClamp * (0.5f * (float)height / cam.fy);
-    f.rz = 1.f / f.z;
-    f.rz2 = f.rz * f.rz;
-    const float xr = f.x * f.rz, yr = f.y * f.rz;
-    f.in_x = (xr <= lim_x) && (xr >= -lim_x);
-    f.in_y = (yr <= lim_y) && (yr >= -lim_y);
-    f.tx = f.z * fminf(lim_x, fmaxf(-lim_x, xr));
-    f.ty = f.z * fminf(lim_y, fmaxf(-lim_y, yr));
-    f.J00 = cam.fx * f.rz;
-    f.J11 = cam.fy * f.rz;
-    f.J02 = -cam.fx * f.tx * f.rz2;
-    f.J12 = -cam.fy * f.ty * f.rz2;
-    // Q = J cc, cov2d = Q J^T
     q0[0] = f.J00 * cc[0] + f.J02 * cc[2];
     q0[1] = f.J00 * cc[1] + f.J02 * cc[4];
     q0[2] = f.J00 * cc[2] + f.J02 * cc[5];
@@ -234,21 +244,8 @@ __device__ __forceinline__ bool forward_geom_covar(const Cam &cam, const float *
     f.c00 = q0[0] * f.J00 + q0[2] * f.J02;
     f.c01 = q0[1] * f.J11 + q0[2] * f.J12;
     f.c11 = q1[1] * f.J11 + q1[2] * f.J12;
-    f.u = cam.fx * f.x * f.rz + cam.cx;
-    f.v = cam.fy * f.y * f.rz + cam.cy;
   }
-
-  f.det0 = f.c00 * f.c11 - f.c01 * f.c01;
-  f.b00 = f.c00 + eps2d;
-  f.b11 = f.c11 + eps2d;
-  f.det1 = f.b00 * f.b11 - f.c01 * f.c01;
-  if (f.det1 <= 0.f) return false;
-  f.comp = sqrtf(fmaxf(0.f, f.det0 / f.det1));
-  const float inv = 1.f / f.det1;
-  f.a = f.b11 * inv;
-  f.b = -f.c01 * inv;
-  f.c = f.b00 * inv;
-  return true;
+  return conic_of_cov2d(eps2d, f);
 }
 
 __device__ __forceinline__ int radius_of(const Fwd &f, int width, int height, float radius_clip) {
@@ -291,6 +288,57 @@ struct Grads {
   float mean[3], quat[4], scale[3], opac;
 };
 
+// The steps of the reverse sweep that both shape forms share (backward_geom below, covar_pair_vjp in csrc/covar_dev.h).
+// conic = B^-1  =>  G = -A V A with V = [[va, vb/2],[vb/2, vc]] (b is stored once): the cotangent of cov2d
+__device__ __forceinline__ void conic_vjp(const Fwd &f, float va, float vb, float vc, float &G00, float &G01,
+                                          float &G11) {
+#pragma clang fp contract(off)
+  const float hb = 0.5f * vb;
+  const float av00 = f.a * va + f.b * hb, av01 = f.a * hb + f.b * vc;
+  const float av10 = f.b * va + f.c * hb, av11 = f.b * hb + f.c * vc;
+  G00 = -(av00 * f.a + av01 * f.b);
+  G01 = -(av00 * f.b + av01 * f.c);
+  G11 = -(av10 * f.b + av11 * f.c);
+}
+
+// the compensation's share of G: d comp / d cov2d = (1/(2 comp)) * ((1 - comp^2) conic - eps det(conic) I); gsplat
+// guards the division with +1e-6 and the oracle does the same.  DET_GUARD (the covariance form): nothing where the
+// determinant ratio is negative (comp is clamped to 0 there).
+template <bool DET_GUARD>
+__device__ __forceinline__ void comp_vjp(const Fwd &f, float eps2d, float v_comp, float &G00, float &G01, float &G11) {
+#pragma clang fp contract(off)
+  const float det_conic = f.a * f.c - f.b * f.b;
+  const float vs = (!DET_GUARD || f.det0 / f.det1 >= 0.f) ? v_comp * 0.5f / (f.comp + 1e-6f) : 0.f;
+  const float omc = 1.f - f.comp * f.comp;
+  G00 += vs * (omc * f.a - eps2d * det_conic);
+  G01 += vs * (omc * f.b);
+  G11 += vs * (omc * f.c - eps2d * det_conic);
+}
+
+// camera-space mean's cotangent (vtx, vty, vtz): through mean2d (vx, vy), the depth and -- pinhole -- through J, whose
+// cotangents the caller formed (the fov clamp freezes tx = +-lim z).  Ortho: J is constant, the vJ are not read.
+template <int CM>
+__device__ __forceinline__ void camera_mean_vjp(const Cam &cam, const Fwd &f, float vx, float vy, float v_depth,
+                                                float vJ00, float vJ02, float vJ11, float vJ12, float &vtx, float &vty,
+                                                float &vtz) {
+#pragma clang fp contract(off)
+  if constexpr (CM == kOrtho) {
+    vtx = cam.fx * vx;
+    vty = cam.fy * vy;
+    vtz = v_depth;
+  } else {
+    const float rz3 = f.rz2 * f.rz;
+    vtx = cam.fx * f.rz * vx;
+    vty = cam.fy * f.rz * vy;
+    vtz = -(cam.fx * f.x * vx + cam.fy * f.y * vy) * f.rz2 + v_depth;
+    vtz += -cam.fx * f.rz2 * vJ00 - cam.fy * f.rz2 * vJ11;
+    if (f.in_x) { vtx += -cam.fx * f.rz2 * vJ02; vtz += 2.f * cam.fx * f.tx * rz3 * vJ02; }
+    else        { vtz += cam.fx * f.tx * rz3 * vJ02; }
+    if (f.in_y) { vty += -cam.fy * f.rz2 * vJ12; vtz += 2.f * cam.fy * f.ty * rz3 * vJ12; }
+    else        { vtz += cam.fy * f.ty * rz3 * vJ12; }
+  }
+}
+
 // CAM (csrc/viewmat_grad.hip): the same sweep stops at the camera-space cotangents and leaves the CAMERA's share in
 // v_cam[12] -- rows of [v_R | v_tr], v_R[i][j] = v_t[i] mean[j] + sum_k vW[3 i + k] M[j][k] with M = Rq diag(s) (the
 // transpose-side product of W = Rv M), v_tr = v_t -- from the world mean `mean`; `o` is not touched.  The default
@@ -312,23 +360,9 @@ __device__ __forceinline__ void backward_geom(const Cam &cam, const Fwd &f, floa
   float v_o = ext ? 0.f : (aa ? vo_eff * f.comp : vo_eff);
   const float v_comp = ext ? v_comp_ext : (aa ? vo_eff * f.o : 0.f);
 
-  // conic = B^-1  =>  G = -A V A with V = [[va, vb/2],[vb/2, vc]] (b is stored once)
-  const float hb = 0.5f * vb;
-  const float av00 = f.a * va + f.b * hb, av01 = f.a * hb + f.b * vc;
-  const float av10 = f.b * va + f.c * hb, av11 = f.b * hb + f.c * vc;
-  float G00 = -(av00 * f.a + av01 * f.b);
-  float G01 = -(av00 * f.b + av01 * f.c);
-  float G11 = -(av10 * f.b + av11 * f.c);
-  if (aa) {
-    // d comp / d cov2d = (1/(2 comp)) * ((1 - comp^2) conic - eps det(conic) I); gsplat guards the
-    // division with +1e-6 and the oracle does the same
-    const float det_conic = f.a * f.c - f.b * f.b;
-    const float vs = v_comp * 0.5f / (f.comp + 1e-6f);
-    const float omc = 1.f - f.comp * f.comp;
-    G00 += vs * (omc * f.a - eps2d * det_conic);
-    G01 += vs * (omc * f.b);
-    G11 += vs * (omc * f.c - eps2d * det_conic);
-  }
+  float G00, G01, G11;
+  conic_vjp(f, va, vb, vc, G00, G01, G11);
+  if (aa) comp_vjp<false>(f, eps2d, v_comp, G00, G01, G11);
   // cov2d = P P^T  =>  v_P = 2 G P
   float vp0[3], vp1[3];
 #pragma unroll
@@ -336,42 +370,23 @@ __device__ __forceinline__ void backward_geom(const Cam &cam, const Fwd &f, floa
     vp0[k] = 2.f * (G00 * f.p0[k] + G01 * f.p1[k]);
     vp1[k] = 2.f * (G01 * f.p0[k] + G11 * f.p1[k]);
   }
+  // P = J W (ortho: the constant J = [[fx, 0, 0], [0, fy, 0]] has no cotangent)
   float vW[9];
-  float vtx, vty, vtz;
-  if constexpr (CM == kOrtho) {
-    // P = J W with the constant J = [[fx, 0, 0], [0, fy, 0]]; camera-space mean: through mean2d and the depth only
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      vW[k] = f.J00 * vp0[k];
-      vW[3 + k] = f.J11 * vp1[k];
-      vW[6 + k] = 0.f;
-    }
-    vtx = cam.fx * vx;
-    vty = cam.fy * vy;
-    vtz = v_depth_ext;
-  } else {
-    // P = J W
-    const float vJ00 = vp0[0] * f.W[0] + vp0[1] * f.W[1] + vp0[2] * f.W[2];
-    const float vJ02 = vp0[0] * f.W[6] + vp0[1] * f.W[7] + vp0[2] * f.W[8];
-    const float vJ11 = vp1[0] * f.W[3] + vp1[1] * f.W[4] + vp1[2] * f.W[5];
-    const float vJ12 = vp1[0] * f.W[6] + vp1[1] * f.W[7] + vp1[2] * f.W[8];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      vW[k] = f.J00 * vp0[k];
-      vW[3 + k] = f.J11 * vp1[k];
-      vW[6 + k] = f.J02 * vp0[k] + f.J12 * vp1[k];
-    }
-    // camera-space mean: through mean2d and through J (fov clamp freezes tx = +-lim z)
-    const float rz3 = f.rz2 * f.rz;
-    vtx = cam.fx * f.rz * vx;
-    vty = cam.fy * f.rz * vy;
-    vtz = -(cam.fx * f.x * vx + cam.fy * f.y * vy) * f.rz2 + v_depth_ext;
-    vtz += -cam.fx * f.rz2 * vJ00 - cam.fy * f.rz2 * vJ11;
-    if (f.in_x) { vtx += -cam.fx * f.rz2 * vJ02; vtz += 2.f * cam.fx * f.tx * rz3 * vJ02; }
-    else        { vtz += cam.fx * f.tx * rz3 * vJ02; }
-    if (f.in_y) { vty += -cam.fy * f.rz2 * vJ12; vtz += 2.f * cam.fy * f.ty * rz3 * vJ12; }
-    else        { vtz += cam.fy * f.ty * rz3 * vJ12; }
+  float vJ00 = 0.f, vJ02 = 0.f, vJ11 = 0.f, vJ12 = 0.f;
+  if constexpr (CM != kOrtho) {
+    vJ00 = vp0[0] * f.W[0] + vp0[1] * f.W[1] + vp0[2] * f.W[2];
+    vJ02 = vp0[0] * f.W[6] + vp0[1] * f.W[7] + vp0[2] * f.W[8];
+    vJ11 = vp1[0] * f.W[3] + vp1[1] * f.W[4] + vp1[2] * f.W[5];
+    vJ12 = vp1[0] * f.W[6] + vp1[1] * f.W[7] + vp1[2] * f.W[8];
   }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    vW[k] = f.J00 * vp0[k];
+    vW[3 + k] = f.J11 * vp1[k];
+    if constexpr (CM == kOrtho) vW[6 + k] = 0.f; else vW[6 + k] = f.J02 * vp0[k] + f.J12 * vp1[k];
+  }
+  float vtx, vty, vtz;
+  camera_mean_vjp<CM>(cam, f, vx, vy, v_depth_ext, vJ00, vJ02, vJ11, vJ12, vtx, vty, vtz);
   if constexpr (CAM) {
     const float vt[3] = {vtx, vty, vtz};
 #pragma unroll
@@ -416,6 +431,68 @@ __device__ __forceinline__ void backward_geom(const Cam &cam, const Fwd &f, floa
   if (flags & EG_FLAG_LOGIT_OPACITIES) v_o *= f.o * (1.f - f.o);
   o.opac = v_o;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The quats + scales form of a Gaussian's shape, as the kernels written once for both forms take it (packed.hip,
+// viewmat_grad.hip; CovarForm in csrc/covar_dev.h is the other): the inputs, the forward of one (camera, Gaussian)
+// pair, the record's opacity, the gradient of one row and the pair's reverse sweep.  The host fills the four pointers;
+// `raw` is the kernel's (forward() loads it, pair_vjp reads it).
+struct QuatScaleForm {
+  const float *means, *quats, *scales, *opacities;
+  Raw raw;
+
+  using Visible = float4;  // the dense layout's [C, N, 8] record of the compositing kernels: word 7 is the radius
+  static __device__ __forceinline__ bool visible(const float4 *splat, long long q) {
+    return __float_as_int(splat[2 * q + 1].w) > 0;
+  }
+
+  template <int CM>
+  __device__ __forceinline__ bool forward(const Cam &cam, int g, int width, int height, float near_plane,
+                                          float far_plane, float eps2d, uint32_t flags, Fwd &f) {
+    raw = load_raw(means, quats, scales, opacities, g);
+    return forward_geom<CM>(cam, raw, width, height, near_plane, far_plane, eps2d, flags, f);
+  }
+  __device__ __forceinline__ float opacity(const Fwd &f, int) const { return f.o; }
+
+  // one row of v_means [*, 3], v_quats [*, 4], v_scales [*, 3] (no opacity gradient: the caller owns that product)
+  struct Out {
+    float *v_means, *v_quats, *v_scales;
+  };
+  struct Grad : Grads {
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) mean[k] = scale[k] = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) quat[k] = 0.f;
+    }
+    __device__ __forceinline__ void operator+=(const Grad &o) {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { mean[k] += o.mean[k]; scale[k] += o.scale[k]; }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) quat[k] += o.quat[k];
+    }
+    __device__ __forceinline__ void store(const Out &out, long long row) const {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { out.v_means[3 * row + k] = mean[k]; out.v_scales[3 * row + k] = scale[k]; }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) out.v_quats[4 * row + k] = quat[k];
+    }
+  };
+
+  // pair p = (cam, g) of a visible list: its share of the row's gradient, or (CAM) the camera's share in v_cam[12].
+  // The pair passed the near / far and det culls in the forward, so the recomputation runs with open limits.
+  template <bool CAM, int CM>
+  __device__ __forceinline__ void pair_vjp(const Cam &cam, int g, long long p, int width, int height, float eps2d,
+                                           uint32_t flags, const float4 *__restrict__ g2d,
+                                           const float *__restrict__ v_comps, const float *__restrict__ v_depths,
+                                           Grad &gr, float *v_cam = nullptr) {
+    const float4 ga = g2d[2 * p], gb = g2d[2 * p + 1];
+    Fwd f;
+    forward<CM>(cam, g, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f);
+    backward_geom<CAM, CM>(cam, f, eps2d, flags, ga, gb, true, v_comps[p], v_depths ? v_depths[p] : 0.f, gr, v_cam, raw.m);
+  }
+};
 
 inline AdamK make_adamk(const eg_adam_hyper &h) {
   // host side in double, exactly how torch.optim.Adam forms its scalars before casting to fp32

@@ -4,10 +4,11 @@
 // visible pair and keep the Gaussian's share.  The camera's share is a sum over the Gaussians, asked for by pose
 // optimisers only: it lives here, in two kernels of its own that nobody else pays for.
 //
-//   partial  grid (B, C), 256 lanes: one lane per pair of camera blockIdx.y.  A visible pair recomputes forward_geom
-//            (open cull limits: it passed the culls in the forward, like the other backwards), runs backward_geom<true>
-//            and holds the 12 values of [v_R | v_tr]; every other lane holds zeros.  Sum over the wave with DPP, over
-//            the four waves through LDS in wave order, one 12-float partial per workgroup into scratch [C, B, 12].
+//   partial  grid (B, C), 256 lanes: one lane per pair of camera blockIdx.y.  A visible pair recomputes its forward
+//            (open cull limits: it passed the culls in the forward, like the other backwards), runs the reverse sweep
+//            up to the camera (quats + scales: backward_geom<true>) and holds the 12 values of [v_R | v_tr]; every
+//            other lane holds zeros.  Sum over the wave with DPP, over the four waves through LDS in wave order, one
+//            12-float partial per workgroup into scratch [C, B, 12].
 //   fold     grid (C), 256 lanes: lane t adds the partials t, t + 256, ... in ascending order, then the same
 //            wave / four-wave sum; v_viewmats[c] is written whole, the zero bottom row included.
 //
@@ -15,10 +16,11 @@
 // Gaussian blockIdx.x * 256 + lane, visible when the radius word of the saved [C, N, 8] record is positive) and PACKED
 // (pair = indptr[c] + blockIdx.x * 256 + lane inside camera c's range of the packed list, every pair visible).
 //
-// The covariance form (eg_project_covars_bwd_viewmats): the same two layouts behind forward_geom_covar, the dense one
-// told by radii [C, N] (eg_project_covars_fwd_cams_flags has no record).  With cc = Rv S Rv^T, S the world covariance,
-// the camera's share of a pair is v_R = v_t mean^T + (v_cc + v_cc^T) Rv S, v_tr = v_t (covar_pair_vjp<true>,
-// csrc/covar_dev.h).  The same sums, the same fold kernel.
+// The partial kernel is a template over the form the Gaussian's shape arrives in (QuatScaleForm, csrc/project_dev.h;
+// CovarForm, csrc/covar_dev.h, behind eg_project_covars_bwd_viewmats): the form's pair_vjp<true> leaves the camera's
+// share of a pair, and the form tells which DENSE pairs are visible -- the radius word of the record, or radii [C, N]
+// (eg_project_covars_fwd_cams_flags has no record).  With cc = Rv S Rv^T, S the world covariance, the covariance form's
+// share is v_R = v_t mean^T + (v_cc + v_cc^T) Rv S, v_tr = v_t (covar_pair_vjp<true>).  The same sums, the same fold.
 #include "common.h"
 #include "covar_dev.h"
 #include "project_dev.h"
@@ -39,16 +41,14 @@ __device__ __forceinline__ void block_sum12(const float (&v)[12], float (*s_part
   __syncthreads();
 }
 
-// CM: the camera model (csrc/project_dev.h), kOrtho with EG_FLAG_ORTHO.
-template <bool PACKED, int CM>
+// CM: the camera model (csrc/project_dev.h), kOrtho with EG_FLAG_ORTHO.  `vis`: what Form::visible reads (DENSE only).
+template <class Form, bool PACKED, int CM>
 __global__ void __launch_bounds__(kVg)
-viewmat_partial_kernel(const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
-                       const float *__restrict__ opacities, const float *__restrict__ viewmats,
-                       const float *__restrict__ Ks, int N, int width, int height, float eps2d, uint32_t flags,
-                       const float4 *__restrict__ splat, const long long *__restrict__ indptr, long long nnz,
-                       const long long *__restrict__ gaussian_ids, const float4 *__restrict__ g2d,
-                       const float *__restrict__ v_comps, const float *__restrict__ v_depths,
-                       float *__restrict__ scratch) {
+viewmat_partial_kernel(Form form, const float *__restrict__ viewmats, const float *__restrict__ Ks, int N, int width,
+                       int height, float eps2d, uint32_t flags, const typename Form::Visible *__restrict__ vis,
+                       const long long *__restrict__ indptr, long long nnz, const long long *__restrict__ gaussian_ids,
+                       const float4 *__restrict__ g2d, const float *__restrict__ v_comps,
+                       const float *__restrict__ v_depths, float *__restrict__ scratch) {
   __shared__ float s_part[kVg / 64][12];
   const int c = blockIdx.y;
   long long p = -1;  // index of the pair in g2d / v_comps / v_depths
@@ -64,7 +64,7 @@ viewmat_partial_kernel(const float *__restrict__ means, const float *__restrict_
     const int i = blockIdx.x * kVg + threadIdx.x;
     if (i < N) {
       const long long q = (long long)c * N + i;
-      if (__float_as_int(splat[2 * q + 1].w) > 0) { p = q; g = i; }
+      if (Form::visible(vis, q)) { p = q; g = i; }
     }
   }
   float v[12];
@@ -72,64 +72,8 @@ viewmat_partial_kernel(const float *__restrict__ means, const float *__restrict_
   for (int k = 0; k < 12; ++k) v[k] = 0.f;
   if (g >= 0) {
     const Cam cam = load_cam(viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c);
-    const Raw raw = load_raw(means, quats, scales, opacities, g);
-    const float4 ga = g2d[2 * p], gb = g2d[2 * p + 1];
-    Fwd f;
-    forward_geom<CM>(cam, raw, width, height, -3.0e38f, 3.0e38f, eps2d, flags, f);
-    Grads unused;
-    backward_geom<true, CM>(cam, f, eps2d, flags, ga, gb, true, v_comps[p], v_depths ? v_depths[p] : 0.f, unused, v, raw.m);
-  }
-  block_sum12(v, s_part);
-  if (threadIdx.x < 12) {
-    const int k = threadIdx.x;
-    scratch[((size_t)c * gridDim.x + blockIdx.x) * 12 + k] = ((s_part[0][k] + s_part[1][k]) + s_part[2][k]) + s_part[3][k];
-  }
-}
-
-// the covariance form of viewmat_partial_kernel: covars [N, 6]; DENSE pairs are visible when radii [C, N] is positive
-template <bool PACKED, int CM>
-__global__ void __launch_bounds__(kVg)
-viewmat_partial_covars_kernel(const float *__restrict__ means, const float *__restrict__ covars,
-                              const float *__restrict__ viewmats, const float *__restrict__ Ks, int N, int width,
-                              int height, float eps2d, uint32_t flags, const int *__restrict__ radii,
-                              const long long *__restrict__ indptr, long long nnz,
-                              const long long *__restrict__ gaussian_ids, const float4 *__restrict__ g2d,
-                              const float *__restrict__ v_comps, const float *__restrict__ v_depths,
-                              float *__restrict__ scratch) {
-  __shared__ float s_part[kVg / 64][12];
-  const int c = blockIdx.y;
-  long long p = -1;  // index of the pair in g2d / v_comps / v_depths
-  int g = -1;
-  if (PACKED) {
-    const long long lo = max(0ll, indptr[c]), hi = min(indptr[c + 1], nnz);  // (guards against a caller's stale array)
-    const long long q = lo + (long long)blockIdx.x * kVg + threadIdx.x;
-    if (q < hi) {
-      const long long id = gaussian_ids[q];
-      if (id >= 0 && id < N) { p = q; g = (int)id; }
-    }
-  } else {
-    const int i = blockIdx.x * kVg + threadIdx.x;
-    if (i < N) {
-      const long long q = (long long)c * N + i;
-      if (radii[q] > 0) { p = q; g = i; }
-    }
-  }
-  float v[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) v[k] = 0.f;
-  if (g >= 0) {
-    const Cam cam = load_cam(viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c);
-    float m[3], cv[6], cc[6], q0[3], q1[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) m[k] = means[3 * (size_t)g + k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) cv[k] = covars[6 * (size_t)g + k];
-    Fwd f;
-    // open cull limits: the pair passed the culls in the forward (a det cull here leaves the lane's zeros)
-    if (forward_geom_covar<CM>(cam, m, cv, width, height, -3.0e38f, 3.0e38f, eps2d, f, cc, q0, q1)) {
-      const CovarCot ct = load_covar_cot(g2d, v_comps, v_depths, p, flags & EG_FLAG_ANTIALIASED);
-      covar_pair_vjp<true, CM>(cam, m, cv, f, q0, q1, eps2d, ct, nullptr, nullptr, v);
-    }
+    typename Form::Grad unused;
+    form.template pair_vjp<true, CM>(cam, g, p, width, height, eps2d, flags, g2d, v_comps, v_depths, unused, v);
   }
   block_sum12(v, s_part);
   if (threadIdx.x < 12) {
@@ -161,6 +105,26 @@ viewmat_fold_kernel(const float *__restrict__ scratch, int B, float *__restrict_
 
 using namespace eg;
 
+// the B partials of every camera (dense: `vis`, and indptr, nnz and gaussian_ids are NULL / 0; packed: vis is NULL --
+// the entries check that), then the fold
+template <class Form>
+static void launch_viewmats(const Form &form, const float *viewmats, const float *Ks, int N, int C, int width, int height,
+                            float eps2d, uint32_t flags, const typename Form::Visible *vis, const int64_t *indptr,
+                            int64_t nnz, const int64_t *gaussian_ids, const float *g2d, const float *v_comps,
+                            const float *v_depths, float *scratch, int B, float *v_viewmats, hipStream_t s) {
+  if (B > 0)
+    with_cam_model(flags, [&](auto cm) {
+      constexpr int CM = decltype(cm)::value;
+      auto launch = [&](auto kernel) {
+        kernel<<<dim3(B, C), kVg, 0, s>>>(form, viewmats, Ks, N, width, height, eps2d, flags, vis,
+                                          (const long long *)indptr, (long long)nnz, (const long long *)gaussian_ids,
+                                          (const float4 *)g2d, v_comps, v_depths, scratch);
+      };
+      if (vis) launch(viewmat_partial_kernel<Form, false, CM>); else launch(viewmat_partial_kernel<Form, true, CM>);
+    });
+  viewmat_fold_kernel<<<C, kVg, 0, s>>>(scratch, B, v_viewmats);
+}
+
 extern "C" int eg_project_bwd_viewmats(const float *means, const float *quats, const float *scales,
                                        const float *opacities, const float *viewmats, const float *Ks, int32_t N,
                                        int32_t C, int32_t width, int32_t height, float eps2d, uint32_t flags,
@@ -179,21 +143,9 @@ extern "C" int eg_project_bwd_viewmats(const float *means, const float *quats, c
     EG_REQUIRE(means && quats && scales && opacities && g2d && v_comps && scratch, "null pointer");
     EG_REQUIRE(!packed || gaussian_ids, "null pointer");
   }
-  hipStream_t s = as_stream(stream);
-#define EG_VIEWMAT_PARTIAL(PACKED_, CM_)                                                                             \
-  viewmat_partial_kernel<PACKED_, CM_><<<dim3(B, C), kVg, 0, s>>>(                                                   \
-      means, quats, scales, opacities, viewmats, Ks, N, width, height, eps2d, flags, (const float4 *)splat,          \
-      (const long long *)indptr, (long long)nnz, (const long long *)gaussian_ids, (const float4 *)g2d, v_comps,      \
-      v_depths, scratch)
-  if (B > 0) {  // (dense: indptr, nnz and gaussian_ids are NULL / 0, checked above; packed: splat is NULL)
-    if (flags & EG_FLAG_ORTHO) {
-      if (packed) EG_VIEWMAT_PARTIAL(true, kOrtho); else EG_VIEWMAT_PARTIAL(false, kOrtho);
-    } else {
-      if (packed) EG_VIEWMAT_PARTIAL(true, kPinhole); else EG_VIEWMAT_PARTIAL(false, kPinhole);
-    }
-  }
-#undef EG_VIEWMAT_PARTIAL
-  viewmat_fold_kernel<<<C, kVg, 0, s>>>(scratch, B, v_viewmats);
+  launch_viewmats(QuatScaleForm{means, quats, scales, opacities}, viewmats, Ks, N, C, width, height, eps2d, flags,
+                  (const float4 *)splat, indptr, nnz, gaussian_ids, g2d, v_comps, v_depths, scratch, B, v_viewmats,
+                  as_stream(stream));
   return check_launch("project_bwd_viewmats");
 }
 
@@ -216,19 +168,7 @@ extern "C" int eg_project_covars_bwd_viewmats(const float *means, const float *c
     EG_REQUIRE(!(flags & EG_FLAG_ANTIALIASED) || v_comps, "null pointer");
     EG_REQUIRE(!packed || gaussian_ids, "null pointer");
   }
-  hipStream_t s = as_stream(stream);
-#define EG_VIEWMAT_PARTIAL(PACKED_, CM_)                                                                             \
-  viewmat_partial_covars_kernel<PACKED_, CM_><<<dim3(B, C), kVg, 0, s>>>(                                            \
-      means, covars, viewmats, Ks, N, width, height, eps2d, flags, radii, (const long long *)indptr, (long long)nnz, \
-      (const long long *)gaussian_ids, (const float4 *)g2d, v_comps, v_depths, scratch)
-  if (B > 0) {  // (dense: indptr, nnz and gaussian_ids are NULL / 0, checked above; packed: radii is NULL)
-    if (flags & EG_FLAG_ORTHO) {
-      if (packed) EG_VIEWMAT_PARTIAL(true, kOrtho); else EG_VIEWMAT_PARTIAL(false, kOrtho);
-    } else {
-      if (packed) EG_VIEWMAT_PARTIAL(true, kPinhole); else EG_VIEWMAT_PARTIAL(false, kPinhole);
-    }
-  }
-#undef EG_VIEWMAT_PARTIAL
-  viewmat_fold_kernel<<<C, kVg, 0, s>>>(scratch, B, v_viewmats);
+  launch_viewmats(CovarForm{means, covars, nullptr}, viewmats, Ks, N, C, width, height, eps2d, flags, radii, indptr, nnz,
+                  gaussian_ids, g2d, v_comps, v_depths, scratch, B, v_viewmats, as_stream(stream));
   return check_launch("project_covars_bwd_viewmats");
 }
