@@ -31,7 +31,7 @@ FLAG_FRONT_PREFIX = 32   # EG_FLAG_FRONT_PREFIX (tile grids above PREFIX_HERE_MA
 PREFIX_HERE_MAX_TILES = 2560  # kPrefixHereMaxTiles (csrc/common.h)
 REWALK_SPECULATE = -2  # EG_REWALK_SPECULATE
 MAX_WS_TAG = 0xfffe      # EG_MAX_WS_TAG
-TS_STAGE_BATCH = {8: 128, 32: 256}  # kStage8 / kStage32 (csrc/tiles.hip): Gaussians per staging batch of the 8- / 32-pixel compositing
+TS_STAGE_BATCH = {8: 128, 32: 256}  # kStage8 / kStage32 (csrc/tiles.hip): Gaussians per staging batch of the 8- / 32-pixel compositing (16: kStage32 too)
 PACKED_STRIDE = 0        # EG_PACKED_STRIDE: the record stride N of the mode / wide compositing entries on packed records
 
 

@@ -167,17 +167,22 @@ __device__ __forceinline__ int xcd_tile(int b, int T) {
   return x * q + (x < r ? x : r) + k;
 }
 
-// tile box [x0,x1) x [y0,y1) of a Gaussian, fp32 arithmetic in the same order as the oracle:
-// (c / 16) -+ (r / 16), floor / ceil, clamp to the grid.
-__device__ __forceinline__ void tile_box(float x, float y, int radius, int tw, int th, int &x0, int &y0,
-                                         int &x1, int &y1) {
-  const float ts = (float)kTile;
+// tile box [x0,x1) x [y0,y1) of a Gaussian on tiles of `ts` pixels, fp32 arithmetic in the same order as the oracle:
+// (c / ts) -+ (r / ts), floor / ceil, clamp to the grid.
+__device__ __forceinline__ void tile_box_ts(float x, float y, int radius, float ts, int tw, int th, int &x0, int &y0,
+                                            int &x1, int &y1) {
   const float tr = (float)radius / ts;
   const float tx = x / ts, ty = y / ts;
   x0 = min(max((int)floorf(tx - tr), 0), tw);
   y0 = min(max((int)floorf(ty - tr), 0), th);
   x1 = min(max((int)ceilf(tx + tr), 0), tw);
   y1 = min(max((int)ceilf(ty + tr), 0), th);
+}
+
+// ... on the 16-pixel tiles of the training step and of the default rasterization
+__device__ __forceinline__ void tile_box(float x, float y, int radius, int tw, int th, int &x0, int &y0,
+                                         int &x1, int &y1) {
+  tile_box_ts(x, y, radius, (float)kTile, tw, th, x0, y0, x1, y1);
 }
 
 // exclusive scan of one int per thread over a THREADS-wide workgroup (wave64 shuffles + one LDS hop)

@@ -1,6 +1,6 @@
 // Per-pixel intersection lists (gsplat rasterize_to_indices_in_range / accumulate; edgegaussians_amd/functional.py).
 //
-// indices_kernel<TS, WRITE>: the forward walk of the compositing kernels (composite_wide.hip, tiles.hip) -- the same
+// indices_kernel<TS, WRITE>: the forward walk of the chunked compositing kernels (tiles.hip) -- the same
 // source expressions for sigma, the threshold skip, alpha, the 1/255 cut and the transmittance stop, compiled with the
 // same flags -- over the batches [range_start, range_end) of every tile's list, a batch being TS * TS LIST ENTRIES,
 // starting from a caller's transmittance per pixel.  It does not composite; it COUNTS the entries a pixel takes
@@ -8,9 +8,9 @@
 // and the pixel's rows are [starts[p], starts[p] + count)).  Two passes of one deterministic walk, no atomics: the
 // rows come out in (camera, pixel) order and in list order inside a pixel, the same bits every run.
 //
-// Workgroup shapes as in the compositing: TS = 8 one 64-lane workgroup per tile, TS = 16 one 256-thread workgroup per
-// tile, TS = 32 one 256-thread workgroup per 16 x 16 quadrant.  A round stages kIxStage = 64 (TS = 8) or 256 entries
-// through LDS: two float4 per entry, 2 / 8 KiB per workgroup, far below what would bound the occupancy (8 workgroups of
+// Workgroup shapes and pixel mapping are the compositing's (ts_pixel, wide_dev.h): TS = 8 one 64-lane workgroup per
+// tile, TS = 16 one 256-thread workgroup per tile, TS = 32 one 256-thread workgroup per 16 x 16 quadrant.  A round
+// stages kIxStage = 64 (TS = 8) or 256 entries through LDS: two float4 per entry, 2 / 8 KiB per workgroup, far below what would bound the occupancy (8 workgroups of
 // four waves fill a CU's 32 wave slots at 64 KiB of its 160 KiB); the stage divides the batch, so the range bounds
 // fall on round boundaries.  Every thread reaches every barrier: a thread whose pixel lies outside the image stages
 // with the others and is "done" from the start, the loop bounds depend on the tile alone, and the only break is
@@ -28,43 +28,29 @@
 // Both are linear in the channels, so a wide D is a sequence of chunk launches: the first writes alphas / T_k / v_alpha
 // (and carries v_alphas), the later ones add their channels' share to v_alpha.
 #include "common.h"
+#include "wide_dev.h"
 
 namespace eg {
 
-constexpr int ix_threads(int ts) { return ts == 8 ? 64 : 256; }
 constexpr int ix_stage(int ts) { return ts == 8 ? 64 : 256; }  // entries per staging round; divides ts * ts
-constexpr int ix_sub(int ts) { return ts == 32 ? 4 : 1; }      // workgroups per tile
 
 template <int TS, bool WRITE>
-__global__ void __launch_bounds__(ix_threads(TS))
+__global__ void __launch_bounds__(ts_threads(TS))
 indices_kernel(const float2 *__restrict__ means2d, const float *__restrict__ conics,
                const float *__restrict__ opacities, const float *__restrict__ transmittances,
                const int *__restrict__ offsets, const int *__restrict__ flat, long long n_isects, int N, int width,
                int height, int tw, int th, long long range_start, long long range_end, int *__restrict__ counts,
                const long long *__restrict__ starts, long long total, long long *__restrict__ gaussian_ids,
                long long *__restrict__ pixel_ids, long long *__restrict__ camera_ids) {
-  constexpr int THREADS = ix_threads(TS), STAGE = ix_stage(TS), SUB = ix_sub(TS);
+  constexpr int THREADS = ts_threads(TS), STAGE = ix_stage(TS);
   constexpr long long BATCH = (long long)TS * TS;
   static_assert(BATCH % STAGE == 0 && STAGE <= THREADS, "a round is one entry per thread and divides the batch");
   __shared__ float4 sA[STAGE];  // x, y, a, b
   __shared__ float4 sB[STAGE];  // c, o, sigma threshold, Gaussian id (int bits)
 
-  const int c = blockIdx.y, n_tiles = tw * th;
-  const int unit = xcd_tile(blockIdx.x, n_tiles * SUB);
-  const int tile = unit / SUB, q = unit % SUB, tid = threadIdx.x;
-  const int ty = tile / tw, tx = tile - ty * tw;
-  int i0, j0, i, j;
-  if constexpr (TS == 8) {
-    i0 = ty * 8; j0 = tx * 8;
-    i = i0 + (tid >> 3); j = j0 + (tid & 7);
-  } else if constexpr (TS == 16) {
-    i0 = ty * 16; j0 = tx * 16;
-    i = i0 + (tid >> 4); j = j0 + (tid & 15);
-  } else {
-    i0 = ty * 32 + (q >> 1) * 16; j0 = tx * 32 + (q & 1) * 16;
-    i = i0 + (tid >> 4); j = j0 + (tid & 15);
-  }
-  if (i0 >= height || j0 >= width) return;  // (a quadrant outside the image: the whole workgroup)
+  const int c = blockIdx.y, n_tiles = tw * th, tid = threadIdx.x;
+  int tile, i, j;
+  if (!ts_pixel<TS>(tw, th, width, height, tile, i, j)) return;  // (a quadrant outside the image: the whole workgroup)
 
   // the tile's entries [lo, hi) of flat, then the call's batches of them [first, last): workgroup-uniform
   long long lo = 0;
@@ -220,7 +206,7 @@ using namespace eg;
   } while (0)
 
 #define EG_IX_LAUNCH(TS, WRITE)                                                                                      \
-  indices_kernel<TS, WRITE><<<dim3(tw * th * ix_sub(TS), C), ix_threads(TS), 0, s>>>(                                \
+  indices_kernel<TS, WRITE><<<dim3(tw * th * ts_sub(TS), C), ts_threads(TS), 0, s>>>(                                \
       (const float2 *)means2d, conics, opacities, transmittances, offsets, flatten_ids, (long long)n_isects, N, width, \
       height, tw, th, (long long)range_start, (long long)range_end, counts_, starts_, (long long)total_,              \
       (long long *)gids_, (long long *)pids_, (long long *)cids_)

@@ -1,5 +1,7 @@
-// Tile sizes 8 and 32 (rasterization(tile_size=8 | 32)): binning with a run-time tile size and the compositing kernels
-// templated on it.  tile_size = 16 never comes here: it keeps binning.hip, composite.hip and composite_wide.hip.
+// Binning with a run-time tile size (rasterization(tile_size=8 | 32)) and the chunked compositing kernels, templated on
+// the tile size, for tiles of 8, 16 and 32 pixels.  At tile_size = 16 the binning is binning.hip's and D = 1, 3 and the
+// depth-only modes are composited by composite.hip; colours of any other channel count come here
+// (eg_composite_{fwd,bwd}_wide_cams).
 //
 // Binning.  tile_count_kernel / tile_emit_kernel of binning.hip with the tile size as an argument: the same tile box
 // ((x / ts) -+ (r / ts) in fp32, floor / ceil, clamp), the same LDS-privatised histogram (grids of up to 16 384 tiles for
@@ -9,9 +11,30 @@
 // array of C + 1 range bounds, which serves both layouts of the projection: [c N, (c + 1) N) for the dense [C, N, ...]
 // arrays, indptr for the packed lists.
 //
-// Compositing: one kernel family <TS, CH, DEPTH, BG> for chunks of CH = 2 .. 32 channels (n_real of them real) and the
-// depth-only form CH = 0, which stages no colours; the walk, its source expressions, the staging through LDS, the halving
-// exchange and the single-atomic write-out are those of composite_wide.hip.
+// Compositing: one kernel family <TS, CH, DEPTH, BG>.  A call composites ONE chunk of `n_real` channels that lives
+// inside full-width tensors: colors / v_colors / backgrounds are addressed with the row stride `cs`, render / v_render
+// with the row stride `ps`, so the caller passes pointers to the chunk's first channel and never copies.  CH = 2, 4, 8,
+// 16, 32; a narrower chunk runs in the next width up, its padding channels staged as exact zeros and never loaded from
+// or written to global memory (n_real guards every load, store and atomic).  CH = 0 (tiles of 8 and 32 only) is the
+// depth-only form, which stages no colours.
+//
+// Forward: the per-pixel walk of composite_fwd_kernel (composite.hip) with the same source expressions for sigma, the
+// threshold skip, alpha, the 1/255 cut and the transmittance stop, so alphas and last_ids do not depend on the width or
+// on how a call is cut into chunks.  The colour rows of a batch are staged through LDS by the whole workgroup, one
+// 16-byte unit per lane (consecutive lanes fetch consecutive units of a row: coalesced loads, conflict-free
+// ds_write_b128); the walk reads them back as broadcast ds_read_b128.
+//
+// Backward: the walk of composite_bwd_colors_kernel.  Its reduction -- one six-step butterfly per partial, then lane 0
+// issuing every atomic -- costs 6 (8 + CH + 1) cross-lane operations and 8 + CH + 1 serial atomics per (wave,
+// Gaussian).  Here the CH colour partials and the 8 splat-side partials are reduced by a HALVING EXCHANGE
+// (lane_transpose_sum, wide_dev.h): in a step over lane bit b a lane keeps one half of its values, hands the other half to
+// lane ^ (1 << b) and adds what it receives, so n values cost n/2 + n/4 + ... + 1 = n - 1 exchanges and finish with
+// component k in lane k.  Lanes 0 .. CH-1 then hold the colour sums, lanes 32 .. 39 the splat-side sums and lane 63
+// the depth sum, and ONE atomic instruction adds them all: consecutive lanes to consecutive addresses.  Measured
+// against the plain scheme instantiated at the same widths (profiles/channels_bwd_reduction_ab.jsonl).
+//
+//   ts = 16  ONE 256-THREAD WORKGROUP PER TILE, one pixel per thread, kStage32 = 256 Gaussians per batch: the shape of
+//            the classic kernels of composite.hip.
 //   ts = 8   a tile is 64 pixels = one wave: ONE 64-LANE WORKGROUP PER TILE.  The wave stages kStage8 = 128 Gaussians per
 //            batch (two per lane) and walks them; a barrier of a one-wave workgroup costs nothing, and no wave ever waits
 //            for the list of another tile (four tiles per 256-thread workgroup would hold the three short lists' waves --
@@ -31,18 +54,7 @@ namespace eg {
 constexpr int kTsBinThreads = 512;
 constexpr int kTsMaxLdsWords = 16384;  // 64 KiB of LDS counters; larger grids use the direct-atomic path
 
-inline bool tile_size_ok(int ts) { return ts == 8 || ts == 32; }  // (16: binning.hip, composite*.hip)
-
-// common.h tile_box with `ts` in place of 16
-__device__ __forceinline__ void tile_box_ts(float x, float y, int radius, float ts, int tw, int th, int &x0, int &y0,
-                                            int &x1, int &y1) {
-  const float tr = (float)radius / ts;
-  const float tx = x / ts, ty = y / ts;
-  x0 = min(max((int)floorf(tx - tr), 0), tw);
-  y0 = min(max((int)floorf(ty - tr), 0), th);
-  x1 = min(max((int)ceilf(tx + tr), 0), tw);
-  y1 = min(max((int)ceilf(ty + tr), 0), th);
-}
+inline bool tile_size_ok(int ts) { return ts == 8 || ts == 32; }  // (16: binning.hip and the wide entries)
 
 // one camera's n Gaussians: tiles_per_gauss [n] (NULL ok), tile_counts [T] accumulated
 template <bool LDS>
@@ -145,29 +157,8 @@ ts_rebase_kernel(int *__restrict__ flatten_ids, long long *__restrict__ isect_id
 // ---------------------------------------------------------------------------------------------
 // compositing
 constexpr int kStage8 = 128;   // Gaussians per staging batch, ts = 8 (64 lanes: two per lane)
-constexpr int kStage32 = 256;  // ... ts = 32 (256 threads: one per thread)
-constexpr int ts_threads(int ts) { return ts == 8 ? 64 : 256; }
+constexpr int kStage32 = 256;  // ... ts = 16 and 32 (256 threads: one per thread)
 constexpr int ts_stage(int ts) { return ts == 8 ? kStage8 : kStage32; }
-constexpr int ts_sub(int ts) { return ts == 32 ? 4 : 1; }  // workgroups per tile
-
-// workgroup -> (tile, pixel of this thread); false: the workgroup's pixels all lie outside the image (uniform)
-template <int TS>
-__device__ __forceinline__ bool ts_pixel(int tw, int th, int width, int height, int &tile, int &i, int &j) {
-  constexpr int SUB = ts_sub(TS);
-  const int unit = xcd_tile(blockIdx.x, tw * th * SUB);  // (the quadrants of a tile are neighbours: one XCD, mostly)
-  tile = unit / SUB;
-  const int q = unit % SUB, tid = threadIdx.x;
-  const int ty = tile / tw, tx = tile - ty * tw;
-  int i0, j0;
-  if constexpr (TS == 8) {
-    i0 = ty * 8; j0 = tx * 8;
-    i = i0 + (tid >> 3); j = j0 + (tid & 7);
-  } else {
-    i0 = ty * 32 + (q >> 1) * 16; j0 = tx * 32 + (q & 1) * 16;
-    i = i0 + (tid >> 4); j = j0 + (tid & 15);
-  }
-  return i0 < height && j0 < width;
-}
 
 template <int TS, int CH, bool DEPTH, bool BG>
 __global__ void __launch_bounds__(ts_threads(TS))
@@ -491,6 +482,16 @@ extern "C" int eg_tile_emit_sort_ts(const float *means2d, const int32_t *radii, 
   return EG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Chunked compositing.  Two pairs of entries, each with its own argument checks (the wide pair: 16-pixel tiles, no
+// tile_size argument, no depth-only form), then one launcher per direction.
+#define EG_WIDE_CHECK(C, N, channels, n_real, depth, width, height, cs, ps)                                  \
+  EG_REQUIRE(C >= 1 && C <= 65535 && N >= 0 && width > 0 && height > 0, "bad sizes");                         \
+  EG_REQUIRE(channels >= 1 && channels <= 32, "channels (the chunk width) must be 1 .. 32");                  \
+  EG_REQUIRE(n_real >= 1 && n_real <= channels, "n_real must be 1 .. channels");                              \
+  EG_REQUIRE(cs >= n_real, "color_stride is smaller than the channel count");                                 \
+  EG_REQUIRE(ps >= n_real + (depth ? 1 : 0), "pixel_stride is smaller than the channel count")
+
 #define EG_TS_CHECK(C, N, channels, n_real, depth, width, height, tile_size, cs, ps)                          \
   EG_REQUIRE(tile_size_ok(tile_size), "tile_size must be 8 or 32 (16: eg_composite_*_wide_cams)");            \
   EG_REQUIRE(C >= 1 && C <= 65535 && N >= 0 && width > 0 && height > 0, "bad sizes");                         \
@@ -501,6 +502,7 @@ extern "C" int eg_tile_emit_sort_ts(const float *means2d, const int32_t *radii, 
   EG_REQUIRE(ps >= n_real + (depth ? 1 : 0), "pixel_stride is smaller than the channel count");               \
   EG_REQUIRE((int64_t)cdiv(width, tile_size) * cdiv(height, tile_size) * 4 < (1ll << 31), "bad sizes")
 
+// tile size, then channel width, then (DEPTH, BG)
 #define EG_TS_DB(LAUNCH, TS, CH)                                                        \
   do {                                                                                  \
     if (depth) { if (bg) LAUNCH(TS, CH, true, true); else LAUNCH(TS, CH, true, false); } \
@@ -509,24 +511,101 @@ extern "C" int eg_tile_emit_sort_ts(const float *means2d, const int32_t *radii, 
 
 #define EG_TS_CH(LAUNCH, TS)                            \
   do {                                                  \
-    if (channels == 0) LAUNCH(TS, 0, true, false);      \
-    else if (channels <= 2) EG_TS_DB(LAUNCH, TS, 2);    \
+    if (channels <= 2) EG_TS_DB(LAUNCH, TS, 2);         \
     else if (channels <= 4) EG_TS_DB(LAUNCH, TS, 4);    \
     else if (channels <= 8) EG_TS_DB(LAUNCH, TS, 8);    \
     else if (channels <= 16) EG_TS_DB(LAUNCH, TS, 16);  \
     else EG_TS_DB(LAUNCH, TS, 32);                      \
   } while (0)
 
-#define EG_TS_DISPATCH(LAUNCH)                                                   \
-  do {                                                                           \
-    if (tile_size == 8) EG_TS_CH(LAUNCH, 8); else EG_TS_CH(LAUNCH, 32);          \
+// (the depth-only form CH = 0 exists at 8 and 32 alone: at 16 the depth-only modes are composite.hip's)
+#define EG_TS_DISPATCH(LAUNCH)                                                                                  \
+  do {                                                                                                          \
+    if (tile_size == 16) EG_TS_CH(LAUNCH, 16);                                                                  \
+    else if (channels == 0) { if (tile_size == 8) LAUNCH(8, 0, true, false); else LAUNCH(32, 0, true, false); } \
+    else if (tile_size == 8) EG_TS_CH(LAUNCH, 8);                                                               \
+    else EG_TS_CH(LAUNCH, 32);                                                                                  \
   } while (0)
 
 // the colour rows can be fetched in 16-byte (CH = 2: 8-byte) units
-static int ts_rows_aligned(const float *colors, int channels, int cs) {
+static int wide_rows_aligned(const float *colors, int channels, int cs) {
   if (channels == 0) return 0;
   const int vw = channels <= 2 ? 2 : 4;
   return ((uintptr_t)colors % (vw * sizeof(float)) == 0) && (cs % vw == 0);
+}
+
+// (the arguments are the entries', checked there; `entry` names the entry in a launch error)
+static int ts_composite_fwd_launch(const char *entry, int tile_size, int C, const float *splat, int N,
+                                   const float *colors, int colors_per_camera, int channels, int depth,
+                                   const float *backgrounds, const int32_t *offsets, const int32_t *flatten_ids,
+                                   int width, int height, float *render, float *alphas, int32_t *last_ids, int n_real,
+                                   int color_stride, int pixel_stride, eg_stream_t stream) {
+  const int tw = cdiv(width, tile_size), th = cdiv(height, tile_size);
+  const float *bg = channels > 0 ? backgrounds : nullptr;
+  const WideArgs wa = {bg, nullptr, N, colors_per_camera != 0, n_real, color_stride, pixel_stride,
+                       wide_rows_aligned(colors, channels, color_stride)};
+  hipStream_t s = as_stream(stream);
+#define EG_LAUNCH_FWD_TS(TS, CH, DEPTH, BG)                                                                     \
+  ts_composite_fwd_kernel<TS, CH, DEPTH, BG><<<dim3(tw * th * ts_sub(TS), C), ts_threads(TS), 0, s>>>(          \
+      (const float4 *)splat, colors, offsets, flatten_ids, width, height, tw, th, render, alphas, last_ids, wa)
+  EG_TS_DISPATCH(EG_LAUNCH_FWD_TS);
+#undef EG_LAUNCH_FWD_TS
+  return check_launch(entry);
+}
+
+static int ts_composite_bwd_launch(const char *entry, int tile_size, int C, const float *splat, int N,
+                                   const float *colors, int colors_per_camera, int channels, int depth,
+                                   const float *backgrounds, const int32_t *offsets, const int32_t *flatten_ids,
+                                   int width, int height, const float *alphas, const int32_t *last_ids,
+                                   const float *v_render, const float *v_alphas, float *g2d, float *v_colors,
+                                   float *v_depths, int n_real, int color_stride, int pixel_stride,
+                                   eg_stream_t stream) {
+  const int tw = cdiv(width, tile_size), th = cdiv(height, tile_size);
+  const float *bg = channels > 0 ? backgrounds : nullptr;
+  const WideArgs wa = {bg, v_depths, N, colors_per_camera != 0, n_real, color_stride, pixel_stride,
+                       wide_rows_aligned(colors, channels, color_stride)};
+  hipStream_t s = as_stream(stream);
+#define EG_LAUNCH_BWD_TS(TS, CH, DEPTH, BG)                                                                     \
+  ts_composite_bwd_kernel<TS, CH, DEPTH, BG><<<dim3(tw * th * ts_sub(TS), C), ts_threads(TS), 0, s>>>(          \
+      (const float4 *)splat, colors, offsets, flatten_ids, width, height, tw, th, alphas, last_ids, v_render,      \
+      v_alphas, g2d, v_colors, wa)
+  EG_TS_DISPATCH(EG_LAUNCH_BWD_TS);
+#undef EG_LAUNCH_BWD_TS
+  return check_launch(entry);
+}
+#undef EG_TS_DISPATCH
+#undef EG_TS_CH
+#undef EG_TS_DB
+
+extern "C" int eg_composite_fwd_wide_cams(int32_t C, const float *splat, int32_t N, const float *colors,
+                                          int32_t colors_per_camera, int32_t channels, int32_t depth,
+                                          const float *backgrounds, const int32_t *offsets,
+                                          const int32_t *flatten_ids, int32_t width, int32_t height, float *render,
+                                          float *alphas, int32_t *last_ids, int32_t n_real, int32_t color_stride,
+                                          int32_t pixel_stride, eg_stream_t stream) {
+  EG_WIDE_CHECK(C, N, channels, n_real, depth, width, height, color_stride, pixel_stride);
+  EG_REQUIRE(colors, "null colors (channels > 0)");
+  EG_REQUIRE(splat && offsets && flatten_ids && render, "null pointer");
+  return ts_composite_fwd_launch("composite_fwd_wide_cams", kTile, C, splat, N, colors, colors_per_camera, channels,
+                                 depth, backgrounds, offsets, flatten_ids, width, height, render, alphas, last_ids,
+                                 n_real, color_stride, pixel_stride, stream);
+}
+
+extern "C" int eg_composite_bwd_wide_cams(int32_t C, const float *splat, int32_t N, const float *colors,
+                                          int32_t colors_per_camera, int32_t channels, int32_t depth,
+                                          const float *backgrounds, const int32_t *offsets,
+                                          const int32_t *flatten_ids, int32_t width, int32_t height,
+                                          const float *alphas, const int32_t *last_ids, const float *v_render,
+                                          const float *v_alphas, float *g2d, float *v_colors, float *v_depths,
+                                          int32_t n_real, int32_t color_stride, int32_t pixel_stride,
+                                          eg_stream_t stream) {
+  EG_WIDE_CHECK(C, N, channels, n_real, depth, width, height, color_stride, pixel_stride);
+  EG_REQUIRE(colors, "null colors (channels > 0)");
+  EG_REQUIRE(splat && offsets && flatten_ids && alphas && last_ids && v_render && g2d, "null pointer");
+  EG_REQUIRE(!depth || v_depths, "null v_depths (depth channel)");
+  return ts_composite_bwd_launch("composite_bwd_wide_cams", kTile, C, splat, N, colors, colors_per_camera, channels,
+                                 depth, backgrounds, offsets, flatten_ids, width, height, alphas, last_ids, v_render,
+                                 v_alphas, g2d, v_colors, v_depths, n_real, color_stride, pixel_stride, stream);
 }
 
 extern "C" int eg_composite_fwd_ts_cams(int32_t C, const float *splat, int32_t N, const float *colors,
@@ -538,17 +617,9 @@ extern "C" int eg_composite_fwd_ts_cams(int32_t C, const float *splat, int32_t N
   EG_TS_CHECK(C, N, channels, n_real, depth, width, height, tile_size, color_stride, pixel_stride);
   EG_REQUIRE(channels == 0 || colors, "null colors (channels > 0)");
   EG_REQUIRE(splat && offsets && flatten_ids && render, "null pointer");
-  const int tw = cdiv(width, tile_size), th = cdiv(height, tile_size);
-  const float *bg = channels > 0 ? backgrounds : nullptr;
-  const WideArgs wa = {bg, nullptr, N, colors_per_camera != 0, n_real, color_stride, pixel_stride,
-                       ts_rows_aligned(colors, channels, color_stride)};
-  hipStream_t s = as_stream(stream);
-#define EG_LAUNCH_FWD_TS(TS, CH, DEPTH, BG)                                                                     \
-  ts_composite_fwd_kernel<TS, CH, DEPTH, BG><<<dim3(tw * th * ts_sub(TS), C), ts_threads(TS), 0, s>>>(          \
-      (const float4 *)splat, colors, offsets, flatten_ids, width, height, tw, th, render, alphas, last_ids, wa)
-  EG_TS_DISPATCH(EG_LAUNCH_FWD_TS);
-#undef EG_LAUNCH_FWD_TS
-  return check_launch("composite_fwd_ts_cams");
+  return ts_composite_fwd_launch("composite_fwd_ts_cams", tile_size, C, splat, N, colors, colors_per_camera, channels,
+                                 depth, backgrounds, offsets, flatten_ids, width, height, render, alphas, last_ids,
+                                 n_real, color_stride, pixel_stride, stream);
 }
 
 extern "C" int eg_composite_bwd_ts_cams(int32_t C, const float *splat, int32_t N, const float *colors,
@@ -562,21 +633,11 @@ extern "C" int eg_composite_bwd_ts_cams(int32_t C, const float *splat, int32_t N
   EG_REQUIRE(channels == 0 || colors, "null colors (channels > 0)");
   EG_REQUIRE(splat && offsets && flatten_ids && alphas && last_ids && v_render && g2d, "null pointer");
   EG_REQUIRE(!depth || v_depths, "null v_depths (depth channel)");
-  const int tw = cdiv(width, tile_size), th = cdiv(height, tile_size);
-  const float *bg = channels > 0 ? backgrounds : nullptr;
-  const WideArgs wa = {bg, v_depths, N, colors_per_camera != 0, n_real, color_stride, pixel_stride,
-                       ts_rows_aligned(colors, channels, color_stride)};
-  hipStream_t s = as_stream(stream);
-#define EG_LAUNCH_BWD_TS(TS, CH, DEPTH, BG)                                                                     \
-  ts_composite_bwd_kernel<TS, CH, DEPTH, BG><<<dim3(tw * th * ts_sub(TS), C), ts_threads(TS), 0, s>>>(          \
-      (const float4 *)splat, colors, offsets, flatten_ids, width, height, tw, th, alphas, last_ids, v_render,      \
-      v_alphas, g2d, v_colors, wa)
-  EG_TS_DISPATCH(EG_LAUNCH_BWD_TS);
-#undef EG_LAUNCH_BWD_TS
-  return check_launch("composite_bwd_ts_cams");
+  return ts_composite_bwd_launch("composite_bwd_ts_cams", tile_size, C, splat, N, colors, colors_per_camera, channels,
+                                 depth, backgrounds, offsets, flatten_ids, width, height, alphas, last_ids, v_render,
+                                 v_alphas, g2d, v_colors, v_depths, n_real, color_stride, pixel_stride, stream);
 }
-#undef EG_TS_DISPATCH
-#undef EG_TS_CH
-#undef EG_TS_DB
 #undef EG_TS_CHECK
+#undef EG_WIDE_CHECK
 #undef EG_TS_RANGES
+

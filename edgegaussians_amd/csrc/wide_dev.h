@@ -1,9 +1,35 @@
-// Device helpers shared by the chunked compositing kernels (composite_wide.hip: 16-pixel tiles; tiles.hip: 8- and
-// 32-pixel tiles): the chunk's addressing block, the cameras' list bases and the halving-exchange wave reduction.
+// Device helpers of the chunked compositing kernels (tiles.hip: tiles of 8, 16 and 32 pixels) and of the per-pixel
+// lists (indices.hip): the workgroup -> (tile, pixel) mapping of the three tile sizes, the chunk's addressing block, the
+// cameras' list bases, the staging of the colour rows and the halving-exchange wave reduction.
 #pragma once
 #include "common.h"
 
 namespace eg {
+
+// ts = 8: one 64-lane workgroup per tile; 16: one 256-thread workgroup per tile; 32: one per 16 x 16 quadrant
+constexpr int ts_threads(int ts) { return ts == 8 ? 64 : 256; }
+constexpr int ts_sub(int ts) { return ts == 32 ? 4 : 1; }  // workgroups per tile
+
+// workgroup -> (tile, pixel of this thread); false: the workgroup's pixels all lie outside the image (uniform)
+template <int TS>
+__device__ __forceinline__ bool ts_pixel(int tw, int th, int width, int height, int &tile, int &i, int &j) {
+  static_assert(TS == 8 || TS == 16 || TS == 32, "tile sizes 8, 16 and 32");
+  constexpr int SUB = ts_sub(TS);
+  const int unit = xcd_tile(blockIdx.x, tw * th * SUB);  // (the quadrants of a tile are neighbours: one XCD, mostly)
+  tile = unit / SUB;
+  const int q = unit % SUB, tid = threadIdx.x;
+  const int ty = tile / tw, tx = tile - ty * tw;
+  int i0, j0;
+  if constexpr (TS == 8) {
+    i0 = ty * 8; j0 = tx * 8;
+    i = i0 + (tid >> 3); j = j0 + (tid & 7);
+  } else {  // a 16 x 16 block of pixels: the tile (q == 0), or quadrant q of a 32-pixel tile
+    i0 = ty * TS + (q >> 1) * 16; j0 = tx * TS + (q & 1) * 16;
+    i = i0 + (tid >> 4); j = j0 + (tid & 15);
+  }
+  // (a tile's first pixel is always inside the image; a quadrant's need not be)
+  return TS == 16 || (i0 < height && j0 < width);
+}
 
 struct WideArgs {
   const float *bg;    // backgrounds of the chunk: camera c's row at bg + c * cs (BG)
@@ -25,7 +51,7 @@ __device__ __forceinline__ int wide_list_base(const int *__restrict__ offsets, i
 
 // Colour rows of the n Gaussians flat[first + step * r], r = 0 .. n-1, into sC[r * CH ..]: unit e = (row, 4 channels)
 // is fetched by thread e % THREADS with one 16-byte load where the rows are aligned and the unit holds real channels only.
-template <int CH, int THREADS = kTilePix>
+template <int CH, int THREADS>
 __device__ __forceinline__ void stage_colors(float *__restrict__ sC, const float *__restrict__ colors,
                                              const int *__restrict__ flat, int first, int step, int n,
                                              const WideArgs &wa) {

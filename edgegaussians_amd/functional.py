@@ -310,12 +310,9 @@ def rasterize_to_pixels(means2d: Tensor, conics: Tensor, colors: Tensor, opaciti
         # (clamped into the list: offsets outside it must not send a kernel outside `flatten_ids`)
         local = torch.cat([first - first[:, :1], (ends - first[:, 0])[:, None]], dim=1).clamp_(0, M).contiguous()
     opac = opacities.contiguous()
-    if tile_size != TILE:
+    if tile_size != TILE or D not in (1, 3):
         render, alphas, _ = _R._TileCompositing.apply(means2d, conics, colors, opac, None, backgrounds, width, height, local,
                                                       flat, bool(absgrad), splat, False, 32, tile_size)
-    elif D not in (1, 3):
-        render, alphas, _ = _R._WideCompositing.apply(means2d, conics, colors, opac, None, backgrounds, width, height, local,
-                                                      flat, bool(absgrad), splat, False, 32)
     elif backgrounds is not None:
         render, alphas, _ = _R._ModeCompositing.apply(means2d, conics, colors, opac, None, backgrounds, width, height, local,
                                                       flat, bool(absgrad), splat, False)

@@ -565,77 +565,23 @@ class _ModeCompositing(torch.autograd.Function):
                 None, None, None, None, None, None, None, None)
 
 
-class _WideCompositing(torch.autograd.Function):
-    """`_ModeCompositing` for colours of any channel count D (csrc/composite_wide.hip): the D channels are composited in
-    ceil(D / chunk) launches per direction of eg_composite_{fwd,bwd}_wide_cams, each addressing its chunk inside the
-    full-width tensors (no copies).  Forward: the first chunk writes `alphas` and `last_ids`, the depth channel rides on
-    the last.  Backward: the first chunk alone receives `v_alphas`; g2d and v_depths are zeroed once and accumulated
-    over the chunks, so `absgrad` is the sum of the chunks' abs-gradients."""
-
-    @staticmethod
-    def forward(ctx, means2d, conics, colors, opacities, depths, backgrounds, width, height, offsets, flatten_ids,
-                absgrad, packed_splat, depth, chunk, packed_cams=None):
-        # (packed_cams: as in _ModeCompositing)
-        Cn, N = (packed_cams, _lib.PACKED_STRIDE) if packed_cams is not None else (means2d.shape[0], means2d.shape[1])
-        _ptr1 = _ptr_or_dummy if packed_cams is not None else ptr
-        dev = means2d.device
-        D = colors.shape[-1]
-        colors_c = colors.contiguous()
-        bg = backgrounds.contiguous() if backgrounds is not None else None
-        P = D + int(depth)
-        render = torch.empty(Cn, height, width, P, device=dev)
-        alphas = torch.empty(Cn, height, width, 1, device=dev)
-        last_ids = torch.empty(Cn, height, width, dtype=torch.int32, device=dev)
-        per_cam = int(colors_c.dim() == 3 or packed_cams is not None)
-        for c0 in range(0, D, chunk):
-            w = min(chunk, D - c0)
-            first, final = c0 == 0, c0 + w == D
-            call("eg_composite_fwd_wide_cams", Cn, _ptr1(packed_splat), N, _ptr1(colors_c) + 4 * c0, per_cam, w,
-                 int(depth and final), ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width,
-                 height, ptr(render) + 4 * c0, ptr(alphas) if first else None, ptr(last_ids) if first else None, w, D, P,
-                 stream())
-        ctx.save_for_backward(means2d, packed_splat, colors_c, bg, alphas, last_ids, offsets, flatten_ids)
-        ctx.cfg = (width, height, absgrad, depth, D, per_cam, chunk, packed_cams)
-        ctx.mark_non_differentiable(last_ids)
-        return render, alphas, last_ids
-
-    @staticmethod
-    def backward(ctx, v_render, v_alphas, _v_last):
-        width, height, absgrad, depth, D, per_cam, chunk, packed_cams = ctx.cfg
-        means2d, splat, colors, bg, alphas, last_ids, offsets, flatten_ids = ctx.saved_tensors
-        Cn, N = (packed_cams, _lib.PACKED_STRIDE) if packed_cams is not None else (means2d.shape[0], means2d.shape[1])
-        lead = tuple(means2d.shape[:-1])  # (C, N), or (nnz,) on packed records
-        _ptr1 = _ptr_or_dummy if packed_cams is not None else ptr
-        dev = means2d.device
-        P = D + int(depth)
-        v_render = v_render.contiguous()
-        v_alphas = v_alphas.contiguous()
-        g2d = torch.zeros(*lead, 8, device=dev)
-        v_colors = torch.zeros(*lead, D, device=dev) if ctx.needs_input_grad[2] else None
-        v_depths = torch.zeros(*lead, device=dev) if depth else None
-        for c0 in range(0, D, chunk):
-            w = min(chunk, D - c0)
-            first, final = c0 == 0, c0 + w == D
-            call("eg_composite_bwd_wide_cams", Cn, _ptr1(splat), N, _ptr1(colors) + 4 * c0, per_cam, w, int(depth and final),
-                 ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width, height, ptr(alphas),
-                 ptr(last_ids), ptr(v_render) + 4 * c0, ptr(v_alphas) if first else None, _ptr1(g2d),
-                 _ptr1(v_colors) + 4 * c0 if v_colors is not None else None,
-                 _ptr1(v_depths) if (depth and final) else None, w, D, P, stream())
-        if v_colors is not None and not per_cam:
-            v_colors = v_colors.sum(0)
-        v_bg = None
-        if bg is not None and ctx.needs_input_grad[5]:  # (gsplat computes it in torch the same way)
-            v_bg = (v_render[..., :D] * (1.0 - alphas)).sum((1, 2))
-        if absgrad:
-            means2d.absgrad = g2d[..., 2:4].contiguous()
-        return (g2d[..., 0:2].contiguous(), g2d[..., 4:7].contiguous(), v_colors, g2d[..., 7].contiguous(), v_depths, v_bg,
-                None, None, None, None, None, None, None, None, None)
+def _call_chunked(direction, tile_size, head, tail):
+    """One launch of the chunked compositing (csrc/tiles.hip).  `head` ends with width and height; the entries for
+    16-pixel tiles, eg_composite_{fwd,bwd}_wide_cams, take no tile_size after them."""
+    if tile_size == TILE:
+        call(f"eg_composite_{direction}_wide_cams", *head, *tail)
+    else:
+        call(f"eg_composite_{direction}_ts_cams", *head, tile_size, *tail)
 
 
 class _TileCompositing(torch.autograd.Function):
-    """`_WideCompositing` on tiles of 8 or 32 pixels (csrc/tiles.hip, eg_composite_{fwd,bwd}_ts_cams): every channel
-    count goes through the one kernel family, D = 1 and 3 included, in chunks of `chunk` channels; `colors` None (the
-    depth-only modes) is one launch each way of the form that stages no colours."""
+    """`_ModeCompositing` by the chunked kernels (csrc/tiles.hip): at 16-pixel tiles for colours of any channel count D
+    other than 1 and 3, at 8 and 32 for every mode, D = 1 and 3 included; `colors` None (the depth-only modes, 8 and 32
+    alone) is one launch each way of the form that stages no colours.  The D channels are composited in
+    ceil(D / chunk) launches per direction, each addressing its chunk inside the full-width tensors (no copies).
+    Forward: the first chunk writes `alphas` and `last_ids`, the depth channel rides on the last.  Backward: the first
+    chunk alone receives `v_alphas`; g2d and v_depths are zeroed once and accumulated over the chunks, so `absgrad` is
+    the sum of the chunks' abs-gradients."""
 
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, depths, backgrounds, width, height, offsets, flatten_ids,
@@ -653,15 +599,17 @@ class _TileCompositing(torch.autograd.Function):
         last_ids = torch.empty(Cn, height, width, dtype=torch.int32, device=dev)
         per_cam = int(colors_c is not None and (colors_c.dim() == 3 or packed_cams is not None))
         if D == 0:
-            call("eg_composite_fwd_ts_cams", Cn, _ptr1(packed_splat), N, None, 0, 0, 1, None, ptr(offsets), ptr(flatten_ids),
-                 width, height, tile_size, ptr(render), ptr(alphas), ptr(last_ids), 0, 0, P, stream())
+            _call_chunked("fwd", tile_size,
+                          (Cn, _ptr1(packed_splat), N, None, 0, 0, 1, None, ptr(offsets), ptr(flatten_ids), width, height),
+                          (ptr(render), ptr(alphas), ptr(last_ids), 0, 0, P, stream()))
         for c0 in range(0, D, chunk):
             w = min(chunk, D - c0)
             first, final = c0 == 0, c0 + w == D
-            call("eg_composite_fwd_ts_cams", Cn, _ptr1(packed_splat), N, _ptr1(colors_c) + 4 * c0, per_cam, w,
-                 int(depth and final), ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width,
-                 height, tile_size, ptr(render) + 4 * c0, ptr(alphas) if first else None, ptr(last_ids) if first else None,
-                 w, D, P, stream())
+            _call_chunked("fwd", tile_size,
+                          (Cn, _ptr1(packed_splat), N, _ptr1(colors_c) + 4 * c0, per_cam, w, int(depth and final),
+                           ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width, height),
+                          (ptr(render) + 4 * c0, ptr(alphas) if first else None, ptr(last_ids) if first else None,
+                           w, D, P, stream()))
         ctx.save_for_backward(means2d, packed_splat, colors_c, bg, alphas, last_ids, offsets, flatten_ids)
         ctx.cfg = (width, height, absgrad, depth, D, per_cam, chunk, tile_size, packed_cams)
         ctx.mark_non_differentiable(last_ids)
@@ -682,17 +630,19 @@ class _TileCompositing(torch.autograd.Function):
         v_colors = torch.zeros(*lead, D, device=dev) if (D > 0 and ctx.needs_input_grad[2]) else None
         v_depths = torch.zeros(*lead, device=dev) if depth else None
         if D == 0:
-            call("eg_composite_bwd_ts_cams", Cn, _ptr1(splat), N, None, 0, 0, 1, None, ptr(offsets), ptr(flatten_ids), width,
-                 height, tile_size, ptr(alphas), ptr(last_ids), ptr(v_render), ptr(v_alphas), _ptr1(g2d), None,
-                 _ptr1(v_depths), 0, 0, P, stream())
+            _call_chunked("bwd", tile_size,
+                          (Cn, _ptr1(splat), N, None, 0, 0, 1, None, ptr(offsets), ptr(flatten_ids), width, height),
+                          (ptr(alphas), ptr(last_ids), ptr(v_render), ptr(v_alphas), _ptr1(g2d), None, _ptr1(v_depths),
+                           0, 0, P, stream()))
         for c0 in range(0, D, chunk):
             w = min(chunk, D - c0)
             first, final = c0 == 0, c0 + w == D
-            call("eg_composite_bwd_ts_cams", Cn, _ptr1(splat), N, _ptr1(colors) + 4 * c0, per_cam, w, int(depth and final),
-                 ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width, height, tile_size,
-                 ptr(alphas), ptr(last_ids), ptr(v_render) + 4 * c0, ptr(v_alphas) if first else None, _ptr1(g2d),
-                 _ptr1(v_colors) + 4 * c0 if v_colors is not None else None,
-                 _ptr1(v_depths) if (depth and final) else None, w, D, P, stream())
+            _call_chunked("bwd", tile_size,
+                          (Cn, _ptr1(splat), N, _ptr1(colors) + 4 * c0, per_cam, w, int(depth and final),
+                           ptr(bg) + 4 * c0 if bg is not None else None, ptr(offsets), ptr(flatten_ids), width, height),
+                          (ptr(alphas), ptr(last_ids), ptr(v_render) + 4 * c0, ptr(v_alphas) if first else None,
+                           _ptr1(g2d), _ptr1(v_colors) + 4 * c0 if v_colors is not None else None,
+                           _ptr1(v_depths) if (depth and final) else None, w, D, P, stream()))
         if v_colors is not None and not per_cam:
             v_colors = v_colors.sum(0)
         v_bg = None
@@ -1196,14 +1146,10 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
             binfo = {"isect_ids": torch.cat([i_l[c] | (c << (32 + tile_bits)) for c in range(Cn)]),
                      "flatten_ids": torch.cat([f_l[c] + c * N for c in range(Cn)]),
                      "isect_offsets": torch.stack([(o_l[c][:-1] + bases[c]).reshape(th, tw) for c in range(Cn)])}
-    if tile_size != TILE:
+    if tile_size != TILE or (chunk is not None and colors is not None):
         render, alphas, last_ids = _TileCompositing.apply(
             means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
             bool(absgrad), _splat, depth, chunk, tile_size)
-    elif chunk is not None and colors is not None:
-        render, alphas, last_ids = _WideCompositing.apply(
-            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
-            bool(absgrad), _splat, depth, chunk)
     else:
         render, alphas, last_ids = _ModeCompositing.apply(
             means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
@@ -1290,14 +1236,10 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
         # plain RGB with 1 or 3 channels: the mode kernels' <CH, no depth, background> instantiation under a zero
         # background (T_final * 0 added to every channel), as `_mode_rasterization` runs RGB with real backgrounds
         backgrounds = torch.zeros(Cn, colors.shape[-1], device=dev)
-    if tile_size != TILE:
+    if tile_size != TILE or (chunk is not None and colors is not None):
         render, alphas, last_ids = _TileCompositing.apply(
             means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
             bool(absgrad), splat, depth, chunk, tile_size, Cn)
-    elif chunk is not None and colors is not None:
-        render, alphas, last_ids = _WideCompositing.apply(
-            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
-            bool(absgrad), splat, depth, chunk, Cn)
     else:
         render, alphas, last_ids = _ModeCompositing.apply(
             means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
@@ -1359,7 +1301,7 @@ def rasterization(
 
     D = 1 or 3 takes the paths described below.  Any other D -- ``colors`` [N, D] or [C, N, D], every render mode, with
     or without ``backgrounds`` -- goes through projection, binning and the sort once and is then composited in
-    ``ceil(D / chunk)`` launches per direction, ``chunk = min(channel_chunk, 32)`` (csrc/composite_wide.hip);
+    ``ceil(D / chunk)`` launches per direction, ``chunk = min(channel_chunk, 32)`` (csrc/tiles.hip);
     ``channel_chunk`` must be a positive int (ValueError otherwise).  ``alphas``, ``info["last_ids"]`` and the binning
     tensors do not depend on the chunking.  With one chunk ``info["means2d"].absgrad`` is gsplat's definition; with
     several it is the sum of the chunks' abs-gradients (each chunk's share of dL/dmeans2d enters with its own absolute

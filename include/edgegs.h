@@ -686,8 +686,8 @@ int eg_composite_bwd_modes_cams(int32_t C, const float *splat /*[C,N,8]*/, int32
                                 float *g2d /*[C,N,8]*/, float *v_colors /*[C,N,channels] or NULL*/,
                                 float *v_depths /*[C,N], with depth*/, eg_stream_t stream);
 
-/* ---- colours of any channel count (rasterization(colors=[..., D]) with D other than 1 or 3), csrc/composite_wide.hip:
- * the two entries above for ONE CHUNK of a wider tensor.  `channels` (1 .. 32) is the chunk width the caller declares; it
+/* ---- colours of any channel count (rasterization(colors=[..., D]) with D other than 1 or 3), csrc/tiles.hip (the
+ * kernels of eg_composite_{fwd,bwd}_ts_cams on 16-pixel tiles): the two entries above for ONE CHUNK of a wider tensor.  `channels` (1 .. 32) is the chunk width the caller declares; it
  * runs in the kernel instantiated for the next of 2, 4, 8, 16, 32, and `n_real` (1 .. channels) of its channels are real:
  * only those are loaded, stored or added to.  colors / v_colors / backgrounds point at the chunk's first channel inside
  * tensors whose rows are `color_stride` floats apart ([N, color_stride] or, with colors_per_camera != 0,

@@ -5,11 +5,11 @@ compositing entries (oracle.ref_torch.composite + autograd) and the per-row boun
 
 The chunked entries and the kernels behind them (DISPATCH below is checked against the case table by the host test):
 
-  eg_composite_{fwd,bwd}_ts_cams    csrc/tiles.hip           ts_composite_{fwd,bwd}_kernel<TS, CH, DEPTH, BG>
+  eg_composite_{fwd,bwd}_ts_cams    csrc/tiles.hip      ts_composite_{fwd,bwd}_kernel<TS, CH, DEPTH, BG>
       TS in {8, 32}; CH = 0 with (DEPTH, BG) = (1, 0) only; CH in {2, 4, 8, 16, 32} with all four (DEPTH, BG)
-  eg_composite_{fwd,bwd}_wide_cams  csrc/composite_wide.hip  composite_{fwd,bwd}_wide_kernel<CH, DEPTH, BG>
+  eg_composite_{fwd,bwd}_wide_cams  csrc/tiles.hip      ts_composite_{fwd,bwd}_kernel<16, CH, DEPTH, BG>
       CH in {2, 4, 8, 16, 32}, all four (DEPTH, BG)
-  eg_composite_{fwd,bwd}_modes_cams csrc/composite.hip       composite_fwd_kernel<CH, false, DEPTH, BG> /
+  eg_composite_{fwd,bwd}_modes_cams csrc/composite.hip  composite_fwd_kernel<CH, false, DEPTH, BG> /
       composite_bwd_colors_kernel<CH, DEPTH, BG>: CH = 0 with (1, 0); CH in {1, 3} with (1, 0), (0, 1), (1, 1)
   eg_composite_fwd / eg_composite_bwd_colors csrc/composite.hip  the same kernels with CH in {1, 3} and (0, 0)
 """
@@ -24,7 +24,7 @@ from tests.util import (FWD_ROW_TOL, REL_ALPHA, REL_T, ROW_FLOOR, ROW_KAPPA_FACT
                         ulp_perturbed)
 
 W, H = 44, 27                     # partial tiles on both axes at 8, 16 and 32 pixels
-STAGE = {8: 128, 16: 256, 32: 256}  # Gaussians per staging batch (kStage8, kTilePix, kStage32); == _lib.TS_STAGE_BATCH at 8 / 32
+STAGE = {8: 128, 16: 256, 32: 256}  # Gaussians per staging batch (kStage8, kStage32, kStage32); == _lib.TS_STAGE_BATCH at 8 / 32
 AMIN, AMAX, TSTOP = 1.0 / 255.0, 0.999, 1e-4
 N_DRAWS = 4                       # one-ulp perturbation draws behind kappa_r
 BORDER_ALPHA_SLACK = 1.0 / 255.0 + 2e-4   # what one flipped threshold contribution moves a borderline pixel's alpha by

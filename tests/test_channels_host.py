@@ -1,4 +1,4 @@
-"""The two entries of csrc/composite_wide.hip are exported with the signatures include/edgegs.h declares, and reject bad
+"""The two wide entries of csrc/tiles.hip are exported with the signatures include/edgegs.h declares, and reject bad
 arguments with a negative code before any HIP call (no device is touched: this runs without a GPU)."""
 import ctypes
 import os

@@ -1,4 +1,4 @@
-"""Colours of any channel count through `rasterization` (csrc/composite_wide.hip), against a dense PyTorch oracle built
+"""Colours of any channel count through `rasterization` (the wide entries of csrc/tiles.hip), against a dense PyTorch oracle built
 here from oracle.ref_torch's projection, binning and compositing plus gsplat 1.0.0's mode and background rules (autograd
 backward).  Scene discipline of the render-mode tests: integer-borderline Gaussians are taken out, pixels within a margin
 of a float threshold get zero upstream gradient.  200 x 136 has partial tiles on both edges and tiles deeper than one

@@ -1,6 +1,6 @@
 """Every chunked compositing kernel, per pixel and per Gaussian, at the C ABI.
 
-eg_composite_{fwd,bwd}_ts_cams (csrc/tiles.hip), eg_composite_{fwd,bwd}_wide_cams (csrc/composite_wide.hip) and
+eg_composite_{fwd,bwd}_ts_cams (csrc/tiles.hip), eg_composite_{fwd,bwd}_wide_cams (csrc/tiles.hip, 16-pixel tiles) and
 eg_composite_{fwd,bwd}_modes_cams (csrc/composite.hip) are driven through `_lib.call` on the synthetic splat records of
 tests/composite_util.py and on lists binned from those same floats by oracle.ref_torch, so that nothing but the
 compositing is compared, and compared with the float64 walk of the same inputs (oracle.ref_torch.composite in float64,
@@ -28,7 +28,7 @@ changes the entries' interface and is not done here.
 
 Dispatch (tests/composite_util.py DISPATCH; tests/test_composite_host.py shows the table below covers it): the dense
 scene runs ts_composite_{fwd,bwd}_kernel<TS, CH, DEPTH, BG> for TS in {8, 32} x (CH = 0 depth only; CH in {2, 4, 8, 16,
-32} x all four (DEPTH, BG)), composite_{fwd,bwd}_wide_kernel<CH, DEPTH, BG> for the same five widths x four pairs, and
+32} x all four (DEPTH, BG)), ts_composite_{fwd,bwd}_kernel<16, CH, DEPTH, BG> for the same five widths x four pairs, and
 the mode instantiations CH = 0 / depth, CH in {1, 3} x {(1, 0), (0, 1), (1, 1)}.  The sparse scene (untouched pixels, an
 empty tile, lists under one batch) and the two-camera set (list base, per-camera offsets and colours) run a
 cross-section; the riders vary the addressing only.

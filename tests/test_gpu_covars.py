@@ -414,7 +414,7 @@ def test_rider_depth_mode_with_backgrounds(env):
 
 
 def test_rider_five_channels(env):
-    """D = 5 (csrc/composite_wide.hip behind the projection from covariances) against the oracle composite."""
+    """D = 5 (the wide entries of csrc/tiles.hip behind the projection from covariances) against the oracle composite."""
     ws, _colors, _wr, _wa = CU.whole_inputs()
     keep = CU.whole_keep(16, True)
     g = torch.Generator().manual_seed(47)

@@ -417,7 +417,7 @@ def test_rider_depth_mode_with_backgrounds(env):
 
 
 def test_rider_five_channels(env):
-    """D = 5 under ortho (csrc/composite_wide.hip behind the orthographic projection) against the oracle composite."""
+    """D = 5 under ortho (the wide entries of csrc/tiles.hip behind the orthographic projection) against the oracle composite."""
     ws, _colors, _wr, wa = _whole_inputs()
     keep = OU.whole_keep(16, True)
     g = torch.Generator().manual_seed(47)
