@@ -18,6 +18,12 @@
 // ties broken by Gaussian id, which is exactly what a stable sort of index-ordered emissions gives.
 // Segments larger than the LDS capacity fall back to a hybrid global/LDS bitonic sort by the
 // same workgroup (slow path, correct for any size).
+//
+// The general path (rasterization / functional) counts and emits here for tiles of 8, 16 and 32 pixels: ONE counting
+// kernel and ONE emission kernel from (means2d, radii, depths) with the tile size as an argument, their launchers, and
+// ONE per-camera binning step (bin_camera: emission, eg_sort_pairs, the rebase kernel) that eg_tile_emit_sort_cams
+// (cams.hip), eg_packed_bin (packed.hip) and eg_tile_emit_sort_ts (tiles.hip) loop over.  tile_emit_kernel is the
+// emission from the splat records of the training step's classic layout.
 #include <cstdlib>
 
 #include "common.h"
@@ -29,32 +35,41 @@ namespace eg {
 // cache lines (the object covers ~13x13 central tiles), so per-intersection global atomics serialise
 // on those lines (measured: 250 us for 480k atomics).  Each 512-thread workgroup histograms its
 // Gaussians into LDS first and flushes one global atomic per touched tile.
+//
+// tile_count_kernel and tile_emit_means2d_kernel are THE counting and emission of the general path (rasterization /
+// functional) for tiles of 8, 16 and 32 pixels: the tile size is an argument (tile_box_ts divides by it in fp32, in
+// the oracle's order).  launch_tile_count / launch_tile_emit hold the choice between the LDS histogram and direct
+// atomics; every entry that counts or emits from (means2d, radii, depths) goes through them.
 constexpr int kBinThreads = 512;
-constexpr int kMaxLdsTiles = 16384;  // 64 KiB of counters; larger grids use the direct-atomic path
+// 64 KiB of LDS counters: the counting keeps one word per tile (grids of up to 16 384 tiles), the emission two (up to
+// 8 192); larger grids use the direct-atomic path -- at 8-pixel tiles a 1024 x 1032 image has 16 512 tiles
+constexpr int kMaxLdsWords = 16384;
 
+// one camera's n Gaussians on a grid of tw x th tiles of ts pixels: tiles_per_gauss [n] (NULL ok), tile_counts [T]
+// accumulated
 template <bool LDS>
 __global__ void __launch_bounds__(kBinThreads)
-tile_count_kernel(const float2 *__restrict__ means2d, const int *__restrict__ radii, int N, int width,
-                  int height, int *__restrict__ tiles_per_gauss, int *__restrict__ tile_counts) {
+tile_count_kernel(const float2 *__restrict__ means2d, const int *__restrict__ radii, int n, float ts, int tw, int th,
+                  int *__restrict__ tiles_per_gauss, int *__restrict__ tile_counts) {
   extern __shared__ __attribute__((aligned(16))) int s_hist[];
-  const int tw = (width + kTile - 1) / kTile, th = (height + kTile - 1) / kTile, T = tw * th;
+  const int T = tw * th;
   if (LDS) {
     for (int t = threadIdx.x; t < T; t += kBinThreads) s_hist[t] = 0;
     __syncthreads();
   }
   const int g = blockIdx.x * kBinThreads + threadIdx.x;
-  if (g < N) {
+  if (g < n) {
     const int radius = radii[g];
-    int n = 0;
+    int cnt = 0;
     if (radius > 0) {
       const float2 m = means2d[g];
       int x0, y0, x1, y1;
-      tile_box(m.x, m.y, radius, tw, th, x0, y0, x1, y1);
-      n = (y1 - y0) * (x1 - x0);
+      tile_box_ts(m.x, m.y, radius, ts, tw, th, x0, y0, x1, y1);
+      cnt = (y1 - y0) * (x1 - x0);
       for (int ty = y0; ty < y1; ++ty)
         for (int tx = x0; tx < x1; ++tx) atomicAdd(LDS ? &s_hist[ty * tw + tx] : &tile_counts[ty * tw + tx], 1);
     }
-    if (tiles_per_gauss) tiles_per_gauss[g] = n;
+    if (tiles_per_gauss) tiles_per_gauss[g] = cnt;
   }
   if (LDS) {
     __syncthreads();
@@ -143,12 +158,69 @@ tile_offsets_kernel(const int *__restrict__ counts, int T, long long capacity, i
 
 // emit: block-local histogram in LDS -> ONE returning global atomic per (block, touched tile) reserves
 // a run of slots in the tile's segment -> block-local LDS cursors hand out the slots.
+//
+// The means2d form (the general path, tiles of 8, 16 and 32 pixels): one camera's n Gaussians, key = depth bits << 32 |
+// index inside the camera's range; the cursors -- the tile counts -- are counted back down to zero.
 template <bool LDS>
 __global__ void __launch_bounds__(kBinThreads)
-tile_emit_kernel(const float2 *__restrict__ means2d, const int *__restrict__ radii,
-                 const float *__restrict__ depths, const float4 *__restrict__ splat, unsigned flags, int N,
-                 int width, int height, const int *__restrict__ offsets, int *__restrict__ cursor,
-                 long long capacity, unsigned long long *__restrict__ keys, const unsigned *__restrict__ tile_mask) {
+tile_emit_means2d_kernel(const float2 *__restrict__ means2d, const int *__restrict__ radii,
+                         const float *__restrict__ depths, int n, float ts, int tw, int th,
+                         const int *__restrict__ offsets, int *__restrict__ cursor, long long capacity,
+                         unsigned long long *__restrict__ keys) {
+  extern __shared__ __attribute__((aligned(16))) int s_mem[];
+  const int T = tw * th;
+  int *s_hist = s_mem, *s_base = s_mem + T;
+  if (LDS) {
+    for (int t = threadIdx.x; t < T; t += kBinThreads) s_hist[t] = 0;
+    __syncthreads();
+  }
+  const int g = blockIdx.x * kBinThreads + threadIdx.x;
+  int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+  float depth = 0.f;
+  if (g < n) {
+    const int radius = radii[g];
+    if (radius > 0) {
+      const float2 m = means2d[g];
+      depth = depths[g];
+      tile_box_ts(m.x, m.y, radius, ts, tw, th, x0, y0, x1, y1);
+    }
+  }
+  const unsigned long long key = ((unsigned long long)(unsigned)__float_as_int(depth) << 32) | (unsigned)g;
+  if (!LDS) {
+    for (int ty = y0; ty < y1; ++ty)
+      for (int tx = x0; tx < x1; ++tx) {
+        const int t = ty * tw + tx;
+        const long long idx = (long long)offsets[t] + (atomicSub(&cursor[t], 1) - 1);
+        if (idx >= 0 && idx < capacity) keys[idx] = key;
+      }
+    return;
+  }
+  for (int ty = y0; ty < y1; ++ty)
+    for (int tx = x0; tx < x1; ++tx) atomicAdd(&s_hist[ty * tw + tx], 1);
+  __syncthreads();
+  for (int t = threadIdx.x; t < T; t += kBinThreads) {
+    const int c = s_hist[t];
+    if (c) {
+      s_base[t] = offsets[t] + (atomicSub(&cursor[t], c) - c);  // slots [base, base + c)
+      s_hist[t] = 0;
+    }
+  }
+  __syncthreads();
+  for (int ty = y0; ty < y1; ++ty)
+    for (int tx = x0; tx < x1; ++tx) {
+      const int t = ty * tw + tx;
+      const long long idx = (long long)s_base[t] + atomicAdd(&s_hist[t], 1);
+      if (idx >= 0 && idx < capacity) keys[idx] = key;
+    }
+}
+
+// The splat-record form (16-pixel tiles; the training step's classic layout): the same slot claiming on the records
+// of the projection, with the tight tile boxes and the exact tile hits of EG_FLAG_TIGHT_TILES.
+template <bool LDS>
+__global__ void __launch_bounds__(kBinThreads)
+tile_emit_kernel(const float4 *__restrict__ splat, unsigned flags, int N, int width, int height,
+                 const int *__restrict__ offsets, int *__restrict__ cursor, long long capacity,
+                 unsigned long long *__restrict__ keys, const unsigned *__restrict__ tile_mask) {
   extern __shared__ __attribute__((aligned(16))) int s_mem[];
   const int tw = (width + kTile - 1) / kTile, th = (height + kTile - 1) / kTile, T = tw * th;
   int *s_hist = s_mem, *s_base = s_mem + T;
@@ -160,24 +232,20 @@ tile_emit_kernel(const float2 *__restrict__ means2d, const int *__restrict__ rad
   float x = 0.f, y = 0.f, depth = 0.f;
   float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
   int radius = 0;
+  const bool exact = flags & EG_FLAG_TIGHT_TILES;  // must mirror the counting pass exactly
+  // the counting pass left the exact hits of small boxes as a bit mask (all ones = "re-test")
+  unsigned mask = 0xffffffffu;
   if (g < N) {
-    if (splat) {
-      s0 = splat[2 * g]; s1 = splat[2 * g + 1];
-      x = s0.x; y = s0.y; depth = s1.z; radius = __float_as_int(s1.w);
-    } else {
-      const float2 m = means2d[g];
-      x = m.x; y = m.y; depth = depths[g]; radius = radii[g];
-    }
+    s0 = splat[2 * g]; s1 = splat[2 * g + 1];
+    x = s0.x; y = s0.y; depth = s1.z; radius = __float_as_int(s1.w);
+    if (exact && tile_mask) mask = tile_mask[g];
   }
   int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
   if (radius > 0) {
-    if (splat && (flags & EG_FLAG_TIGHT_TILES)) tile_box_tight(x, y, radius, s0.z, s0.w, s1.x, s1.y, tw, th, x0, y0, x1, y1);
+    if (exact) tile_box_tight(x, y, radius, s0.z, s0.w, s1.x, s1.y, tw, th, x0, y0, x1, y1);
     else tile_box(x, y, radius, tw, th, x0, y0, x1, y1);
   }
   const unsigned long long key = ((unsigned long long)(unsigned)__float_as_int(depth) << 32) | (unsigned)g;
-  const bool exact = splat && (flags & EG_FLAG_TIGHT_TILES);  // must mirror the counting pass exactly
-  // the counting pass left the exact hits of small boxes as a bit mask (all ones = "re-test")
-  const unsigned mask = (exact && tile_mask && g < N) ? tile_mask[g] : 0xffffffffu;
   const bool use_mask = exact && mask != 0xffffffffu;
   const int bw = x1 - x0;
 #define EG_TILE_OK(tx, ty)                                                           \
@@ -997,6 +1065,64 @@ tile_sort_kernel(unsigned long long *__restrict__ keys, const int *__restrict__ 
   }  // tile loop
 }
 
+// sorted ids of one camera's range -> indices into the whole list (id_base != 0); the camera into the isect ids
+__global__ void __launch_bounds__(256)
+tile_rebase_kernel(int *__restrict__ flatten_ids, long long *__restrict__ isect_ids, long long M, int id_base,
+                   long long camera_bits) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= M) return;
+  if (id_base) flatten_ids[i] += id_base;
+  if (isect_ids) isect_ids[i] |= camera_bits;
+}
+
+void launch_tile_count(const float *means2d, const int32_t *radii, int n, int tile_size, int tw, int th,
+                       int32_t *tiles_per_gauss, int32_t *tile_counts, hipStream_t st) {
+  const int T = tw * th;
+  if (T <= kMaxLdsWords)
+    tile_count_kernel<true><<<cdiv(n, kBinThreads), kBinThreads, sizeof(int) * T, st>>>(
+        (const float2 *)means2d, radii, n, (float)tile_size, tw, th, tiles_per_gauss, tile_counts);
+  else
+    tile_count_kernel<false><<<cdiv(n, kBinThreads), kBinThreads, 0, st>>>(
+        (const float2 *)means2d, radii, n, (float)tile_size, tw, th, tiles_per_gauss, tile_counts);
+}
+
+void launch_tile_emit(const float *means2d, const int32_t *radii, const float *depths, int n, int tile_size, int tw,
+                      int th, const int32_t *offsets, int32_t *tile_counts, int64_t capacity, uint64_t *keys,
+                      hipStream_t st) {
+  const int T = tw * th;
+  if (2 * T <= kMaxLdsWords)
+    tile_emit_means2d_kernel<true><<<cdiv(n, kBinThreads), kBinThreads, sizeof(int) * 2 * T, st>>>(
+        (const float2 *)means2d, radii, depths, n, (float)tile_size, tw, th, offsets, tile_counts, (long long)capacity,
+        (unsigned long long *)keys);
+  else
+    tile_emit_means2d_kernel<false><<<cdiv(n, kBinThreads), kBinThreads, 0, st>>>(
+        (const float2 *)means2d, radii, depths, n, (float)tile_size, tw, th, offsets, tile_counts, (long long)capacity,
+        (unsigned long long *)keys);
+}
+
+int tile_bits(int T) {
+  int bits = 0;
+  while ((1 << bits) <= T) ++bits;  // floor(log2(T)) + 1
+  return bits;
+}
+
+int bin_camera(const char *what, const float *means2d, const int32_t *radii, const float *depths, int n, int tile_size,
+               int tw, int th, const int32_t *offsets, int32_t *tile_counts, int64_t M, uint64_t *keys,
+               int32_t *flatten_ids, int64_t *isect_ids, int32_t max_tile_hint, int id_base, int64_t camera_bits,
+               eg_stream_t stream) {
+  launch_tile_emit(means2d, radii, depths, n, tile_size, tw, th, offsets, tile_counts, M, keys, as_stream(stream));
+  int rc = check_launch(what);
+  if (rc) return rc;
+  rc = eg_sort_pairs(keys, offsets, tw * th, M, flatten_ids, isect_ids, max_tile_hint, stream);
+  if (rc) return rc;
+  if (M > 0 && (id_base != 0 || (isect_ids && camera_bits != 0))) {
+    tile_rebase_kernel<<<cdiv(M, 256), 256, 0, as_stream(stream)>>>(flatten_ids, (long long *)isect_ids, (long long)M,
+                                                                     id_base, (long long)camera_bits);
+    rc = check_launch(what);
+  }
+  return rc;
+}
+
 }  // namespace eg
 
 using namespace eg;
@@ -1006,13 +1132,8 @@ extern "C" int eg_tile_count(const float *means2d, const int32_t *radii, int32_t
   EG_REQUIRE(N >= 0 && width > 0 && height > 0, "bad sizes");
   if (N == 0) return EG_OK;
   EG_REQUIRE(means2d && radii && tile_counts, "null pointer");
-  const int T = cdiv(width, kTile) * cdiv(height, kTile);
-  if (T <= kMaxLdsTiles)
-    tile_count_kernel<true><<<cdiv(N, kBinThreads), kBinThreads, sizeof(int) * T, as_stream(stream)>>>(
-        (const float2 *)means2d, radii, N, width, height, tiles_per_gauss, tile_counts);
-  else
-    tile_count_kernel<false><<<cdiv(N, kBinThreads), kBinThreads, 0, as_stream(stream)>>>(
-        (const float2 *)means2d, radii, N, width, height, tiles_per_gauss, tile_counts);
+  launch_tile_count(means2d, radii, N, kTile, cdiv(width, kTile), cdiv(height, kTile), tiles_per_gauss, tile_counts,
+                    as_stream(stream));
   return check_launch("tile_count");
 }
 
@@ -1032,14 +1153,17 @@ extern "C" int eg_tile_emit(const float *means2d, const int32_t *radii, const fl
   EG_REQUIRE(offsets && tile_cursor && (keys || capacity == 0), "null pointer");
   EG_REQUIRE(splat || (means2d && radii && depths), "need splat or (means2d, radii, depths)");
   const int T = cdiv(width, kTile) * cdiv(height, kTile);
-  if (2 * T <= kMaxLdsTiles)
+  if (!splat)  // (the general path: flags and tile_mask belong to the records)
+    launch_tile_emit(means2d, radii, depths, N, kTile, cdiv(width, kTile), cdiv(height, kTile), offsets, tile_cursor,
+                     capacity, keys, as_stream(stream));
+  else if (2 * T <= kMaxLdsWords)
     tile_emit_kernel<true><<<cdiv(N, kBinThreads), kBinThreads, sizeof(int) * 2 * T, as_stream(stream)>>>(
-        (const float2 *)means2d, radii, depths, (const float4 *)splat, flags, N, width, height, offsets,
-        tile_cursor, (long long)capacity, (unsigned long long *)keys, tile_mask);
+        (const float4 *)splat, flags, N, width, height, offsets, tile_cursor, (long long)capacity,
+        (unsigned long long *)keys, tile_mask);
   else
     tile_emit_kernel<false><<<cdiv(N, kBinThreads), kBinThreads, 0, as_stream(stream)>>>(
-        (const float2 *)means2d, radii, depths, (const float4 *)splat, flags, N, width, height, offsets,
-        tile_cursor, (long long)capacity, (unsigned long long *)keys, tile_mask);
+        (const float4 *)splat, flags, N, width, height, offsets, tile_cursor, (long long)capacity,
+        (unsigned long long *)keys, tile_mask);
   return check_launch("tile_emit");
 }
 

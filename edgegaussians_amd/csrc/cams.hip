@@ -68,8 +68,9 @@ extern "C" int eg_tile_offsets_cams(const int32_t *tile_counts, int32_t T, int32
   return EG_OK;
 }
 
-// key emission + per-tile sort of every camera; keys / flatten_ids / isect_ids: HOST arrays of C device pointers (camera c's
-// arrays hold M_host[c] entries; isect_ids or its entries may be NULL), tile_counts [C, T] is returned to zero
+// key emission + per-tile sort of every camera (the general path's per-camera step: bin_camera, binning.hip); keys /
+// flatten_ids / isect_ids: HOST arrays of C device pointers (camera c's arrays hold M_host[c] entries; isect_ids or its
+// entries may be NULL), tile_counts [C, T] is returned to zero
 extern "C" int eg_tile_emit_sort_cams(const float *means2d, const int32_t *radii, const float *depths, int32_t N, int32_t C,
                                       int32_t width, int32_t height, const int32_t *offsets, int32_t *tile_counts,
                                       const int64_t *M_host, uint64_t *const *keys, int32_t *const *flatten_ids,
@@ -78,14 +79,14 @@ extern "C" int eg_tile_emit_sort_cams(const float *means2d, const int32_t *radii
   if (N == 0) return EG_OK;
   EG_REQUIRE(means2d && radii && depths && offsets && tile_counts && M_host && keys && flatten_ids, "null pointer");
   const size_t n = (size_t)N;
-  const int T = cdiv(width, kTile) * cdiv(height, kTile);
+  const int tw = cdiv(width, kTile), th = cdiv(height, kTile), T = tw * th;
   for (int c = 0; c < C; ++c) {
     EG_REQUIRE(M_host[c] >= 0 && (M_host[c] == 0 || (keys[c] && flatten_ids[c])), "null isect array");
-    int rc = eg_tile_emit(means2d + 2 * n * c, radii + n * c, depths + n * c, nullptr, 0, N, width, height,
-                          offsets + (size_t)(T + 1) * c, tile_counts + (size_t)T * c, M_host[c], keys[c], nullptr, stream);
-    if (rc) return rc;
-    rc = eg_sort_pairs(keys[c], offsets + (size_t)(T + 1) * c, T, M_host[c], flatten_ids[c],
-                       isect_ids ? isect_ids[c] : nullptr, max_tile_host ? max_tile_host[c] : 0, stream);
+    // (no id base, no camera bits: the ids stay local to the camera, as the compositing of its list takes them)
+    const int rc = bin_camera("tile_emit_sort_cams", means2d + 2 * n * c, radii + n * c, depths + n * c, N, kTile, tw, th,
+                              offsets + (size_t)(T + 1) * c, tile_counts + (size_t)T * c, M_host[c], keys[c],
+                              flatten_ids[c], isect_ids ? isect_ids[c] : nullptr, max_tile_host ? max_tile_host[c] : 0,
+                              0, 0, stream);
     if (rc) return rc;
   }
   return EG_OK;

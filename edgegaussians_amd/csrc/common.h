@@ -118,6 +118,23 @@ int launch_project_bwd_batched(float *means, float *quats, float *scales, float 
                                float *m, float *v, const eg_adam_hyper *hyper_host, const Batch &bt, int C,
                                hipStream_t st);
 
+// Binning of the general path (binning.hip): THE counting and means2d-form emission kernels, for tiles of 8, 16 and 32
+// pixels on a grid of tw x th tiles.  One camera's n Gaussians per launch; the launchers choose between the LDS
+// histogram and direct atomics and check nothing.
+void launch_tile_count(const float *means2d, const int32_t *radii, int n, int tile_size, int tw, int th,
+                       int32_t *tiles_per_gauss, int32_t *tile_counts, hipStream_t st);
+void launch_tile_emit(const float *means2d, const int32_t *radii, const float *depths, int n, int tile_size, int tw,
+                      int th, const int32_t *offsets, int32_t *tile_counts, int64_t capacity, uint64_t *keys,
+                      hipStream_t st);
+int tile_bits(int T);  // bits of a tile index inside the isect ids: floor(log2(T)) + 1
+// One camera's binning step behind the scan, on the camera's base pointers: emission, eg_sort_pairs, and -- with an
+// id_base or camera_bits (the camera shifted above the tile bits; isect_ids NULL ok) -- the rebase of the sorted ids.
+// tile_counts [T] is returned to zero.  `what` names the calling entry in a launch error.
+int bin_camera(const char *what, const float *means2d, const int32_t *radii, const float *depths, int n, int tile_size,
+               int tw, int th, const int32_t *offsets, int32_t *tile_counts, int64_t M, uint64_t *keys,
+               int32_t *flatten_ids, int64_t *isect_ids, int32_t max_tile_hint, int id_base, int64_t camera_bits,
+               eg_stream_t stream);
+
 inline hipStream_t as_stream(eg_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 #if defined(__HIPCC__)
 // Inclusive scan over the 64 lanes of a wavefront with DPP (row shifts inside the rows of 16, then the two row

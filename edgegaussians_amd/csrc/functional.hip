@@ -383,10 +383,8 @@ extern "C" int eg_isect_offset_encode(const int64_t *isect_ids, int64_t M, int32
   EG_REQUIRE(T64 < (1ll << 30) && T64 * C < (1ll << 31), "bad sizes");
   EG_REQUIRE(offsets && (M == 0 || isect_ids), "null pointer");
   const int T = (int)T64;
-  int tile_bits = 0;
-  while ((1 << tile_bits) <= T) ++tile_bits;  // floor(log2(T)) + 1
   const long long CT = (long long)T * C;
   isect_offset_encode_kernel<<<cdiv(M > 0 ? M : CT, kFn), kFn, 0, as_stream(stream)>>>(
-      (const long long *)isect_ids, (long long)M, tile_bits, T, CT, offsets);
+      (const long long *)isect_ids, (long long)M, tile_bits(T), T, CT, offsets);
   return check_launch("isect_offset_encode");
 }

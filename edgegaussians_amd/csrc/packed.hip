@@ -12,8 +12,9 @@
 //           with ballot / popcount and a 4-wave prefix, and writes the record of the compositing kernels, the per-pair
 //           outputs, the ids, tiles_per_gauss and the per-camera tile counters (LDS histogram, one global atomic per
 //           workgroup and touched tile, like project_fwd_kernel).
-//   bin     camera c's range is a single-camera problem: eg_tile_emit / eg_sort_pairs through base pointers, then
-//           the sorted ids are rebased to the whole packed list and the camera goes into the isect ids.
+//   bin     camera c's range is a single-camera problem: the general path's per-camera binning step (bin_camera,
+//           binning.hip: emission, eg_sort_pairs, rebase) through base pointers, with indptr[c] as the id base -- the
+//           sorted ids index the whole packed list -- and the camera in the isect ids.
 //   bwd     dense gradients: one thread per Gaussian walks the cameras 0 .. C-1 (eg_project_bwd_cams's order), finds
 //           its pair by binary search in the camera's ascending ids, sums in registers, writes every row once (zeros
 //           where nobody sees it).  No atomics, no zero-fill: bit-identical from run to run.
@@ -152,16 +153,6 @@ packed_write_kernel(Form form, const PackedView v, const int *__restrict__ block
       if (c) atomicAdd(&tile_counts[t], c);
     }
   }
-}
-
-// sorted ids of one camera's range -> indices into the whole packed list; the camera into the isect ids
-__global__ void __launch_bounds__(256)
-packed_rebase_kernel(int *__restrict__ flatten_ids, long long *__restrict__ isect_ids, long long M, int id_base,
-                     long long camera_bits) {
-  const long long i = blockIdx.x * 256ll + threadIdx.x;
-  if (i >= M) return;
-  flatten_ids[i] += id_base;
-  if (isect_ids) isect_ids[i] |= camera_bits;
 }
 
 // the cotangents of the pairs: the [nnz, 8] record of the compositing backwards, v_comps [nnz], v_depths [nnz] (NULL ok)
@@ -318,9 +309,8 @@ extern "C" int eg_packed_bin(const float *means2d, const int32_t *radii, const f
                              eg_stream_t stream) {
   EG_REQUIRE(C >= 1 && width > 0 && height > 0, "bad sizes");
   EG_REQUIRE(indptr_host && offsets && tile_counts && M_host, "null pointer");
-  const int T = cdiv(width, kTile) * cdiv(height, kTile);
-  int tile_bits = 0;
-  while ((1 << tile_bits) <= T) ++tile_bits;  // floor(log2(T)) + 1
+  const int tw = cdiv(width, kTile), th = cdiv(height, kTile), T = tw * th;
+  const int bits = tile_bits(T);
   EG_REQUIRE(indptr_host[0] == 0, "indptr must start at 0");
   for (int c = 0; c < C; ++c) {  // (everything is checked before the first launch)
     const int64_t n = indptr_host[c + 1] - indptr_host[c], M = M_host[c];
@@ -331,19 +321,11 @@ extern "C" int eg_packed_bin(const float *means2d, const int32_t *radii, const f
   for (int c = 0; c < C; ++c) {
     const int64_t b = indptr_host[c], n = indptr_host[c + 1] - b, M = M_host[c];
     if (M > 0) {
-      const int32_t *offs = offsets + (size_t)(T + 1) * c;
-      int rc = eg_tile_emit(means2d + 2 * b, radii + b, depths + b, nullptr, 0, (int32_t)n, width, height, offs,
-                            tile_counts + (size_t)T * c, M, keys + m_base, nullptr, stream);
+      const int rc = bin_camera("packed_bin", means2d + 2 * b, radii + b, depths + b, (int)n, kTile, tw, th,
+                                offsets + (size_t)(T + 1) * c, tile_counts + (size_t)T * c, M, keys + m_base,
+                                flatten_ids + m_base, isect_ids ? isect_ids + m_base : nullptr,
+                                max_tile_host ? max_tile_host[c] : 0, (int)b, (int64_t)c << (32 + bits), stream);
       if (rc) return rc;
-      int64_t *ids = isect_ids ? isect_ids + m_base : nullptr;
-      rc = eg_sort_pairs(keys + m_base, offs, T, M, flatten_ids + m_base, ids, max_tile_host ? max_tile_host[c] : 0, stream);
-      if (rc) return rc;
-      if (b > 0 || (ids && c > 0)) {
-        packed_rebase_kernel<<<cdiv(M, 256), 256, 0, as_stream(stream)>>>(
-            flatten_ids + m_base, (long long *)ids, (long long)M, (int)b, (long long)c << (32 + tile_bits));
-        rc = check_launch("packed_bin");
-        if (rc) return rc;
-      }
     }
     m_base += M;
   }

@@ -1,15 +1,13 @@
-// Binning with a run-time tile size (rasterization(tile_size=8 | 32)) and the chunked compositing kernels, templated on
-// the tile size, for tiles of 8, 16 and 32 pixels.  At tile_size = 16 the binning is binning.hip's and D = 1, 3 and the
-// depth-only modes are composited by composite.hip; colours of any other channel count come here
-// (eg_composite_{fwd,bwd}_wide_cams).
+// The entries of rasterization(tile_size=8 | 32) and the chunked compositing kernels, templated on the tile size, for
+// tiles of 8, 16 and 32 pixels.  At tile_size = 16 D = 1, 3 and the depth-only modes are composited by composite.hip;
+// colours of any other channel count come here (eg_composite_{fwd,bwd}_wide_cams).
 //
-// Binning.  tile_count_kernel / tile_emit_kernel of binning.hip with the tile size as an argument: the same tile box
-// ((x / ts) -+ (r / ts) in fp32, floor / ceil, clamp), the same LDS-privatised histogram (grids of up to 16 384 tiles for
-// the counting, 8 192 for the emission, which keeps two words per tile) and the same direct-atomic fallback beyond -- at
-// ts = 8 a 1024 x 1032 image has 16 512 tiles.  The scan (eg_tile_offsets_cams) and the per-tile sort (eg_sort_pairs)
-// know the tile size only through T and are used as they are.  The cameras' Gaussians are addressed through a host
-// array of C + 1 range bounds, which serves both layouts of the projection: [c N, (c + 1) N) for the dense [C, N, ...]
-// arrays, indptr for the packed lists.
+// Binning.  eg_tile_count_ts / eg_tile_emit_sort_ts run the general path's one counting kernel, one emission kernel and
+// one per-camera step (binning.hip: launch_tile_count, bin_camera) with the tile size as an argument; the scan
+// (eg_tile_offsets_cams) and the per-tile sort know the tile size only through T.  The cameras' Gaussians are addressed
+// through a host array of C + 1 range bounds, which serves both layouts of the projection: [c N, (c + 1) N) for the
+// dense [C, N, ...] arrays, indptr for the packed lists.  The entries here refuse 16: that size has eg_tile_count,
+// eg_tile_emit_sort_cams and eg_packed_bin.
 //
 // Compositing: one kernel family <TS, CH, DEPTH, BG>.  A call composites ONE chunk of `n_real` channels that lives
 // inside full-width tensors: colors / v_colors / backgrounds are addressed with the row stride `cs`, render / v_render
@@ -51,108 +49,7 @@
 
 namespace eg {
 
-constexpr int kTsBinThreads = 512;
-constexpr int kTsMaxLdsWords = 16384;  // 64 KiB of LDS counters; larger grids use the direct-atomic path
-
 inline bool tile_size_ok(int ts) { return ts == 8 || ts == 32; }  // (16: binning.hip and the wide entries)
-
-// one camera's n Gaussians: tiles_per_gauss [n] (NULL ok), tile_counts [T] accumulated
-template <bool LDS>
-__global__ void __launch_bounds__(kTsBinThreads)
-ts_count_kernel(const float2 *__restrict__ means2d, const int *__restrict__ radii, int n, float ts, int tw, int th,
-                int *__restrict__ tiles_per_gauss, int *__restrict__ tile_counts) {
-  extern __shared__ __attribute__((aligned(16))) int s_hist[];
-  const int T = tw * th;
-  if (LDS) {
-    for (int t = threadIdx.x; t < T; t += kTsBinThreads) s_hist[t] = 0;
-    __syncthreads();
-  }
-  const int g = blockIdx.x * kTsBinThreads + threadIdx.x;
-  if (g < n) {
-    const int radius = radii[g];
-    int cnt = 0;
-    if (radius > 0) {
-      const float2 m = means2d[g];
-      int x0, y0, x1, y1;
-      tile_box_ts(m.x, m.y, radius, ts, tw, th, x0, y0, x1, y1);
-      cnt = (y1 - y0) * (x1 - x0);
-      for (int ty = y0; ty < y1; ++ty)
-        for (int tx = x0; tx < x1; ++tx) atomicAdd(LDS ? &s_hist[ty * tw + tx] : &tile_counts[ty * tw + tx], 1);
-    }
-    if (tiles_per_gauss) tiles_per_gauss[g] = cnt;
-  }
-  if (LDS) {
-    __syncthreads();
-    for (int t = threadIdx.x; t < T; t += kTsBinThreads) {
-      const int c = s_hist[t];
-      if (c) atomicAdd(&tile_counts[t], c);
-    }
-  }
-}
-
-// one camera's n Gaussians: key = depth bits << 32 | index inside the camera's range; the slots are claimed as in
-// tile_emit_kernel (the cursors -- the tile counts -- are counted back down to zero)
-template <bool LDS>
-__global__ void __launch_bounds__(kTsBinThreads)
-ts_emit_kernel(const float2 *__restrict__ means2d, const int *__restrict__ radii, const float *__restrict__ depths,
-               int n, float ts, int tw, int th, const int *__restrict__ offsets, int *__restrict__ cursor,
-               long long capacity, unsigned long long *__restrict__ keys) {
-  extern __shared__ __attribute__((aligned(16))) int s_mem[];
-  const int T = tw * th;
-  int *s_hist = s_mem, *s_base = s_mem + T;
-  if (LDS) {
-    for (int t = threadIdx.x; t < T; t += kTsBinThreads) s_hist[t] = 0;
-    __syncthreads();
-  }
-  const int g = blockIdx.x * kTsBinThreads + threadIdx.x;
-  int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
-  float depth = 0.f;
-  if (g < n) {
-    const int radius = radii[g];
-    if (radius > 0) {
-      const float2 m = means2d[g];
-      depth = depths[g];
-      tile_box_ts(m.x, m.y, radius, ts, tw, th, x0, y0, x1, y1);
-    }
-  }
-  const unsigned long long key = ((unsigned long long)(unsigned)__float_as_int(depth) << 32) | (unsigned)g;
-  if (!LDS) {
-    for (int ty = y0; ty < y1; ++ty)
-      for (int tx = x0; tx < x1; ++tx) {
-        const int t = ty * tw + tx;
-        const long long idx = (long long)offsets[t] + (atomicSub(&cursor[t], 1) - 1);
-        if (idx >= 0 && idx < capacity) keys[idx] = key;
-      }
-    return;
-  }
-  for (int ty = y0; ty < y1; ++ty)
-    for (int tx = x0; tx < x1; ++tx) atomicAdd(&s_hist[ty * tw + tx], 1);
-  __syncthreads();
-  for (int t = threadIdx.x; t < T; t += kTsBinThreads) {
-    const int c = s_hist[t];
-    if (c) {
-      s_base[t] = offsets[t] + (atomicSub(&cursor[t], c) - c);  // slots [base, base + c)
-      s_hist[t] = 0;
-    }
-  }
-  __syncthreads();
-  for (int ty = y0; ty < y1; ++ty)
-    for (int tx = x0; tx < x1; ++tx) {
-      const int t = ty * tw + tx;
-      const long long idx = (long long)s_base[t] + atomicAdd(&s_hist[t], 1);
-      if (idx >= 0 && idx < capacity) keys[idx] = key;
-    }
-}
-
-// sorted ids of one camera's range -> indices into the whole list (id_base != 0); the camera into the isect ids
-__global__ void __launch_bounds__(256)
-ts_rebase_kernel(int *__restrict__ flatten_ids, long long *__restrict__ isect_ids, long long M, int id_base,
-                 long long camera_bits) {
-  const long long i = blockIdx.x * 256ll + threadIdx.x;
-  if (i >= M) return;
-  if (id_base) flatten_ids[i] += id_base;
-  if (isect_ids) isect_ids[i] |= camera_bits;
-}
 
 // ---------------------------------------------------------------------------------------------
 // compositing
@@ -421,13 +318,8 @@ extern "C" int eg_tile_count_ts(const float *means2d, const int32_t *radii, cons
     const int64_t b = ranges_host[c];
     const int n = (int)(ranges_host[c + 1] - b);
     if (n == 0) continue;
-    int32_t *tpg = tiles_per_gauss ? tiles_per_gauss + b : nullptr;
-    if (T <= kTsMaxLdsWords)
-      ts_count_kernel<true><<<cdiv(n, kTsBinThreads), kTsBinThreads, sizeof(int) * T, as_stream(stream)>>>(
-          (const float2 *)means2d + b, radii + b, n, (float)tile_size, tw, th, tpg, tile_counts + T * c);
-    else
-      ts_count_kernel<false><<<cdiv(n, kTsBinThreads), kTsBinThreads, 0, as_stream(stream)>>>(
-          (const float2 *)means2d + b, radii + b, n, (float)tile_size, tw, th, tpg, tile_counts + T * c);
+    launch_tile_count(means2d + 2 * b, radii + b, n, tile_size, tw, th, tiles_per_gauss ? tiles_per_gauss + b : nullptr,
+                      tile_counts + T * c, as_stream(stream));
   }
   return check_launch("tile_count_ts");
 }
@@ -443,8 +335,7 @@ extern "C" int eg_tile_emit_sort_ts(const float *means2d, const int32_t *radii, 
   const int64_t T64 = (int64_t)tw * th;
   EG_REQUIRE(T64 < (1ll << 30), "bad sizes");
   const int T = (int)T64;
-  int tile_bits = 0;
-  while ((1 << tile_bits) <= T) ++tile_bits;  // floor(log2(T)) + 1
+  const int bits = tile_bits(T);
   for (int c = 0; c < C; ++c) {  // (everything is checked before the first launch)
     const int64_t n = ranges_host[c + 1] - ranges_host[c], M = M_host[c];
     EG_REQUIRE(M >= 0 && (!rebase || ranges_host[c] < (1ll << 31)), "bad sizes");
@@ -455,27 +346,11 @@ extern "C" int eg_tile_emit_sort_ts(const float *means2d, const int32_t *radii, 
     const int64_t b = ranges_host[c], M = M_host[c];
     const int n = (int)(ranges_host[c + 1] - b);
     if (M > 0) {
-      const int32_t *offs = offsets + (size_t)(T + 1) * c;
-      if (2 * T <= kTsMaxLdsWords)
-        ts_emit_kernel<true><<<cdiv(n, kTsBinThreads), kTsBinThreads, sizeof(int) * 2 * T, as_stream(stream)>>>(
-            (const float2 *)means2d + b, radii + b, depths + b, n, (float)tile_size, tw, th, offs,
-            tile_counts + (size_t)T * c, (long long)M, (unsigned long long *)keys + m_base);
-      else
-        ts_emit_kernel<false><<<cdiv(n, kTsBinThreads), kTsBinThreads, 0, as_stream(stream)>>>(
-            (const float2 *)means2d + b, radii + b, depths + b, n, (float)tile_size, tw, th, offs,
-            tile_counts + (size_t)T * c, (long long)M, (unsigned long long *)keys + m_base);
-      int rc = check_launch("tile_emit_sort_ts");
+      const int rc = bin_camera("tile_emit_sort_ts", means2d + 2 * b, radii + b, depths + b, n, tile_size, tw, th,
+                                offsets + (size_t)(T + 1) * c, tile_counts + (size_t)T * c, M, keys + m_base,
+                                flatten_ids + m_base, isect_ids ? isect_ids + m_base : nullptr,
+                                max_tile_host ? max_tile_host[c] : 0, rebase ? (int)b : 0, (int64_t)c << (32 + bits), stream);
       if (rc) return rc;
-      int64_t *ids = isect_ids ? isect_ids + m_base : nullptr;
-      rc = eg_sort_pairs(keys + m_base, offs, T, M, flatten_ids + m_base, ids, max_tile_host ? max_tile_host[c] : 0, stream);
-      if (rc) return rc;
-      const int id_base = rebase ? (int)b : 0;
-      if (id_base != 0 || (ids && c > 0)) {
-        ts_rebase_kernel<<<cdiv(M, 256), 256, 0, as_stream(stream)>>>(flatten_ids + m_base, (long long *)ids, (long long)M,
-                                                                     id_base, (long long)c << (32 + tile_bits));
-        rc = check_launch("tile_emit_sort_ts");
-        if (rc) return rc;
-      }
     }
     m_base += M;
   }

@@ -21,7 +21,6 @@ Not supported, each a NotImplementedError: ``packed=True`` (use ``rasterization(
 ``sort=False``, ``masks``, and a ``viewmats`` that requires grad together with ``covars``."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Tuple
 
@@ -218,25 +217,13 @@ def isect_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, 
     T = tw * th
     m2, rd, dp = means2d.detach().contiguous(), radii.contiguous(), depths.detach().contiguous()
     tpg = torch.zeros(Cn, N, dtype=torch.int32, device=dev)
-    empty = (tpg, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev))
     if N == 0:
-        return empty
+        return tpg, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
     counts = torch.zeros(Cn, T, dtype=torch.int32, device=dev)
-    tile_bits = int(math.floor(math.log2(T))) + 1
-    if tile_size != TILE:
-        ranges = [c * N for c in range(Cn + 1)]
-        call("eg_tile_count_ts", ptr(m2), ptr(rd), (C.c_int64 * (Cn + 1))(*ranges), Cn, width, height, tile_size, ptr(tpg),
-             ptr(counts), stream())
-        _offsets, flat, ids, Ms = _R.isect_tiles_and_sort_ts(m2, rd, dp, ranges, counts, width, height, tile_size, rebase=True)
-        M = sum(Ms)
-        return tpg, ids[:M], flat[:M]
-    for c in range(Cn):
-        call("eg_tile_count", ptr(m2[c]), ptr(rd[c]), N, width, height, ptr(tpg[c]), ptr(counts[c]), stream())
-    _o, f_l, i_l, Ms = _R.isect_tiles_and_sort_cams(m2, rd, dp, counts, width, height)[:4]
-    if sum(Ms) == 0:
-        return empty
-    return (tpg, torch.cat([i_l[c] | (c << (32 + tile_bits)) for c in range(Cn)]),
-            torch.cat([f_l[c] + c * N for c in range(Cn)]))
+    ranges = [c * N for c in range(Cn + 1)]
+    _R.count_tiles(m2, rd, ranges, width, height, tile_size, tpg, counts)
+    info = _R.bin_tiles(m2, rd, dp, ranges, counts, width, height, tile_size, packed=False).info
+    return tpg, info["isect_ids"], info["flatten_ids"]
 
 
 @torch.no_grad()

@@ -18,7 +18,7 @@ include/edgegs.h with raw device pointers on the current HIP stream.  No CPU fal
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -70,7 +70,7 @@ def _check(t: Tensor, shape, name: str, dtype=torch.float32):
 
 class _Projection(torch.autograd.Function):
     """gsplat ``fully_fused_projection`` (packed=False) for C cameras, tile counting fused in (tile_size 16; any other
-    tile size: the projection without its counting, then eg_tile_count_ts).  `ortho`: EG_FLAG_ORTHO, the orthographic
+    tile size: the projection without its counting, then `count_tiles`).  `ortho`: EG_FLAG_ORTHO, the orthographic
     instantiations of the same kernels, forward and backward."""
 
     @staticmethod
@@ -97,8 +97,7 @@ class _Projection(torch.autograd.Function):
              near_plane, far_plane, eps2d, radius_clip, flags, ptr(splat), ptr(radii), ptr(means2d), ptr(depths), ptr(conics),
              ptr(comps), ptr(tpg) if fused else None, ptr(counts) if fused else None, stream())
         if not fused:
-            call("eg_tile_count_ts", ptr(means2d), ptr(radii), (C.c_int64 * (Cn + 1))(*[c * N for c in range(Cn + 1)]), Cn,
-                 width, height, tile_size, ptr(tpg), ptr(counts), stream())
+            count_tiles(means2d, radii, [c * N for c in range(Cn + 1)], width, height, tile_size, tpg, counts)
         ctx.save_for_backward(means_c, quats_c, scales_c, opac_c, vm, Kc, splat)
         ctx.cfg = (width, height, eps2d, flags)
         ctx.mark_non_differentiable(radii, tpg, counts, splat)
@@ -203,8 +202,7 @@ class _PackedProjection(torch.autograd.Function):
              near_plane, far_plane, eps2d, radius_clip, flags, ptr(block_base), nnz, ptr(splat), ptr(radii), ptr(means2d),
              ptr(depths), ptr(conics), ptr(comps), ptr(tpg), ptr(camera_ids), ptr(gaussian_ids), ptr(counts16), stream())
         if tile_size != TILE:  # (tiles_per_gauss is written again, for this tile size)
-            call("eg_tile_count_ts", ptr(means2d), ptr(radii), (C.c_int64 * (Cn + 1))(*indptr_host), Cn, width, height,
-                 tile_size, ptr(tpg), ptr(counts), stream())
+            count_tiles(means2d, radii, indptr_host, width, height, tile_size, tpg, counts)
         holder["indptr"] = indptr_host
         ctx.save_for_backward(means_c, quats_c, scales_c, opac_c, vm, Kc, indptr, camera_ids, gaussian_ids)
         ctx.cfg = (width, height, eps2d, flags, bool(sparse_grad))
@@ -307,12 +305,7 @@ class _CovarProjection(torch.autograd.Function):
         splat = torch.cat([means2d, conics, (o * comps if antialiased else o)[..., None], depths[..., None],
                            radii.view(torch.float32)[..., None]], dim=-1).contiguous()
         if N > 0:
-            if tile_size == TILE:
-                for c in range(Cn):
-                    call("eg_tile_count", ptr(means2d[c]), ptr(radii[c]), N, width, height, ptr(tpg[c]), ptr(counts[c]), stream())
-            else:
-                call("eg_tile_count_ts", ptr(means2d), ptr(radii), (C.c_int64 * (Cn + 1))(*[c * N for c in range(Cn + 1)]), Cn,
-                     width, height, tile_size, ptr(tpg), ptr(counts), stream())
+            count_tiles(means2d, radii, [c * N for c in range(Cn + 1)], width, height, tile_size, tpg, counts)
         ctx.save_for_backward(means_c, cv, vm, Kc, radii)
         ctx.cfg = (width, height, eps2d, flags, bool(antialiased))
         ctx.mark_non_differentiable(radii, tpg, counts, splat)
@@ -386,8 +379,7 @@ class _PackedCovarProjection(torch.autograd.Function):
              far_plane, eps2d, radius_clip, flags, ptr(block_base), nnz, ptr(splat), ptr(radii), ptr(means2d), ptr(depths),
              ptr(conics), ptr(comps), ptr(tpg), ptr(camera_ids), ptr(gaussian_ids), ptr(counts16), stream())
         if tile_size != TILE:  # (tiles_per_gauss is written again, for this tile size)
-            call("eg_tile_count_ts", ptr(means2d), ptr(radii), (C.c_int64 * (Cn + 1))(*indptr_host), Cn, width, height,
-                 tile_size, ptr(tpg), ptr(counts), stream())
+            count_tiles(means2d, radii, indptr_host, width, height, tile_size, tpg, counts)
         holder["indptr"] = indptr_host
         ctx.save_for_backward(means_c, cv, vm, Kc, indptr, camera_ids, gaussian_ids)
         ctx.cfg = (width, height, eps2d, flags, bool(sparse_grad))
@@ -1041,61 +1033,98 @@ def isect_tiles_and_sort(means2d: Tensor, radii: Tensor, depths: Tensor, counts:
     return offsets, flat[:M], (ids[:M] if ids is not None else None), M, item_offsets, total, n_items
 
 
-def isect_tiles_and_sort_cams(means2d: Tensor, radii: Tensor, depths: Tensor, counts: Tensor, width: int, height: int,
-                              extra_flag: Optional[Tensor] = None):
-    """`isect_tiles_and_sort` for the C cameras of one call ([C, N, ...] inputs, `counts` [C, T]) by THREE native calls and
-    ONE host read-back (round 6: it was three calls and one read-back PER CAMERA): the C tile scans, then -- the M_c known --
-    key emission + per-tile sort of every camera (csrc/cams.hip).  Returns per-camera lists
-    (offsets, flat, ids, M, item_offsets, total, n_items) and the value of `extra_flag`."""
+def count_tiles(means2d: Tensor, radii: Tensor, ranges, width: int, height: int, tile_size: int, tpg: Tensor,
+                counts: Tensor) -> None:
+    """The tile counts of `tile_size` for C cameras: camera c owns entries [ranges[c], ranges[c + 1]) of the flat
+    `means2d` / `radii` / `tpg` (tiles_per_gauss, written) and row c of `counts` [C, T] (accumulated).  eg_tile_count
+    per camera at 16, eg_tile_count_ts otherwise.  (The quats + scales projections count 16-pixel tiles inside their
+    own kernels and come here for 8 and 32 only.)"""
+    Cn, T = counts.shape
+    if tile_size == TILE:
+        for c in range(Cn):
+            a = ranges[c]
+            call("eg_tile_count", ptr(means2d) + 8 * a, ptr(radii) + 4 * a, ranges[c + 1] - a, width, height,
+                 ptr(tpg) + 4 * a, ptr(counts) + 4 * T * c, stream())
+    else:
+        call("eg_tile_count_ts", ptr(means2d), ptr(radii), (C.c_int64 * (Cn + 1))(*ranges), Cn, width, height, tile_size,
+             ptr(tpg), ptr(counts), stream())
+
+
+class Binning(NamedTuple):
+    """What `bin_tiles` returns: the cameras' sorted lists one after the other in one allocation."""
+    offsets: Tensor        # [C, T + 1] int32, each row local to its camera's list
+    flat: Tensor           # [max(M, 1)] int32: ids inside the camera's range (dense) or the whole list (packed)
+    Ms: List[int]          # the cameras' intersection counts; M = sum(Ms)
+    item_offsets: Tensor   # [C, T + 1] int32: the scan of the tiles' 128-Gaussian slices
+    total: Tensor          # [C, 4] int32: M_c, overflow flag, items, fullest tile
+    n_items: List[int]
+    info: Dict             # gsplat's isect_ids [M] int64, flatten_ids [M] int32, isect_offsets [C, th, tw] int32
+    extra: Optional[int]   # the value of `extra_flag`
+
+    def camera_lists(self) -> Tuple[Tensor, ...]:
+        """Per-camera views of `flat`; a camera without intersections gets a one-element dummy."""
+        out, base = [], 0
+        for m in self.Ms:
+            out.append(self.flat[base:base + m] if m > 0 else torch.zeros(1, dtype=torch.int32, device=self.flat.device))
+            base += m
+        return tuple(out)
+
+
+def bin_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, ranges, counts: Tensor, width: int, height: int,
+              tile_size: int, packed: bool, extra_flag: Optional[Tensor] = None) -> Binning:
+    """The binning of the general path behind the counting, for C cameras and tiles of 8, 16 or 32 pixels, by TWO native
+    calls and ONE host read-back (gsplat has one too: the cumsum total before allocating): the C tile scans
+    (eg_tile_offsets_cams), then -- the M_c known, keys / flat / ids allocated once for all cameras -- key emission and
+    per-tile sort of every camera: eg_tile_emit_sort_cams (dense, 16), eg_packed_bin (packed, 16) or
+    eg_tile_emit_sort_ts (8 and 32).  Camera c owns entries [ranges[c], ranges[c + 1]) of the flat `means2d` / `radii` /
+    `depths`: [c N, (c + 1) N) of the dense [C, N, ...] arrays, indptr of the packed lists.  `counts` [C, T] holds the
+    tile counts and is returned to zero.  `extra_flag`: a device scalar the caller wants back with the read-back.
+
+    The compositing takes `offsets` and `flat`: ids local to the camera (dense) or indices into the packed list.  The
+    gsplat layout of `info` is assembled here: the camera in the bits above the tile's in `isect_ids` (written
+    natively by all but the dense 16-pixel entry), `flatten_ids` = c * N + n or the packed index, `isect_offsets`
+    global."""
     dev = means2d.device
-    Cn, N = means2d.shape[0], means2d.shape[1]
-    T = counts.shape[1]
+    Cn, T = counts.shape
+    tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
     offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
     item_offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
     total = torch.zeros(Cn, 4, dtype=torch.int32, device=dev)  # total[:, 1] (overflow) is sticky: start from zero
     call("eg_tile_offsets_cams", ptr(counts), T, Cn, 1 << 40, ptr(offsets), ptr(item_offsets), ptr(total), stream())
     words = total.reshape(-1) if extra_flag is None else torch.cat([total.reshape(-1), extra_flag.to(torch.int32).reshape(1)])
-    vals = words.tolist()  # the one read-back of the call (gsplat has one too: the cumsum total before allocating)
+    vals = words.tolist()  # the read-back
     extra = int(vals[4 * Cn]) if extra_flag is not None else None
     Ms = [int(vals[4 * c]) for c in range(Cn)]
     n_items = [int(vals[4 * c + 2]) for c in range(Cn)]
     nmax = [int(vals[4 * c + 3]) for c in range(Cn)]
-    keys = [torch.empty(max(m, 1), dtype=torch.int64, device=dev) for m in Ms]
-    flat = [torch.empty(max(m, 1), dtype=torch.int32, device=dev) for m in Ms]
-    ids = [torch.empty(max(m, 1), dtype=torch.int64, device=dev) for m in Ms]
-    PV = C.c_void_p * Cn
-    call("eg_tile_emit_sort_cams", ptr(means2d), ptr(radii), ptr(depths), N, Cn, width, height, ptr(offsets), ptr(counts),
-         (C.c_int64 * Cn)(*Ms), PV(*[ptr(k) for k in keys]), PV(*[ptr(f) for f in flat]), PV(*[ptr(i) for i in ids]),
-         (C.c_int32 * Cn)(*nmax), stream())
-    return ([offsets[c] for c in range(Cn)], [flat[c][:Ms[c]] for c in range(Cn)], [ids[c][:Ms[c]] for c in range(Cn)], Ms,
-            [item_offsets[c] for c in range(Cn)], [total[c] for c in range(Cn)], n_items, extra)
-
-
-def isect_tiles_and_sort_ts(means2d: Tensor, radii: Tensor, depths: Tensor, ranges, counts: Tensor, width: int, height: int,
-                            tile_size: int, rebase: bool):
-    """Binning on tiles of `tile_size` pixels (csrc/tiles.hip) for C cameras by TWO native calls and one host read-back:
-    the C tile scans, then -- the M_c known -- eg_tile_emit_sort_ts.  Camera c owns entries [ranges[c], ranges[c + 1]) of
-    the flat inputs; `counts` [C, T] holds eg_tile_count_ts's counts and is returned to zero.  Returns offsets [C, T + 1]
-    (each row local to its camera's list), the cameras' flatten_ids and isect_ids one after the other (max(M, 1)
-    entries; the ids index the camera's own range, or with `rebase` the whole list; the isect ids carry the camera)
-    and the M_c."""
-    dev = means2d.device
-    Cn, T = counts.shape
-    offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
-    item_offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
-    total = torch.zeros(Cn, 4, dtype=torch.int32, device=dev)  # total[:, 1] (overflow) is sticky: start from zero
-    call("eg_tile_offsets_cams", ptr(counts), T, Cn, 1 << 40, ptr(offsets), ptr(item_offsets), ptr(total), stream())
-    vals = total.reshape(-1).tolist()  # the read-back of the M_c
-    Ms = [int(vals[4 * c]) for c in range(Cn)]
-    nmax = [int(vals[4 * c + 3]) for c in range(Cn)]
+    bases = [sum(Ms[:c]) for c in range(Cn)]
     M = sum(Ms)
     keys = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
     flat = torch.zeros(max(M, 1), dtype=torch.int32, device=dev)
     ids = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
-    call("eg_tile_emit_sort_ts", ptr(means2d), ptr(radii), ptr(depths), (C.c_int64 * (Cn + 1))(*ranges), Cn, width, height,
-         tile_size, ptr(offsets), ptr(counts), (C.c_int64 * Cn)(*Ms), ptr(keys), ptr(flat), ptr(ids), (C.c_int32 * Cn)(*nmax),
-         int(rebase), stream())
-    return offsets, flat, ids, Ms
+    Ms_host, nmax_host = (C.c_int64 * Cn)(*Ms), (C.c_int32 * Cn)(*nmax)
+    if tile_size != TILE:
+        call("eg_tile_emit_sort_ts", ptr(means2d), ptr(radii), ptr(depths), (C.c_int64 * (Cn + 1))(*ranges), Cn, width,
+             height, tile_size, ptr(offsets), ptr(counts), Ms_host, ptr(keys), ptr(flat), ptr(ids), nmax_host, int(packed),
+             stream())
+    elif packed:
+        call("eg_packed_bin", ptr(means2d), ptr(radii), ptr(depths), (C.c_int64 * (Cn + 1))(*ranges), Cn, width, height,
+             ptr(offsets), ptr(counts), Ms_host, ptr(keys), ptr(flat), ptr(ids), nmax_host, stream())
+    else:  # (host arrays of per-camera pointers: into the one allocation)
+        PV = C.c_void_p * Cn
+        call("eg_tile_emit_sort_cams", ptr(means2d), ptr(radii), ptr(depths), ranges[1] - ranges[0], Cn, width, height,
+             ptr(offsets), ptr(counts), Ms_host, PV(*[ptr(keys) + 8 * b for b in bases]),
+             PV(*[ptr(flat) + 4 * b for b in bases]), PV(*[ptr(ids) + 8 * b for b in bases]), nmax_host, stream())
+    isect_ids, flatten_ids, isect_offsets = ids[:M], flat[:M], offsets[:, :-1]
+    if Cn > 1:
+        isect_offsets = isect_offsets + torch.tensor(bases, dtype=torch.int32, device=dev)[:, None]
+        if not packed:
+            cam = torch.repeat_interleave(torch.arange(Cn, device=dev), torch.tensor(Ms, device=dev), output_size=M)
+            flatten_ids = flatten_ids + (cam * (ranges[1] - ranges[0])).to(torch.int32)
+            if tile_size == TILE:
+                isect_ids = isect_ids | (cam << (32 + int(math.floor(math.log2(T))) + 1))
+    info = {"isect_ids": isect_ids, "flatten_ids": flatten_ids, "isect_offsets": isect_offsets.reshape(Cn, th, tw)}
+    return Binning(offsets, flat, Ms, item_offsets, total, n_items, info, extra)
 
 
 RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
@@ -1109,7 +1138,8 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
     `colors` holds the coefficients and the colours are evaluated behind the projection (its radii are their mask).
     With `chunk` (colours of a channel count other than 1 or 3, in any mode that renders them): the same projection,
     binning and sort, then the compositing of eg_composite_{fwd,bwd}_wide_cams in chunks of `chunk` channels.
-    With a `tile_size` of 8 or 32 (always with `chunk`): counting, emission and compositing by csrc/tiles.hip.
+    With a `tile_size` of 8 or 32 (always with `chunk`): counting and emission by the entries that take a tile size
+    (the general path's one kernel pair, csrc/binning.hip), compositing by csrc/tiles.hip.
     `ortho`: the orthographic projection; everything behind the projection is the same.  `covars` [N, 3, 3]: the
     projection from covariances (`_CovarProjection`; `quats` and `scales` are not read)."""
     N, Cn = means.shape[0], viewmats.shape[0]
@@ -1125,34 +1155,16 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
     if antialiased:
         opac = opac * comps
     tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
-    tile_bits = int(math.floor(math.log2(tw * th))) + 1
     with torch.no_grad():
-        if tile_size != TILE:
-            offsets, flat, ids, Ms = isect_tiles_and_sort_ts(
-                means2d.contiguous(), radii, depths.contiguous(), [c * N for c in range(Cn + 1)], counts, width, height,
-                tile_size, rebase=False)
-            M = sum(Ms)
-            bases = torch.tensor([sum(Ms[:c]) for c in range(Cn)], dtype=torch.int32, device=means.device)
-            cam_base = torch.repeat_interleave(torch.arange(Cn, dtype=torch.int32, device=means.device) * N,
-                                               torch.tensor(Ms, device=means.device), output_size=M)
-            binfo = {"isect_ids": ids[:M], "flatten_ids": flat[:M] + cam_base,
-                     "isect_offsets": (offsets[:, :-1] + bases[:, None]).reshape(Cn, th, tw)}
-        else:
-            o_l, f_l, i_l, Ms = isect_tiles_and_sort_cams(means2d.contiguous(), radii, depths.contiguous(), counts, width,
-                                                          height)[:4]
-            offsets = torch.stack(o_l)  # [C, T+1], each row local to its camera's list
-            flat = torch.cat(f_l) if sum(Ms) > 0 else torch.zeros(1, dtype=torch.int32, device=means.device)
-            bases = [sum(Ms[:c]) for c in range(Cn)]
-            binfo = {"isect_ids": torch.cat([i_l[c] | (c << (32 + tile_bits)) for c in range(Cn)]),
-                     "flatten_ids": torch.cat([f_l[c] + c * N for c in range(Cn)]),
-                     "isect_offsets": torch.stack([(o_l[c][:-1] + bases[c]).reshape(th, tw) for c in range(Cn)])}
+        b = bin_tiles(means2d.contiguous(), radii, depths.contiguous(), [c * N for c in range(Cn + 1)], counts, width,
+                      height, tile_size, packed=False)
     if tile_size != TILE or (chunk is not None and colors is not None):
         render, alphas, last_ids = _TileCompositing.apply(
-            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, b.offsets, b.flat,
             bool(absgrad), _splat, depth, chunk, tile_size)
     else:
         render, alphas, last_ids = _ModeCompositing.apply(
-            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, b.offsets, b.flat,
             bool(absgrad), _splat, depth)
     if render_mode in ("ED", "RGB+ED"):
         render = torch.cat([render[..., :-1], render[..., -1:] / alphas.clamp(min=1e-10)], dim=-1)
@@ -1160,7 +1172,7 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
         "camera_ids": None, "gaussian_ids": None,
         "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
         "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
-        **binfo,
+        **b.info,
         "width": width, "height": height, "tile_size": tile_size, "n_cameras": Cn,
         "last_ids": last_ids,
     }
@@ -1174,8 +1186,9 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
     in torch (dense gradients of the caller's shapes, as in gsplat), every camera's range binned as a single-camera
     problem (eg_packed_bin), and the mode / wide compositing kernels on the packed records (record stride
     _lib.PACKED_STRIDE).  Never the unit-colour fast path.  Two host read-backs: indptr, then the M_c.  With a
-    `tile_size` of 8 or 32 (always with `chunk`): counting, emission and compositing by csrc/tiles.hip.  `covars`
-    [N, 3, 3]: the packed projection from covariances (`_PackedCovarProjection`; `quats` and `scales` are not read)."""
+    `tile_size` of 8 or 32 (always with `chunk`): counting and emission by the entries that take a tile size (the
+    general path's one kernel pair, csrc/binning.hip), compositing by csrc/tiles.hip.  `covars` [N, 3, 3]: the packed
+    projection from covariances (`_PackedCovarProjection`; `quats` and `scales` are not read)."""
     N, Cn = means.shape[0], viewmats.shape[0]
     dev = means.device
     depth = render_mode != "RGB"
@@ -1208,41 +1221,19 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
     if antialiased:
         opac = opac * comps
     tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
-    T = tw * th
-    with torch.no_grad():
-        if tile_size != TILE:
-            offsets, flat, ids, Ms = isect_tiles_and_sort_ts(means2d, radii, depths, indptr, counts, width, height,
-                                                             tile_size, rebase=True)
-            M = sum(Ms)
-        else:
-            offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
-            item_offsets = torch.empty(Cn, T + 1, dtype=torch.int32, device=dev)
-            total = torch.zeros(Cn, 4, dtype=torch.int32, device=dev)
-            call("eg_tile_offsets_cams", ptr(counts), T, Cn, 1 << 40, ptr(offsets), ptr(item_offsets), ptr(total), stream())
-            vals = total.reshape(-1).tolist()  # the second and last read-back of the call
-            Ms = [int(vals[4 * c]) for c in range(Cn)]
-            nmax = [int(vals[4 * c + 3]) for c in range(Cn)]
-            M = sum(Ms)
-            keys = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
-            flat = torch.zeros(max(M, 1), dtype=torch.int32, device=dev)
-            ids = torch.empty(max(M, 1), dtype=torch.int64, device=dev)
-            call("eg_packed_bin", ptr(means2d), ptr(radii), ptr(depths), (C.c_int64 * (Cn + 1))(*indptr), Cn, width, height,
-                 ptr(offsets), ptr(counts), (C.c_int64 * Cn)(*Ms), ptr(keys), ptr(flat), ptr(ids), (C.c_int32 * Cn)(*nmax),
-                 stream())
-        bases = torch.tensor([sum(Ms[:c]) for c in range(Cn)], dtype=torch.int32, device=dev)
-        binfo = {"isect_ids": ids[:M], "flatten_ids": flat[:M],
-                 "isect_offsets": (offsets[:, :-1] + bases[:, None]).reshape(Cn, th, tw)}
+    with torch.no_grad():  # (the second and last read-back of the call)
+        b = bin_tiles(means2d, radii, depths, indptr, counts, width, height, tile_size, packed=True)
     if colors is not None and backgrounds is None and not depth and chunk is None:
         # plain RGB with 1 or 3 channels: the mode kernels' <CH, no depth, background> instantiation under a zero
         # background (T_final * 0 added to every channel), as `_mode_rasterization` runs RGB with real backgrounds
         backgrounds = torch.zeros(Cn, colors.shape[-1], device=dev)
     if tile_size != TILE or (chunk is not None and colors is not None):
         render, alphas, last_ids = _TileCompositing.apply(
-            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, b.offsets, b.flat,
             bool(absgrad), splat, depth, chunk, tile_size, Cn)
     else:
         render, alphas, last_ids = _ModeCompositing.apply(
-            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, offsets, flat,
+            means2d, conics, colors, opac.contiguous(), depths, backgrounds, width, height, b.offsets, b.flat,
             bool(absgrad), splat, depth, Cn)
     if render_mode in ("ED", "RGB+ED"):
         render = torch.cat([render[..., :-1], render[..., -1:] / alphas.clamp(min=1e-10)], dim=-1)
@@ -1250,7 +1241,7 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
         "camera_ids": camera_ids, "gaussian_ids": gaussian_ids,
         "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
         "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
-        **binfo,
+        **b.info,
         "width": width, "height": height, "tile_size": tile_size, "n_cameras": Cn,
         "last_ids": last_ids,
     }
@@ -1274,8 +1265,8 @@ def rasterization(
     ``["tile_height"]`` are ``ceil(width / tile_size)`` / ``ceil(height / tile_size)``, a Gaussian's tile box is
     ``floor / ceil((x -+ r) / tile_size)``, a pixel walks the depth-sorted list of the tile that contains it, and
     ``tiles_per_gauss``, ``isect_ids``, ``flatten_ids``, ``isect_offsets`` and ``last_ids`` refer to those tiles.  16
-    takes the paths described below.  8 and 32 take the general path with counting, key emission and compositing kernels
-    of their own (csrc/tiles.hip) -- every ``packed`` / ``sparse_grad`` / ``render_mode`` / ``backgrounds`` /
+    takes the paths described below.  8 and 32 take the general path -- its counting and key emission kernels with that
+    tile size (csrc/binning.hip), compositing kernels of their own (csrc/tiles.hip) -- with every ``packed`` / ``sparse_grad`` / ``render_mode`` / ``backgrounds`` /
     ``sh_degree`` / ``rasterize_mode`` / ``absgrad`` / cull / pose-gradient combination described below, never the
     unit-colour fast path -- and composite every channel count, D = 1 and 3 included, in ``ceil(D / chunk)`` launches per
     direction (the depth-only modes: one).
@@ -1436,37 +1427,25 @@ def rasterization(
         opac = opac * comps
 
     tw, th = math.ceil(width / TILE), math.ceil(height / TILE)
-    tile_bits = int(math.floor(math.log2(tw * th))) + 1
-    offs_l, flat_l, ids_l, item_l, tot_l, nit_l = [], [], [], [], [], []
-    m_base = 0
-    info_offsets = []
     # the reference always passes torch.ones(N,3) without grad (edge_gs.py:247, a fresh tensor every step): decide
     # "unit colours" on the device and read the verdict back with M (the one host sync gsplat also has)
     # (never with `covars`: that call takes the general compositing kernels whatever its colours are)
     unit_flag = None if (colors.requires_grad or covars is not None) else (colors == 1).all()
     with torch.no_grad():
-        o_l, f_l, i_l, Ms, item_l, tot_l, nit_l, extra = isect_tiles_and_sort_cams(
-            means2d.contiguous(), radii, depths.contiguous(), counts, width, height, extra_flag=unit_flag)
-        for c in range(Cn):
-            offs_l.append(o_l[c])
-            flat_l.append(f_l[c] if Ms[c] > 0 else torch.zeros(1, dtype=torch.int32, device=means.device))
-            ids_l.append((i_l[c] | (c << (32 + tile_bits)), f_l[c] + c * N, Ms[c]))
-            info_offsets.append((o_l[c][:-1] + m_base).reshape(th, tw))
-            m_base += Ms[c]
+        b = bin_tiles(means2d.contiguous(), radii, depths.contiguous(), [c * N for c in range(Cn + 1)], counts, width,
+                      height, TILE, packed=False, extra_flag=unit_flag)
 
     # ... and take the order-independent unit-colour kernels when that is what we were given
-    unit = unit_flag is not None and bool(extra)
+    unit = unit_flag is not None and bool(b.extra)
     render, alphas, last_ids = _Compositing.apply(
-        means2d, conics, colors, opac.contiguous(), width, height, tuple(offs_l), tuple(flat_l), bool(absgrad),
-        unit, tuple(item_l), tuple(tot_l), tuple(nit_l), _splat)
+        means2d, conics, colors, opac.contiguous(), width, height, tuple(b.offsets), b.camera_lists(), bool(absgrad),
+        unit, tuple(b.item_offsets), tuple(b.total), tuple(b.n_items), _splat)
 
     info = {
         "camera_ids": None, "gaussian_ids": None,
         "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
         "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
-        "isect_ids": torch.cat([t[0][:t[2]] for t in ids_l]),
-        "flatten_ids": torch.cat([t[1][:t[2]] for t in ids_l]),
-        "isect_offsets": torch.stack(info_offsets),
+        **b.info,
         "width": width, "height": height, "tile_size": tile_size, "n_cameras": Cn,
         "last_ids": last_ids,
     }

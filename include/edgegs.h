@@ -101,7 +101,8 @@ int eg_project_bin(const float *means, const float *quats, const float *log_scal
                    int32_t *total /*[4]*/, int32_t *ticket /*[1]*/, eg_stream_t stream);
 
 /* ---- G2 (per-Gaussian part) on caller-supplied screen data: tiles_per_gauss + tile_counts from
- * (means2d, radii).  Used when projection ran elsewhere (parity tests feed oracle floats). */
+ * (means2d, radii).  Used when projection ran elsewhere (parity tests feed oracle floats).  The general path's one
+ * counting kernel (tiles of 8, 16 and 32 pixels: eg_tile_count_ts) at 16. */
 int eg_tile_count(const float *means2d, const int32_t *radii, int32_t N, int32_t width, int32_t height,
                   int32_t *tiles_per_gauss /*[N]|NULL*/, int32_t *tile_counts /*[T]*/, eg_stream_t stream);
 
@@ -118,7 +119,10 @@ int eg_tile_offsets(const int32_t *tile_counts /*[T]*/, int32_t T, int64_t capac
                     eg_stream_t stream);
 
 /* ---- G4: emit one (depth_bits<<32 | gaussian_id) key per (Gaussian, tile) into that tile's
- * segment [offsets[t], offsets[t+1]) (order inside a segment arbitrary; eg_sort_pairs fixes it). */
+ * segment [offsets[t], offsets[t+1]) (order inside a segment arbitrary; eg_sort_pairs fixes it).  Two forms: from
+ * (means2d, radii, depths) -- splat NULL; flags and tile_mask are not read -- by the general path's one emission kernel
+ * (tiles of 8, 16 and 32 pixels: eg_tile_emit_sort_ts) at 16; from the splat records by a kernel of its own, which
+ * alone knows the tight boxes and exact tile hits of the training step's classic layout. */
 int eg_tile_emit(const float *means2d_or_null, const int32_t *radii_or_null, const float *depths_or_null,
                  const float *splat_or_null, uint32_t flags /*EG_FLAG_TIGHT_TILES needs splat*/,
                  int32_t N, int32_t width, int32_t height,
@@ -627,7 +631,10 @@ int eg_train_step_batched(const eg_step_args *args_host, int32_t C, const float 
 /* ---- C cameras per native call for the GENERAL operator path (gsplat.rasterization takes viewmats [C,4,4]; the reference
  * itself calls it with one camera, edge_gs.py:250-268).  Native loops over the per-camera entries above -- the same kernels,
  * the same results -- with the cameras' arrays as [C, ...] blocks, or as HOST arrays of C device pointers where the sizes
- * differ per camera (the binning arrays of M_c entries).  One native call per stage, one host read-back for all totals. */
+ * differ per camera (the binning arrays of M_c entries).  One native call per stage, one host read-back for all totals.
+ * eg_tile_emit_sort_cams: per camera the binning step eg_packed_bin and eg_tile_emit_sort_ts run too (emission from
+ * means2d / radii / depths, eg_sort_pairs), here without an id base and without the camera in the isect ids: the sorted
+ * ids stay local to the camera. */
 int eg_project_fwd_cams(const float *means, const float *quats, const float *scales, const float *opacities,
                         const float *viewmats /*[C,4,4]*/, const float *Ks /*[C,3,3]*/, int32_t N, int32_t C, int32_t width,
                         int32_t height, float near_plane, float far_plane, float eps2d, float radius_clip, uint32_t flags,
@@ -730,7 +737,8 @@ int eg_composite_bwd_wide_cams(int32_t C, const float *splat /*[C,N,8]*/, int32_
  *   compositing kernels: x y a b c opacity*compensation depth radius), radii / depths / compensations /
  *   tiles_per_gauss [nnz], means2d [nnz, 2], conics [nnz, 3], camera_ids / gaussian_ids [nnz] int64, and adds the
  *   tile hits to tile_counts [C, T] (zeroed by the caller).  All outputs are required.  nnz == 0: nothing to do.
- * eg_packed_bin: eg_tile_emit + eg_sort_pairs on every camera's range; indptr_host [C + 1], M_host [C] and
+ * eg_packed_bin: emission (the general path's one kernel, as eg_tile_emit without splat) + eg_sort_pairs + the rebase
+ *   of the sorted ids on every camera's range; indptr_host [C + 1], M_host [C] and
  *   max_tile_host [C] (or NULL) are HOST arrays, offsets [C, T + 1] from eg_tile_offsets_cams; keys / flatten_ids /
  *   isect_ids (NULL ok) hold sum(M_host) entries, camera c's from sum(M_host[:c]).  flatten_ids index the whole packed
  *   list; isect_ids carry the camera above the tile bits (camera << (32 + floor(log2(T)) + 1)).
@@ -805,7 +813,9 @@ int eg_packed_bwd_sparse_covars(const float *means, const float *covars /*[N,6]*
  * eg_sort_pairs depend on the tile size through T only and serve these entries as they are.  A tile size other than
  * the ones named, or bad sizes, return EG_ERR_ARG before anything is launched.
  * eg_tile_count_ts / eg_tile_emit_sort_ts (tile_size 8 or 32): eg_tile_count and eg_tile_emit + eg_sort_pairs for C
- *   cameras in one native call.  ranges_host [C + 1] (HOST, ascending): camera c owns entries [ranges_host[c],
+ *   cameras in one native call -- the very kernels of those entries (csrc/binning.hip: one counting and one emission
+ *   kernel with the tile size as an argument), which 16 reaches through eg_tile_count, eg_tile_emit_sort_cams and
+ *   eg_packed_bin.  ranges_host [C + 1] (HOST, ascending): camera c owns entries [ranges_host[c],
  *   ranges_host[c + 1]) of means2d / radii / depths / tiles_per_gauss -- {0, N, 2 N, ...} for the dense [C, N, ...]
  *   arrays of eg_project_fwd_cams (called with tiles_per_gauss and tile_counts NULL: its fused counting is 16-pixel),
  *   indptr for the packed lists of eg_packed_write.  tile_counts [C, T]: zeroed by the caller, accumulated by the count,

@@ -242,7 +242,7 @@ def _plain_kw(sc, cams, colors):
                 viewmats=sc.viewmats[cams].cuda(), Ks=sc.Ks[cams].cuda(), width=sc.width, height=sc.height)
 
 
-@pytest.mark.parametrize("ts", [8, 32])
+@pytest.mark.parametrize("ts", [8, 16, 32])
 @pytest.mark.parametrize("cams", [[1], [0, 2, 3]], ids=["C1", "C3"])
 @pytest.mark.parametrize("packed", [False, True], ids=["dense", "packed"])
 def test_binning_bit_for_bit(env, ts, cams, packed):
@@ -262,18 +262,21 @@ def test_binning_bit_for_bit(env, ts, cams, packed):
     assert M > 0
 
 
-@pytest.mark.parametrize("width,height", [(1024, 1032), (1024, 768)], ids=["16512-tiles", "12288-tiles"])
-def test_binning_beyond_the_lds_histogram(env, width, height):
-    """ts = 8 on 1024 x 1032: 16 512 tiles, more than the counting kernel's LDS histogram holds (direct atomics in the
-    counting and the emission); 1024 x 768: 12 288 tiles, LDS counting with direct-atomic emission."""
+@pytest.mark.parametrize("ts,width,height", [(8, 1024, 1032), (8, 1024, 768), (16, 2048, 2064), (16, 2048, 1536)],
+                         ids=["16512-tiles", "12288-tiles", "ts16-16512-tiles", "ts16-12288-tiles"])
+def test_binning_beyond_the_lds_histogram(env, ts, width, height):
+    """16 512 tiles (ts = 8 on 1024 x 1032, ts = 16 on 2048 x 2064): more than the counting kernel's LDS histogram holds
+    (direct atomics in the counting and the emission); 12 288 tiles (1024 x 768, 2048 x 1536): LDS counting with
+    direct-atomic emission.  The scene's Gaussians are sized in world units, so the 16-pixel cases on images twice as
+    large keep the 8-pixel cases' `scale`: the same boxes in tiles (the oracle's own M > N, checked on the CPU)."""
     from edgegaussians_amd import rasterization
     synth, O = env
     sc = synth.make_scene(3000, 2, width, height, seed=1, spread_opacity=True, scale=0.004)
     N = sc.means.shape[0]
     with torch.no_grad():
-        _r, _a, info = rasterization(tile_size=8, packed=False, **_plain_kw(sc, [0], _colors("N3", 1, N)))
-    assert info["tile_width"] * info["tile_height"] == (width // 8) * math.ceil(height / 8)
-    M = _assert_binning(O, info, 8, width, height, [(0, N)])
+        _r, _a, info = rasterization(tile_size=ts, packed=False, **_plain_kw(sc, [0], _colors("N3", 1, N)))
+    assert info["tile_width"] * info["tile_height"] == (width // ts) * math.ceil(height / ts)
+    M = _assert_binning(O, info, ts, width, height, [(0, N)])
     assert M > N
 
 

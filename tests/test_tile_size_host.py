@@ -67,7 +67,7 @@ def test_bad_tile_sizes_and_sizes_are_rejected_before_any_hip_call(lib):
                                           v_depths, n_real, 4, ps, None)
 
     for f, name in ((count, COUNT), (emit, EMIT), (fwd, FWD), (bwd, BWD)):
-        for ts in (12, 0, -8, 7, 64, 16):  # (16 has its own entries: the kernels with the compiled-in tile)
+        for ts in (12, 0, -8, 7, 64, 16):  # (16 has its own entries)
             assert f(ts=ts) != 0 and name.encode() in h.eg_last_error_string(), (name, ts)
             assert b"tile_size" in h.eg_last_error_string()
         assert f(width=0) != 0 and b"bad sizes" in h.eg_last_error_string()
@@ -84,6 +84,90 @@ def test_bad_tile_sizes_and_sizes_are_rejected_before_any_hip_call(lib):
         assert f(channels=0, n_real=1, depth=1, **({"v_depths": q} if f is bwd else {})) != 0
         assert f(channels=4, n_real=4, depth=1, ps=4, **({"v_depths": q} if f is bwd else {})) != 0  # no fifth column
     assert bwd(channels=0, n_real=0, depth=1, ps=1, v_depths=None) != 0 and b"v_depths" in h.eg_last_error_string()
+
+
+def test_binning_entries_keep_their_error_strings(lib):
+    """The entries over the shared counting / emission kernels and the per-camera binning step (csrc/binning.hip) each
+    keep their own checks and messages.  Every call below is invalid, so none of them reaches a launch."""
+    h = lib.load(require_device=False)
+    buf = (ctypes.c_float * 64)()  # a non-null host address: it is never dereferenced
+    q = ctypes.cast(buf, ctypes.c_void_p)
+    err = h.eg_last_error_string
+
+    def i64(*v):
+        return (ctypes.c_int64 * len(v))(*v)
+
+    def ptrs(*v):
+        return (ctypes.c_void_p * len(v))(*v)
+
+    def count(N=4, width=32, height=32, means2d=q, radii=q, counts=q):
+        return h.eg_tile_count(means2d, radii, N, width, height, q, counts, None)
+
+    def emit(N=4, width=32, height=32, capacity=8, means2d=q, radii=q, depths=q, splat=None, offsets=q, cursor=q, keys=q):
+        return h.eg_tile_emit(means2d, radii, depths, splat, 0, N, width, height, offsets, cursor, capacity, keys, None, None)
+
+    def cams(N=4, C=1, width=32, height=32, means2d=q, offsets=q, M=(5,), keys=ptrs(q), flat=ptrs(q), no_M=False):
+        return h.eg_tile_emit_sort_cams(means2d, q, q, N, C, width, height, offsets, q, None if no_M else i64(*M), keys, flat,
+                                        None, None, None)
+
+    def count_ts(ts=8, C=1, width=32, height=32, rng=(0, 4), means2d=q, counts=q):
+        return h.eg_tile_count_ts(means2d, q, i64(*rng) if rng else None, C, width, height, ts, q, counts, None)
+
+    def emit_ts(ts=8, C=1, width=32, height=32, rng=(0, 4), M=(5,), means2d=q, offsets=q, keys=q, flat=q, rebase=0, no_M=False):
+        return h.eg_tile_emit_sort_ts(means2d, q, q, i64(*rng) if rng else None, C, width, height, ts, offsets, q,
+                                      None if no_M else i64(*M), keys, flat, q, None, rebase, None)
+
+    def packed(indptr=(0, 4), M=(5,), C=1, width=32, height=32, means2d=q, offsets=q, keys=q):
+        return h.eg_packed_bin(means2d, q, q, i64(*indptr) if indptr else None, C, width, height, offsets, q, i64(*M), keys, q,
+                               q, None, None)
+
+    def said(rc, text):
+        assert rc == -1 and text in err(), (rc, text, err())
+
+    # bad sizes
+    for kw in (dict(N=-1), dict(width=0), dict(height=-16)):
+        said(count(**kw), b"eg_tile_count: bad sizes")
+        said(emit(**kw), b"eg_tile_emit: bad sizes")
+        said(cams(**kw), b"eg_tile_emit_sort_cams: bad sizes")
+    said(emit(capacity=-1), b"eg_tile_emit: bad sizes")
+    for kw in (dict(C=0), dict(C=65536), dict(width=0), dict(height=-16)):
+        said(count_ts(**kw), b"eg_tile_count_ts: bad sizes")
+        said(emit_ts(**kw), b"eg_tile_emit_sort_ts: bad sizes")
+    said(cams(C=0), b"eg_tile_emit_sort_cams: bad sizes")
+    for kw in (dict(C=0), dict(width=0), dict(height=-16), dict(M=(-1,)), dict(indptr=(0, 1 << 31)), dict(indptr=(0, -1))):
+        said(packed(**kw), b"eg_packed_bin: bad sizes")
+    said(emit_ts(M=(-1,)), b"eg_tile_emit_sort_ts: bad sizes")
+    said(emit_ts(rng=(1 << 31, (1 << 31) + 4), rebase=1), b"eg_tile_emit_sort_ts: bad sizes")  # past the int32 ids
+    said(emit_ts(width=1 << 20, height=1 << 20), b"eg_tile_emit_sort_ts: bad sizes")           # 2^34 tiles
+    # null pointers
+    for kw in (dict(means2d=None), dict(radii=None), dict(counts=None)):
+        said(count(**kw), b"eg_tile_count: null pointer")
+    for kw in (dict(offsets=None), dict(cursor=None), dict(keys=None)):
+        said(emit(**kw), b"eg_tile_emit: null pointer")
+    for kw in (dict(means2d=None), dict(radii=None), dict(depths=None)):
+        said(emit(**kw), b"eg_tile_emit: need splat or (means2d, radii, depths)")
+    for kw in (dict(means2d=None), dict(offsets=None), dict(no_M=True), dict(keys=None), dict(flat=None)):
+        said(cams(**kw), b"eg_tile_emit_sort_cams: null pointer")
+    said(cams(keys=ptrs(None)), b"eg_tile_emit_sort_cams: null isect array")
+    said(cams(flat=ptrs(None)), b"eg_tile_emit_sort_cams: null isect array")
+    said(cams(M=(-1,)), b"eg_tile_emit_sort_cams: null isect array")
+    for kw in (dict(rng=None), dict(means2d=None), dict(counts=None)):
+        said(count_ts(**kw), b"eg_tile_count_ts: null pointer")
+    for kw in (dict(rng=None), dict(offsets=None), dict(no_M=True), dict(means2d=None), dict(keys=None), dict(flat=None),
+               dict(rng=(0, 0))):  # (the last: intersections of an empty range)
+        said(emit_ts(**kw), b"eg_tile_emit_sort_ts: null pointer")
+    for kw in (dict(indptr=None), dict(offsets=None), dict(means2d=None), dict(keys=None), dict(indptr=(0, 0))):
+        said(packed(**kw), b"eg_packed_bin: null pointer")
+    # bad ranges
+    for f, name in ((count_ts, b"eg_tile_count_ts"), (emit_ts, b"eg_tile_emit_sort_ts")):
+        said(f(rng=(-1, 4)), name + b": bad ranges")
+        said(f(rng=(4, 0)), name + b": bad ranges")
+        said(f(rng=(0, 1 << 31)), name + b": bad ranges")  # a camera's range past the int32 ids
+        said(f(C=2, rng=(0, 4, 2)), name + b": bad ranges")
+    said(packed(indptr=(1, 4)), b"eg_packed_bin: indptr must start at 0")
+    # 16 stays with the entries of its own
+    said(count_ts(ts=16), b"eg_tile_count_ts: tile_size must be 8 or 32 (16: eg_tile_count, eg_tile_emit)")
+    said(emit_ts(ts=16), b"eg_tile_emit_sort_ts: tile_size must be 8 or 32 (16: eg_tile_count, eg_tile_emit)")
 
 
 def test_staging_batches_are_the_kernels(lib):

@@ -1,11 +1,12 @@
 """Stage times of rasterization(tile_size=8 | 16 | 32) ("Tile sizes 8 and 32"): binning, compositing forward
 and compositing backward, on 30 000 Gaussians at 512 x 512, three random colour channels, one camera, packed=False.
 
-    python tools/bench_tile_size.py [--gaussians N] [--size S] [--calls K] [--warmup W]
+    python tools/bench_tile_size.py [--gaussians N] [--size S] [--calls K] [--warmup W] [--packed]
 
 Every native call of a whole rasterization + backward is bracketed by two torch.cuda.Events on the current stream and
 its time is added to its stage; the figure of a stage is the median over the timed calls.  The 16 row is the existing
-path (tile counting fused into the projection, compositing by eg_composite_fwd_cams / eg_composite_bwd_colors)."""
+path (tile counting fused into the projection, compositing by eg_composite_fwd_cams / eg_composite_bwd_colors).
+--packed: the same call with packed=True (binning by eg_packed_bin at 16, compositing by the modes kernels)."""
 import argparse
 import json
 import os
@@ -17,7 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 STAGES = {
-    "binning": ("eg_tile_count_ts", "eg_tile_offsets_cams", "eg_tile_emit_sort_ts", "eg_tile_emit_sort_cams"),
+    "binning": ("eg_tile_count_ts", "eg_tile_offsets_cams", "eg_tile_emit_sort_ts", "eg_tile_emit_sort_cams", "eg_packed_bin"),
     "composite_fwd": ("eg_composite_fwd_ts_cams", "eg_composite_fwd_cams", "eg_composite_fwd_modes_cams",
                       "eg_composite_fwd_wide_cams"),
     "composite_bwd": ("eg_composite_bwd_ts_cams", "eg_composite_bwd_colors", "eg_composite_bwd_modes_cams",
@@ -31,6 +32,7 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--packed", action="store_true")
     a = ap.parse_args()
     from edgegaussians_amd import rasterization, synth
     from edgegaussians_amd import rasterizer as R
@@ -59,14 +61,14 @@ def main():
                 for t in p:
                     t.grad = None
                 render, alpha, info = rasterization(p[0], p[1], torch.exp(p[2]), torch.sigmoid(p[3]).squeeze(-1), colors, vm, Ks,
-                                                    a.size, a.size, packed=False, tile_size=ts)
+                                                    a.size, a.size, packed=a.packed, tile_size=ts)
                 (render.sum() + alpha.sum()).backward()
                 torch.cuda.synchronize()
                 M = int(info["flatten_ids"].shape[0])
                 if it >= a.warmup:
                     for stage, names in STAGES.items():
                         per_call[stage].append(sum(e0.elapsed_time(e1) for n, e0, e1 in spans if n in names))
-            row = {"tile_size": ts, "gaussians": N, "size": a.size, "intersections": M,
+            row = {"tile_size": ts, "packed": a.packed, "gaussians": N, "size": a.size, "intersections": M,
                    "tiles": info["tile_width"] * info["tile_height"],
                    **{f"{k}_us": round(1e3 * statistics.median(v), 1) for k, v in per_call.items()}}
             print(json.dumps(row), flush=True)
