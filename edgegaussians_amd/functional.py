@@ -96,54 +96,6 @@ def quat_scale_to_covar_preci(quats: Tensor, scales: Tensor, compute_covar: bool
 
 
 # ----------------------------------------------------------------------------------------------------------------
-class _CovarProjection(torch.autograd.Function):
-    """gsplat ``fully_fused_projection`` from covariances (packed=False) for C cameras: eg_project_covars_fwd_cams /
-    eg_project_covars_bwd_cams.  The backward sums over the cameras in camera order without atomics.  `ortho`: the
-    orthographic instantiations, through eg_project_covars_{fwd,bwd}_cams_flags with EG_FLAG_ORTHO."""
-
-    @staticmethod
-    def forward(ctx, means, covars, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip, calc_comp,
-                ortho=False):
-        Cn, N = viewmats.shape[0], means.shape[0]
-        dev = means.device
-        m, cv, vm, Kc = means.contiguous(), covars.contiguous(), viewmats.contiguous(), Ks.contiguous()
-        radii = torch.empty(Cn, N, dtype=torch.int32, device=dev)
-        means2d = torch.empty(Cn, N, 2, device=dev)
-        depths = torch.empty(Cn, N, device=dev)
-        conics = torch.empty(Cn, N, 3, device=dev)
-        comps = torch.empty(Cn, N, device=dev) if calc_comp else torch.empty(0, device=dev)
-        args = (ptr(m), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane, far_plane, eps2d, radius_clip,
-                ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps) if calc_comp else None)
-        if ortho:
-            call("eg_project_covars_fwd_cams_flags", *args, _lib.FLAG_ORTHO, stream())
-        else:
-            call("eg_project_covars_fwd_cams", *args, stream())
-        ctx.save_for_backward(m, cv, vm, Kc, radii)
-        ctx.cfg = (width, height, eps2d, calc_comp, bool(ortho))
-        ctx.mark_non_differentiable(*((radii,) if calc_comp else (radii, comps)))
-        return radii, means2d, depths, conics, comps
-
-    @staticmethod
-    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps):
-        m, cv, vm, Kc, radii = ctx.saved_tensors
-        width, height, eps2d, calc_comp, ortho = ctx.cfg
-        Cn, N = vm.shape[0], m.shape[0]
-        dev = m.device
-        vm2d = v_means2d.contiguous() if v_means2d is not None else torch.zeros(Cn, N, 2, device=dev)
-        vcon = v_conics.contiguous() if v_conics is not None else torch.zeros(Cn, N, 3, device=dev)
-        vdep = v_depths.contiguous() if v_depths is not None else None
-        vcomp = v_comps.contiguous() if (calc_comp and v_comps is not None) else None
-        v_means = torch.empty(N, 3, device=dev)
-        v_covars = torch.empty(N, 6, device=dev)
-        args = (ptr(m), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, ptr(radii), ptr(vm2d), ptr(vdep), ptr(vcon),
-                ptr(vcomp), ptr(v_means), ptr(v_covars))
-        if ortho:
-            call("eg_project_covars_bwd_cams_flags", *args, _lib.FLAG_ORTHO, stream())
-        else:
-            call("eg_project_covars_bwd_cams", *args, stream())
-        return (v_means, v_covars) + (None,) * 10
-
-
 def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Optional[Tensor], scales: Optional[Tensor],
                            viewmats: Tensor, Ks: Tensor, width: int, height: int, eps2d: float = 0.3,
                            near_plane: float = 0.01, far_plane: float = 1e10, radius_clip: float = 0.0,
@@ -183,8 +135,9 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Optio
     _check(covars, (N, 6), "covars")
     if viewmats.requires_grad and torch.is_grad_enabled():
         raise NotImplementedError("fully_fused_projection: the gradient of viewmats is not available with covars; pass quats and scales")
-    radii, means2d, depths, conics, comps = _CovarProjection.apply(
-        means, covars, viewmats, Ks, width, height, *cfg, bool(calc_compensations), ortho)
+    # (the dense covariance node of `rasterization`, as a stage: no record, no tile counts, [N, 6] in and out)
+    radii, means2d, depths, conics, comps = _R._CovarProjection.apply(
+        means, covars, None, viewmats, Ks, width, height, *cfg, bool(calc_compensations), TILE, ortho, True)[:5]
     return radii, means2d, depths, conics, (comps if calc_compensations else None)
 
 

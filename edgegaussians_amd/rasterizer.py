@@ -17,8 +17,9 @@ include/edgegs.h with raw device pointers on the current HIP stream.  No CPU fal
 """
 from __future__ import annotations
 
+import itertools
 import math
-from typing import Dict, List, NamedTuple, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -68,10 +69,109 @@ def _check(t: Tensor, shape, name: str, dtype=torch.float32):
         raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
 
 
+_TRIU = (0, 1, 2, 4, 5, 8)  # the upper triangle (00, 01, 02, 11, 12, 22) inside a row-major 3 x 3 block
+
+
+def _covars6(covars: Tensor) -> Tensor:
+    """[N, 3, 3] -> the [N, 6] upper triangle the kernels take (only the entries i <= j are read)."""
+    return covars.reshape(covars.shape[0], 9)[:, _TRIU].contiguous()
+
+
+def _covars_grad33(v6: Tensor) -> Tensor:
+    """The kernels' [rows, 6] gradient (an off-diagonal entry carries both symmetric cotangents) scattered to the upper
+    triangle of [rows, 3, 3], zeros below the diagonal: what autograd gives through ``sym_from6(covars[:, iu, ju])``."""
+    out = torch.zeros(v6.shape[0], 9, device=v6.device)
+    out[:, _TRIU] = v6
+    return out.view(-1, 3, 3)
+
+
+class _Form(NamedTuple):
+    """What differs between the two shape forms of the projection, quats + scales and covariances -- the Python
+    counterpart of QuatScaleForm / CovarForm (csrc/project_dev.h, csrc/covar_dev.h).  Everything else about a
+    projection node is written once, for both."""
+    kernel_inputs: Callable[..., Tuple[Tensor, ...]]  # the caller's shape tensors -> the contiguous kernel inputs
+    entries: Dict[str, str]      # pass -> native entry: the packed count, write, backward and sparse backward, the viewmats partial
+    opacity_heads_all: bool      # the opacity heads every pass's argument list, behind the shape (else only the write's)
+    widths: Tuple[int, ...]      # of the shape gradients' rows, one per kernel input
+    returned: Callable[[Tensor], Tensor]  # a [rows, width] gradient -> the rows of the gradient the caller's tensor gets
+    pose_slot: int               # where `viewmats` stands among the nodes' inputs (means, *shape, opacities, viewmats, ...)
+
+    def head(self, means, shape, opac, vm, Kc, write=False) -> Tuple[Tensor, ...]:
+        """The tensors whose pointers head a pass's argument list."""
+        return (means, *shape, *((opac,) if (self.opacity_heads_all or write) else ()), vm, Kc)
+
+
+_QUAT_SCALE = _Form(
+    kernel_inputs=lambda quats, scales: (quats.contiguous(), scales.contiguous()),
+    entries=dict(count="eg_packed_count", write="eg_packed_write", bwd="eg_packed_bwd", bwd_sparse="eg_packed_bwd_sparse",
+                 viewmats="eg_project_bwd_viewmats"),
+    opacity_heads_all=True, widths=(4, 3), returned=lambda v: v, pose_slot=4)
+_COVAR = _Form(
+    kernel_inputs=lambda covars: (_covars6(covars),),
+    entries=dict(count="eg_packed_count_covars", write="eg_packed_write_covars", bwd="eg_packed_bwd_covars",
+                 bwd_sparse="eg_packed_bwd_sparse_covars", viewmats="eg_project_covars_bwd_viewmats"),
+    opacity_heads_all=False, widths=(6,), returned=_covars_grad33, pose_slot=3)
+
+
+def _dense_outputs(Cn: int, N: int, dev, comps: bool = True):
+    """radii, means2d, depths, conics, compensations of a dense projection, unwritten (`comps` off: an empty tensor)."""
+    return (torch.empty(Cn, N, dtype=torch.int32, device=dev), torch.empty(Cn, N, 2, device=dev),
+            torch.empty(Cn, N, device=dev), torch.empty(Cn, N, 3, device=dev),
+            torch.empty(Cn, N, device=dev) if comps else torch.empty(0, device=dev))
+
+
+def _or_zeros(v: Optional[Tensor], dev, *shape) -> Tensor:
+    """A cotangent nobody sent is zeros."""
+    return (v if v is not None else torch.zeros(*shape, device=dev)).contiguous()
+
+
+def _depth_comp_cotangents(v_depths, v_comps, lead, dev, fill_comps=True):
+    """(v_depths, v_comps) as the backward entries take them: a missing v_depths stays None (their NULL), a missing
+    v_comps is zeros (or, `fill_comps` off, None)."""
+    vcomp = _or_zeros(v_comps, dev, *lead) if (fill_comps or v_comps is not None) else None
+    return (v_depths.contiguous() if v_depths is not None else None), vcomp
+
+
+def _g2d_record(v_means2d, v_conics, lead, dev) -> Tensor:
+    """The [..., 8] record layout of the compositing backward (words 0-1 v_means2d, 4-6 v_conics) from two cotangents,
+    either of which may be missing (zeros).  The one place that knows the layout."""
+    z2 = torch.zeros(*lead, 2, device=dev)
+    vm2d = v_means2d if v_means2d is not None else z2
+    vcon = v_conics if v_conics is not None else torch.zeros(*lead, 3, device=dev)
+    return torch.cat([vm2d, z2, vcon, torch.zeros(*lead, 1, device=dev)], dim=-1).contiguous()
+
+
+def _pose_gradient(form: _Form, head, N, Cn, cfg, key, packed, g2d, vcomp, vdep) -> Tensor:
+    """``viewmats.grad`` [C, 4, 4] (csrc/viewmat_grad.hip: per-workgroup partials, then their sum) -- what a pose
+    optimiser pays for and nobody else.  Dense (`packed` None): the entry tells the layout by `key`, the record (quats +
+    scales) or the radii (covars), and without Gaussians there is none: zeros.  Packed: `packed` = (indptr, nnz,
+    gaussian_ids); always dense [C, 4, 4], with `sparse_grad` as well.  `g2d`: the cotangent record, or the pair
+    (v_means2d, v_conics) it is then built from."""
+    width, height, eps2d, flags = cfg
+    dev = head[0].device
+    if packed is None:
+        v_viewmats = torch.zeros(Cn, 4, 4, device=dev)
+        if N == 0:
+            return v_viewmats
+        rows, layout = N, (ptr(key), None, 0, None)
+    else:
+        indptr, nnz, gaussian_ids = packed
+        v_viewmats = torch.empty(Cn, 4, 4, device=dev)
+        rows, layout = min(nnz, N), (None, ptr(indptr), nnz, ptr(gaussian_ids))
+    blocks = math.ceil(rows / 256)
+    scratch = torch.empty(Cn, blocks, 12, device=dev)
+    if not isinstance(g2d, Tensor):  # (the dense covariance backward has no record of its own: it hands over (v_means2d, v_conics))
+        g2d = _g2d_record(*g2d, (Cn, N), dev)
+    call(form.entries["viewmats"], *map(ptr, head), N, Cn, width, height, eps2d, flags, *layout, ptr(g2d), ptr(vcomp),
+         ptr(vdep), ptr(scratch), blocks, ptr(v_viewmats), stream())
+    return v_viewmats
+
+
 class _Projection(torch.autograd.Function):
     """gsplat ``fully_fused_projection`` (packed=False) for C cameras, tile counting fused in (tile_size 16; any other
     tile size: the projection without its counting, then `count_tiles`).  `ortho`: EG_FLAG_ORTHO, the orthographic
-    instantiations of the same kernels, forward and backward."""
+    instantiations of the same kernels, forward and backward.  Output allocations, cotangent defaults, the cotangent
+    record and the pose gradient come from the helpers above, as `_CovarProjection`'s do."""
 
     @staticmethod
     def forward(ctx, means, quats, scales, opac_for_splat, viewmats, Ks, width, height, eps2d,
@@ -79,33 +179,29 @@ class _Projection(torch.autograd.Function):
         Cn, N = viewmats.shape[0], means.shape[0]
         dev = means.device
         tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
-        means_c, quats_c, scales_c = means.contiguous(), quats.contiguous(), scales.contiguous()
-        opac_c = opac_for_splat.contiguous()
-        vm, Kc = viewmats.contiguous(), Ks.contiguous()
+        means_c, shape = means.contiguous(), _QUAT_SCALE.kernel_inputs(quats, scales)
+        head = _QUAT_SCALE.head(means_c, shape, opac_for_splat.contiguous(), viewmats.contiguous(), Ks.contiguous())
         splat = torch.empty(Cn, N, 8, device=dev)
-        radii = torch.empty(Cn, N, dtype=torch.int32, device=dev)
-        means2d = torch.empty(Cn, N, 2, device=dev)
-        depths = torch.empty(Cn, N, device=dev)
-        conics = torch.empty(Cn, N, 3, device=dev)
-        comps = torch.empty(Cn, N, device=dev)
+        radii, means2d, depths, conics, comps = _dense_outputs(Cn, N, dev)
         tpg = torch.empty(Cn, N, dtype=torch.int32, device=dev)
         counts = torch.zeros(Cn, tw * th, dtype=torch.int32, device=dev)
         flags = (_lib.FLAG_ANTIALIASED if antialiased else 0) | (_lib.FLAG_ORTHO if ortho else 0)
-        # (round 6: the C cameras by ONE native call -- csrc/cams.hip loops over the per-camera launcher)
+        # (the C cameras by ONE native call -- csrc/cams.hip loops over the per-camera launcher)
         fused = tile_size == TILE  # (the counting fused into the projection kernel is the 16-pixel one)
-        call("eg_project_fwd_cams", ptr(means_c), ptr(quats_c), ptr(scales_c), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height,
+        call("eg_project_fwd_cams", *map(ptr, head), N, Cn, width, height,
              near_plane, far_plane, eps2d, radius_clip, flags, ptr(splat), ptr(radii), ptr(means2d), ptr(depths), ptr(conics),
              ptr(comps), ptr(tpg) if fused else None, ptr(counts) if fused else None, stream())
         if not fused:
             count_tiles(means2d, radii, [c * N for c in range(Cn + 1)], width, height, tile_size, tpg, counts)
-        ctx.save_for_backward(means_c, quats_c, scales_c, opac_c, vm, Kc, splat)
+        ctx.save_for_backward(*head, splat)
         ctx.cfg = (width, height, eps2d, flags)
         ctx.mark_non_differentiable(radii, tpg, counts, splat)
         return radii, means2d, depths, conics, comps, tpg, counts, splat
 
     @staticmethod
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, _a, _b, _c):
-        means, quats, scales, opac, vm, Kc, splat = ctx.saved_tensors
+        *head, splat = ctx.saved_tensors
+        means, vm = head[0], head[-2]
         width, height, eps2d, flags = ctx.cfg
         Cn, N = vm.shape[0], means.shape[0]
         dev = means.device
@@ -116,29 +212,17 @@ class _Projection(torch.autograd.Function):
                 and v_conics.storage_offset() == base.storage_offset() + 4):
             g2d = base  # both are views of the compositing backward's packed record: no re-pack
         else:
-            z2 = torch.zeros(Cn, N, 2, device=dev)
-            z1 = torch.zeros(Cn, N, 1, device=dev)
-            vm2d = v_means2d if v_means2d is not None else z2
-            vcon = v_conics if v_conics is not None else torch.zeros(Cn, N, 3, device=dev)
-            g2d = torch.cat([vm2d, z2, vcon, z1], dim=-1).contiguous()
-        vcomp = (v_comps if v_comps is not None else torch.zeros(Cn, N, device=dev)).contiguous()
-        vdep = v_depths.contiguous() if v_depths is not None else None
+            g2d = _g2d_record(v_means2d, v_conics, (Cn, N), dev)
+        vdep, vcomp = _depth_comp_cotangents(v_depths, v_comps, (Cn, N), dev)
         v_means = torch.empty(N, 3, device=dev)
         v_quats = torch.empty(N, 4, device=dev)
         v_scales = torch.empty(N, 3, device=dev)
         # (one native call: camera 0 writes, the others add -- EG_FLAG_GRAD_ACCUM -- in the order of the loop this replaces)
-        call("eg_project_bwd_cams", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d,
-             flags, ptr(splat), ptr(g2d), ptr(vcomp), ptr(vdep) if vdep is not None else None, ptr(v_means), ptr(v_quats),
-             ptr(v_scales), stream())
+        call("eg_project_bwd_cams", *map(ptr, head), N, Cn, width, height, eps2d,
+             flags, ptr(splat), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means), ptr(v_quats), ptr(v_scales), stream())
         v_viewmats = None
-        if ctx.needs_input_grad[4]:  # (a pose optimiser: nobody else pays for these two kernels)
-            v_viewmats = torch.zeros(Cn, 4, 4, device=dev)
-            if N > 0:  # (the entry tells the dense layout by its record, and without Gaussians there is none: zeros)
-                blocks = math.ceil(N / 256)
-                scratch = torch.empty(Cn, blocks, 12, device=dev)
-                call("eg_project_bwd_viewmats", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width,
-                     height, eps2d, flags, ptr(splat), None, 0, None, ptr(g2d), ptr(vcomp), ptr(vdep), ptr(scratch), blocks,
-                     ptr(v_viewmats), stream())
+        if ctx.needs_input_grad[_QUAT_SCALE.pose_slot]:
+            v_viewmats = _pose_gradient(_QUAT_SCALE, head, N, Cn, ctx.cfg, splat, None, g2d, vcomp, vdep)
         return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 10
 
 
@@ -157,277 +241,194 @@ def _ptr_or_dummy(t: Optional[Tensor]) -> Optional[int]:
     return _DUMMY[key].data_ptr()
 
 
+class _CovarProjection(torch.autograd.Function):
+    """`_Projection` from covariances, packed=False, for C cameras (csrc/functional.hip; the backward sums over the
+    cameras in camera order without atomics), in two roles.
+
+    ``rasterization(covars=[N, 3, 3])``: eg_project_covars_{fwd,bwd}_cams_flags and around them what the general path
+    needs: the record of the compositing kernels (built here: that entry writes none), the tile counts of the asked tile
+    size, ``covars.grad`` as [N, 3, 3] and, when ``viewmats`` requires grad, eg_project_covars_bwd_viewmats.  The
+    compensation and its cotangent are read only with `antialiased`.
+
+    `stage`: ``functional.fully_fused_projection(covars=[N, 6])`` -- the same projection, the same bits, with all of that
+    switched off: `covars` and its gradient are [N, 6], `opac_for_splat` is None, the last three outputs are None, and
+    `antialiased` is the stage's ``calc_compensations`` (off: an empty, non-differentiable ``comps`` and a NULL pointer;
+    a missing cotangent of it stays NULL).  A pinhole stage call takes the entries without flags,
+    eg_project_covars_{fwd,bwd}_cams."""
+
+    @staticmethod
+    def forward(ctx, means, covars, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
+                radius_clip, antialiased, tile_size=TILE, ortho=False, stage=False):
+        Cn, N = viewmats.shape[0], means.shape[0]
+        dev = means.device
+        shape = (covars.contiguous(),) if stage else _COVAR.kernel_inputs(covars)
+        head = _COVAR.head(means.contiguous(), shape, None, viewmats.contiguous(), Ks.contiguous())
+        have_comps = antialiased or not stage
+        radii, means2d, depths, conics, comps = _dense_outputs(Cn, N, dev, have_comps)
+        tpg = counts = splat = None
+        if not stage:
+            tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
+            tpg = torch.zeros(Cn, N, dtype=torch.int32, device=dev)
+            counts = torch.zeros(Cn, tw * th, dtype=torch.int32, device=dev)
+        flags = _lib.FLAG_ORTHO if ortho else 0
+        flagged = ortho or not stage
+        call("eg_project_covars_fwd_cams_flags" if flagged else "eg_project_covars_fwd_cams", *map(ptr, head), N, Cn, width,
+             height, near_plane, far_plane, eps2d, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics),
+             ptr(comps) if have_comps else None, *((flags,) if flagged else ()), stream())
+        if not stage:
+            # the record (x y a b c opacity[* compensation] depth radius) of the compositing kernels
+            o = opac_for_splat[None, :].expand(Cn, N)
+            splat = torch.cat([means2d, conics, (o * comps if antialiased else o)[..., None], depths[..., None],
+                               radii.view(torch.float32)[..., None]], dim=-1).contiguous()
+            if N > 0:
+                count_tiles(means2d, radii, [c * N for c in range(Cn + 1)], width, height, tile_size, tpg, counts)
+        ctx.save_for_backward(*head, radii)
+        ctx.cfg = (width, height, eps2d, flags, bool(antialiased), flagged, stage)
+        if stage:
+            ctx.mark_non_differentiable(*((radii,) if have_comps else (radii, comps)))
+        else:
+            ctx.mark_non_differentiable(radii, tpg, counts, splat)
+        return radii, means2d, depths, conics, comps, tpg, counts, splat
+
+    @staticmethod
+    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, _a, _b, _c):
+        *head, radii = ctx.saved_tensors
+        means, vm = head[0], head[-2]
+        width, height, eps2d, flags, antialiased, flagged, stage = ctx.cfg
+        Cn, N = vm.shape[0], means.shape[0]
+        dev = means.device
+        vm2d, vcon = _or_zeros(v_means2d, dev, Cn, N, 2), _or_zeros(v_conics, dev, Cn, N, 3)
+        vdep, vcomp = _depth_comp_cotangents(v_depths, v_comps if antialiased else None, (Cn, N), dev,
+                                             fill_comps=antialiased and not stage)
+        v_means = torch.empty(N, 3, device=dev)
+        v_cv = torch.empty(N, 6, device=dev)
+        call("eg_project_covars_bwd_cams_flags" if flagged else "eg_project_covars_bwd_cams", *map(ptr, head), N, Cn, width,
+             height, eps2d, ptr(radii), ptr(vm2d), ptr(vdep), ptr(vcon), ptr(vcomp), ptr(v_means), ptr(v_cv),
+             *((flags,) if flagged else ()), stream())
+        v_viewmats = None
+        if ctx.needs_input_grad[_COVAR.pose_slot]:
+            cfg = (width, height, eps2d, flags | (_lib.FLAG_ANTIALIASED if antialiased else 0))
+            v_viewmats = _pose_gradient(_COVAR, head, N, Cn, cfg, radii, None, (vm2d, vcon), vcomp, vdep)
+        return (v_means, v_cv if stage else _COVAR.returned(v_cv), None, v_viewmats) + (None,) * 11
+
+
+def _packed_forward(form: _Form, ctx, means, shape, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane,
+                    far_plane, radius_clip, antialiased, sparse_grad, holder, tile_size=TILE, ortho=False):
+    """The forward of `_PackedProjection` / `_PackedCovarProjection`; `shape`: the caller's shape tensors."""
+    Cn, N = viewmats.shape[0], means.shape[0]
+    dev = means.device
+    tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
+    means_c, shape, opac_c = means.contiguous(), form.kernel_inputs(*shape), opac_for_splat.contiguous()
+    vm, Kc = viewmats.contiguous(), Ks.contiguous()
+    head = form.head(means_c, shape, opac_c, vm, Kc)
+    flags = (_lib.FLAG_ANTIALIASED if antialiased else 0) | (_lib.FLAG_ORTHO if ortho else 0)
+    # the only scratch: one int32 per workgroup of 256 pairs
+    block_base = torch.empty(Cn * math.ceil(N / 256), dtype=torch.int32, device=dev)
+    indptr = torch.empty(Cn + 1, dtype=torch.int64, device=dev)
+    cull = (N, Cn, width, height, near_plane, far_plane, eps2d, radius_clip, flags, ptr(block_base))
+    call(form.entries["count"], *map(ptr, head), *cull, ptr(indptr), stream())
+    indptr_host = indptr.tolist()  # the first of the call's two read-backs (the second: the M_c of the binning)
+    nnz = indptr_host[-1]
+    if nnz >= 2 ** 31:
+        raise RuntimeError(f"rasterization(packed=True): {nnz} visible (camera, Gaussian) pairs; the limit is 2^31 - 1")
+    i32 = dict(dtype=torch.int32, device=dev)
+    splat = torch.empty(nnz, 8, device=dev)
+    radii = torch.empty(nnz, **i32)
+    means2d = torch.empty(nnz, 2, device=dev)
+    depths = torch.empty(nnz, device=dev)
+    conics = torch.empty(nnz, 3, device=dev)
+    comps = torch.empty(nnz, device=dev)
+    tpg = torch.empty(nnz, **i32)
+    camera_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
+    gaussian_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
+    counts = torch.zeros(Cn, tw * th, **i32)
+    counts16 = counts if tile_size == TILE else torch.zeros(Cn, math.ceil(width / TILE) * math.ceil(height / TILE), **i32)
+    call(form.entries["write"], *map(ptr, form.head(means_c, shape, opac_c, vm, Kc, write=True)), *cull, nnz, ptr(splat),
+         ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps), ptr(tpg), ptr(camera_ids), ptr(gaussian_ids),
+         ptr(counts16), stream())
+    if tile_size != TILE:  # (tiles_per_gauss is written again, for this tile size)
+        count_tiles(means2d, radii, indptr_host, width, height, tile_size, tpg, counts)
+    holder["indptr"] = indptr_host
+    ctx.save_for_backward(*head, indptr, camera_ids, gaussian_ids)
+    ctx.cfg = (width, height, eps2d, flags, bool(sparse_grad))
+    ctx.mark_non_differentiable(radii, tpg, counts, splat, camera_ids, gaussian_ids)
+    return radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids
+
+
+def _packed_backward(form: _Form, ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, *_rest):
+    """The backward of `_PackedProjection` / `_PackedCovarProjection`: (v_means, one gradient per shape tensor, None for
+    the opacities, v_viewmats) and a None per remaining input."""
+    *head, indptr, camera_ids, gaussian_ids = ctx.saved_tensors
+    means, vm = head[0], head[-2]
+    width, height, eps2d, flags, sparse_grad = ctx.cfg
+    Cn, N, nnz = vm.shape[0], means.shape[0], gaussian_ids.shape[0]
+    dev = means.device
+    g2d = _g2d_record(v_means2d, v_conics, (nnz,), dev)
+    vdep, vcomp = _depth_comp_cotangents(v_depths, v_comps, (nnz,), dev)
+    rows = nnz if sparse_grad else N
+    v_means = torch.empty(rows, 3, device=dev)
+    v_shape = [torch.empty(rows, w, device=dev) for w in form.widths]
+    dims = (N, Cn, width, height, eps2d, flags)
+    if sparse_grad:
+        call(form.entries["bwd_sparse"], *map(ptr, head), *dims, nnz, ptr(camera_ids), ptr(gaussian_ids), ptr(g2d),
+             ptr(vcomp), ptr(vdep), ptr(v_means), *map(ptr, v_shape), stream())
+        idx = gaussian_ids[None]
+        grads = tuple(torch.sparse_coo_tensor(idx, v, size=(N, *v.shape[1:]), is_coalesced=(Cn == 1))
+                      for v in itertools.chain((v_means,), map(form.returned, v_shape)))
+        # (a second owner: torch's AccumulateGrad rebuilds a sparse gradient it owns alone from its indices and
+        # values and loses the coalesced mark on the way; one it shares is cloned, mark included)
+        ctx.sparse_grads = grads
+    else:
+        call(form.entries["bwd"], *map(ptr, head), *dims, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d), ptr(vcomp),
+             ptr(vdep), ptr(v_means), *map(ptr, v_shape), stream())
+        grads = (v_means, *map(form.returned, v_shape))
+    v_viewmats = None
+    if ctx.needs_input_grad[form.pose_slot]:
+        v_viewmats = _pose_gradient(form, head, N, Cn, ctx.cfg[:4], None, (indptr, nnz, gaussian_ids), g2d, vcomp, vdep)
+    return (*grads, None, v_viewmats) + (None,) * 12
+
+
 class _PackedProjection(torch.autograd.Function):
     """gsplat ``fully_fused_projection`` (packed=True) for C cameras (csrc/packed.hip): only the pairs (camera, Gaussian)
     that survive every cull, in ascending order of camera * N + Gaussian.  Forward: eg_packed_count, ONE host read-back
     (indptr, hence nnz: the synchronisation gsplat has there too), eg_packed_write.  Backward: eg_packed_bwd (dense
     [N, k] gradients, summed over the cameras in camera order, no atomics) or, with `sparse_grad`, eg_packed_bwd_sparse
-    (sparse COO gradients of size [N, k] with indices gaussian_ids[None] and values [nnz, k], coalesced iff C == 1).
-    `holder` receives the host copy of indptr.  A `tile_size` other than 16: eg_packed_write counts 16-pixel tiles into
-    a throw-away buffer, and eg_tile_count_ts counts the pairs' tiles of the asked size.  `ortho`: EG_FLAG_ORTHO in every
-    call, forward and backward."""
+    (sparse COO gradients of size [N, k] with indices gaussian_ids[None] and values [nnz, k], coalesced iff C == 1);
+    ``viewmats`` through eg_project_bwd_viewmats.  `holder` receives the host copy of indptr.  A `tile_size` other than
+    16: eg_packed_write counts 16-pixel tiles into a throw-away buffer, and eg_tile_count_ts counts the pairs' tiles of
+    the asked size.  `ortho`: EG_FLAG_ORTHO in every call, forward and backward.  A shell: `_packed_forward` and
+    `_packed_backward` under the quats + scales form."""
 
     @staticmethod
-    def forward(ctx, means, quats, scales, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-                radius_clip, antialiased, sparse_grad, holder, tile_size=TILE, ortho=False):
-        Cn, N = viewmats.shape[0], means.shape[0]
-        dev = means.device
-        tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
-        means_c, quats_c, scales_c = means.contiguous(), quats.contiguous(), scales.contiguous()
-        opac_c = opac_for_splat.contiguous()
-        vm, Kc = viewmats.contiguous(), Ks.contiguous()
-        flags = (_lib.FLAG_ANTIALIASED if antialiased else 0) | (_lib.FLAG_ORTHO if ortho else 0)
-        # the only scratch: one int32 per workgroup of 256 pairs
-        block_base = torch.empty(Cn * math.ceil(N / 256), dtype=torch.int32, device=dev)
-        indptr = torch.empty(Cn + 1, dtype=torch.int64, device=dev)
-        call("eg_packed_count", ptr(means_c), ptr(quats_c), ptr(scales_c), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height,
-             near_plane, far_plane, eps2d, radius_clip, flags, ptr(block_base), ptr(indptr), stream())
-        indptr_host = indptr.tolist()  # the first of the call's two read-backs (the second: the M_c of the binning)
-        nnz = indptr_host[-1]
-        if nnz >= 2 ** 31:
-            raise RuntimeError(f"rasterization(packed=True): {nnz} visible (camera, Gaussian) pairs; the limit is 2^31 - 1")
-        i32 = dict(dtype=torch.int32, device=dev)
-        splat = torch.empty(nnz, 8, device=dev)
-        radii = torch.empty(nnz, **i32)
-        means2d = torch.empty(nnz, 2, device=dev)
-        depths = torch.empty(nnz, device=dev)
-        conics = torch.empty(nnz, 3, device=dev)
-        comps = torch.empty(nnz, device=dev)
-        tpg = torch.empty(nnz, **i32)
-        camera_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
-        gaussian_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
-        counts = torch.zeros(Cn, tw * th, **i32)
-        counts16 = counts if tile_size == TILE else torch.zeros(Cn, math.ceil(width / TILE) * math.ceil(height / TILE), **i32)
-        call("eg_packed_write", ptr(means_c), ptr(quats_c), ptr(scales_c), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height,
-             near_plane, far_plane, eps2d, radius_clip, flags, ptr(block_base), nnz, ptr(splat), ptr(radii), ptr(means2d),
-             ptr(depths), ptr(conics), ptr(comps), ptr(tpg), ptr(camera_ids), ptr(gaussian_ids), ptr(counts16), stream())
-        if tile_size != TILE:  # (tiles_per_gauss is written again, for this tile size)
-            count_tiles(means2d, radii, indptr_host, width, height, tile_size, tpg, counts)
-        holder["indptr"] = indptr_host
-        ctx.save_for_backward(means_c, quats_c, scales_c, opac_c, vm, Kc, indptr, camera_ids, gaussian_ids)
-        ctx.cfg = (width, height, eps2d, flags, bool(sparse_grad))
-        ctx.mark_non_differentiable(radii, tpg, counts, splat, camera_ids, gaussian_ids)
-        return radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids
+    def forward(ctx, means, quats, scales, *rest):
+        return _packed_forward(_QUAT_SCALE, ctx, means, (quats, scales), *rest)
 
     @staticmethod
-    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, *_rest):
-        means, quats, scales, opac, vm, Kc, indptr, camera_ids, gaussian_ids = ctx.saved_tensors
-        width, height, eps2d, flags, sparse_grad = ctx.cfg
-        Cn, N, nnz = vm.shape[0], means.shape[0], gaussian_ids.shape[0]
-        dev = means.device
-        z2 = torch.zeros(nnz, 2, device=dev)
-        z1 = torch.zeros(nnz, 1, device=dev)
-        vm2d = v_means2d if v_means2d is not None else z2
-        vcon = v_conics if v_conics is not None else torch.zeros(nnz, 3, device=dev)
-        g2d = torch.cat([vm2d, z2, vcon, z1], dim=-1).contiguous()  # the [nnz, 8] record layout of the compositing backward
-        vcomp = (v_comps if v_comps is not None else torch.zeros(nnz, device=dev)).contiguous()
-        vdep = v_depths.contiguous() if v_depths is not None else None
-        rows = nnz if sparse_grad else N
-        v_means = torch.empty(rows, 3, device=dev)
-        v_quats = torch.empty(rows, 4, device=dev)
-        v_scales = torch.empty(rows, 3, device=dev)
-        if sparse_grad:
-            call("eg_packed_bwd_sparse", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width, height,
-                 eps2d, flags, nnz, ptr(camera_ids), ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means),
-                 ptr(v_quats), ptr(v_scales), stream())
-            idx = gaussian_ids[None]
-            v_means, v_quats, v_scales = (
-                torch.sparse_coo_tensor(idx, v, size=(N, v.shape[1]), is_coalesced=(Cn == 1))
-                for v in (v_means, v_quats, v_scales))
-            # (a second owner: torch's AccumulateGrad rebuilds a sparse gradient it owns alone from its indices and
-            # values and loses the coalesced mark on the way; one it shares is cloned, mark included)
-            ctx.sparse_grads = (v_means, v_quats, v_scales)
-        else:
-            call("eg_packed_bwd", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d,
-                 flags, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means), ptr(v_quats),
-                 ptr(v_scales), stream())
-        v_viewmats = None
-        if ctx.needs_input_grad[4]:  # (always dense [C, 4, 4], with `sparse_grad` as well)
-            blocks = math.ceil(min(nnz, N) / 256)
-            scratch = torch.empty(Cn, blocks, 12, device=dev)
-            v_viewmats = torch.empty(Cn, 4, 4, device=dev)
-            call("eg_project_bwd_viewmats", ptr(means), ptr(quats), ptr(scales), ptr(opac), ptr(vm), ptr(Kc), N, Cn, width,
-                 height, eps2d, flags, None, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d),
-                 ptr(vcomp), ptr(vdep), ptr(scratch), blocks, ptr(v_viewmats), stream())
-        return (v_means, v_quats, v_scales, None, v_viewmats) + (None,) * 12
-
-
-_TRIU = (0, 1, 2, 4, 5, 8)  # the upper triangle (00, 01, 02, 11, 12, 22) inside a row-major 3 x 3 block
-
-
-def _covars6(covars: Tensor) -> Tensor:
-    """[N, 3, 3] -> the [N, 6] upper triangle the kernels take (only the entries i <= j are read)."""
-    return covars.reshape(covars.shape[0], 9)[:, _TRIU].contiguous()
-
-
-def _covars_grad33(v6: Tensor) -> Tensor:
-    """The kernels' [rows, 6] gradient (an off-diagonal entry carries both symmetric cotangents) scattered to the upper
-    triangle of [rows, 3, 3], zeros below the diagonal: what autograd gives through ``sym_from6(covars[:, iu, ju])``."""
-    out = torch.zeros(v6.shape[0], 9, device=v6.device)
-    out[:, _TRIU] = v6
-    return out.view(-1, 3, 3)
-
-
-def _g2d_record(v_means2d, v_conics, lead, dev) -> Tensor:
-    """The [..., 8] record layout of the compositing backward (words 0-1 v_means2d, 4-6 v_conics) from two cotangents."""
-    z2 = torch.zeros(*lead, 2, device=dev)
-    vm2d = v_means2d if v_means2d is not None else z2
-    vcon = v_conics if v_conics is not None else torch.zeros(*lead, 3, device=dev)
-    return torch.cat([vm2d, z2, vcon, torch.zeros(*lead, 1, device=dev)], dim=-1).contiguous()
-
-
-class _CovarProjection(torch.autograd.Function):
-    """`_Projection` from covariances [N, 3, 3] (gsplat ``rasterization(covars=...)``, packed=False): the projection of
-    ``functional.fully_fused_projection(covars=[N, 6])`` -- eg_project_covars_{fwd,bwd}_cams_flags, the same bits -- and
-    around it what the general path needs: the record of the compositing kernels (built here: that entry writes none),
-    the tile counts of the asked tile size, and, when ``viewmats`` requires grad, eg_project_covars_bwd_viewmats.  The
-    compensation and its cotangent are read only with `antialiased`."""
-
-    @staticmethod
-    def forward(ctx, means, covars, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-                radius_clip, antialiased, tile_size=TILE, ortho=False):
-        Cn, N = viewmats.shape[0], means.shape[0]
-        dev = means.device
-        tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
-        means_c, cv, vm, Kc = means.contiguous(), _covars6(covars), viewmats.contiguous(), Ks.contiguous()
-        radii = torch.empty(Cn, N, dtype=torch.int32, device=dev)
-        means2d = torch.empty(Cn, N, 2, device=dev)
-        depths = torch.empty(Cn, N, device=dev)
-        conics = torch.empty(Cn, N, 3, device=dev)
-        comps = torch.empty(Cn, N, device=dev)
-        tpg = torch.zeros(Cn, N, dtype=torch.int32, device=dev)
-        counts = torch.zeros(Cn, tw * th, dtype=torch.int32, device=dev)
-        flags = _lib.FLAG_ORTHO if ortho else 0
-        call("eg_project_covars_fwd_cams_flags", ptr(means_c), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane,
-             far_plane, eps2d, radius_clip, ptr(radii), ptr(means2d), ptr(depths), ptr(conics), ptr(comps), flags, stream())
-        # the record (x y a b c opacity[* compensation] depth radius) of the compositing kernels
-        o = opac_for_splat[None, :].expand(Cn, N)
-        splat = torch.cat([means2d, conics, (o * comps if antialiased else o)[..., None], depths[..., None],
-                           radii.view(torch.float32)[..., None]], dim=-1).contiguous()
-        if N > 0:
-            count_tiles(means2d, radii, [c * N for c in range(Cn + 1)], width, height, tile_size, tpg, counts)
-        ctx.save_for_backward(means_c, cv, vm, Kc, radii)
-        ctx.cfg = (width, height, eps2d, flags, bool(antialiased))
-        ctx.mark_non_differentiable(radii, tpg, counts, splat)
-        return radii, means2d, depths, conics, comps, tpg, counts, splat
-
-    @staticmethod
-    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, _a, _b, _c):
-        means, cv, vm, Kc, radii = ctx.saved_tensors
-        width, height, eps2d, flags, antialiased = ctx.cfg
-        Cn, N = vm.shape[0], means.shape[0]
-        dev = means.device
-        vm2d = v_means2d.contiguous() if v_means2d is not None else torch.zeros(Cn, N, 2, device=dev)
-        vcon = v_conics.contiguous() if v_conics is not None else torch.zeros(Cn, N, 3, device=dev)
-        vdep = v_depths.contiguous() if v_depths is not None else None
-        vcomp = None
-        if antialiased:
-            vcomp = (v_comps if v_comps is not None else torch.zeros(Cn, N, device=dev)).contiguous()
-        v_means = torch.empty(N, 3, device=dev)
-        v_cv = torch.empty(N, 6, device=dev)
-        call("eg_project_covars_bwd_cams_flags", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, ptr(radii),
-             ptr(vm2d), ptr(vdep), ptr(vcon), ptr(vcomp), ptr(v_means), ptr(v_cv), flags, stream())
-        v_viewmats = None
-        if ctx.needs_input_grad[3]:  # (a pose optimiser: nobody else pays for these two kernels)
-            v_viewmats = torch.zeros(Cn, 4, 4, device=dev)
-            if N > 0:  # (the entry tells the dense layout by its radii, and without Gaussians there are none: zeros)
-                blocks = math.ceil(N / 256)
-                scratch = torch.empty(Cn, blocks, 12, device=dev)
-                g2d = _g2d_record(vm2d, vcon, (Cn, N), dev)
-                call("eg_project_covars_bwd_viewmats", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d,
-                     flags | (_lib.FLAG_ANTIALIASED if antialiased else 0), ptr(radii), None, 0, None, ptr(g2d), ptr(vcomp),
-                     ptr(vdep), ptr(scratch), blocks, ptr(v_viewmats), stream())
-        return (v_means, _covars_grad33(v_cv), None, v_viewmats) + (None,) * 10
+    def backward(ctx, *cotangents):
+        return _packed_backward(_QUAT_SCALE, ctx, *cotangents)
 
 
 class _PackedCovarProjection(torch.autograd.Function):
-    """`_PackedProjection` from covariances [N, 3, 3] (csrc/packed.hip, the eg_packed_*_covars entries): the same outputs,
-    read-back and `holder`.  Backward: eg_packed_bwd_covars (dense ``means.grad`` [N, 3], ``covars.grad`` [N, 3, 3]) or,
-    with `sparse_grad`, eg_packed_bwd_sparse_covars (sparse COO gradients with indices gaussian_ids[None] and values
-    [nnz, 3] / [nnz, 3, 3], coalesced iff C == 1); ``viewmats`` through eg_project_covars_bwd_viewmats."""
+    """`_PackedProjection` from covariances [N, 3, 3]: the same bodies under the covariance form (the
+    eg_packed_*_covars entries, eg_project_covars_bwd_viewmats), the same outputs, read-back and `holder`.  The gradients
+    are ``means.grad`` [N, 3] and ``covars.grad`` [N, 3, 3] or, with `sparse_grad`, sparse COO tensors with indices
+    gaussian_ids[None] and values [nnz, 3] / [nnz, 3, 3], coalesced iff C == 1."""
 
     @staticmethod
-    def forward(ctx, means, covars, opac_for_splat, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
-                radius_clip, antialiased, sparse_grad, holder, tile_size=TILE, ortho=False):
-        Cn, N = viewmats.shape[0], means.shape[0]
-        dev = means.device
-        tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
-        means_c, cv, opac_c = means.contiguous(), _covars6(covars), opac_for_splat.contiguous()
-        vm, Kc = viewmats.contiguous(), Ks.contiguous()
-        flags = (_lib.FLAG_ANTIALIASED if antialiased else 0) | (_lib.FLAG_ORTHO if ortho else 0)
-        block_base = torch.empty(Cn * math.ceil(N / 256), dtype=torch.int32, device=dev)
-        indptr = torch.empty(Cn + 1, dtype=torch.int64, device=dev)
-        call("eg_packed_count_covars", ptr(means_c), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane, far_plane,
-             eps2d, radius_clip, flags, ptr(block_base), ptr(indptr), stream())
-        indptr_host = indptr.tolist()  # the first of the call's two read-backs (the second: the M_c of the binning)
-        nnz = indptr_host[-1]
-        if nnz >= 2 ** 31:
-            raise RuntimeError(f"rasterization(packed=True): {nnz} visible (camera, Gaussian) pairs; the limit is 2^31 - 1")
-        i32 = dict(dtype=torch.int32, device=dev)
-        splat = torch.empty(nnz, 8, device=dev)
-        radii = torch.empty(nnz, **i32)
-        means2d = torch.empty(nnz, 2, device=dev)
-        depths = torch.empty(nnz, device=dev)
-        conics = torch.empty(nnz, 3, device=dev)
-        comps = torch.empty(nnz, device=dev)
-        tpg = torch.empty(nnz, **i32)
-        camera_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
-        gaussian_ids = torch.empty(nnz, dtype=torch.int64, device=dev)
-        counts = torch.zeros(Cn, tw * th, **i32)
-        counts16 = counts if tile_size == TILE else torch.zeros(Cn, math.ceil(width / TILE) * math.ceil(height / TILE), **i32)
-        call("eg_packed_write_covars", ptr(means_c), ptr(cv), ptr(opac_c), ptr(vm), ptr(Kc), N, Cn, width, height, near_plane,
-             far_plane, eps2d, radius_clip, flags, ptr(block_base), nnz, ptr(splat), ptr(radii), ptr(means2d), ptr(depths),
-             ptr(conics), ptr(comps), ptr(tpg), ptr(camera_ids), ptr(gaussian_ids), ptr(counts16), stream())
-        if tile_size != TILE:  # (tiles_per_gauss is written again, for this tile size)
-            count_tiles(means2d, radii, indptr_host, width, height, tile_size, tpg, counts)
-        holder["indptr"] = indptr_host
-        ctx.save_for_backward(means_c, cv, vm, Kc, indptr, camera_ids, gaussian_ids)
-        ctx.cfg = (width, height, eps2d, flags, bool(sparse_grad))
-        ctx.mark_non_differentiable(radii, tpg, counts, splat, camera_ids, gaussian_ids)
-        return radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids
+    def forward(ctx, means, covars, *rest):
+        return _packed_forward(_COVAR, ctx, means, (covars,), *rest)
 
     @staticmethod
-    def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps, *_rest):
-        means, cv, vm, Kc, indptr, camera_ids, gaussian_ids = ctx.saved_tensors
-        width, height, eps2d, flags, sparse_grad = ctx.cfg
-        Cn, N, nnz = vm.shape[0], means.shape[0], gaussian_ids.shape[0]
-        dev = means.device
-        g2d = _g2d_record(v_means2d, v_conics, (nnz,), dev)
-        vcomp = (v_comps if v_comps is not None else torch.zeros(nnz, device=dev)).contiguous()
-        vdep = v_depths.contiguous() if v_depths is not None else None
-        rows = nnz if sparse_grad else N
-        v_means = torch.empty(rows, 3, device=dev)
-        v_cv = torch.empty(rows, 6, device=dev)
-        if sparse_grad:
-            call("eg_packed_bwd_sparse_covars", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, flags, nnz,
-                 ptr(camera_ids), ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means), ptr(v_cv), stream())
-            idx = gaussian_ids[None]
-            v_means = torch.sparse_coo_tensor(idx, v_means, size=(N, 3), is_coalesced=(Cn == 1))
-            v_covars = torch.sparse_coo_tensor(idx, _covars_grad33(v_cv), size=(N, 3, 3), is_coalesced=(Cn == 1))
-            ctx.sparse_grads = (v_means, v_covars)  # (a second owner: see _PackedProjection.backward)
-        else:
-            call("eg_packed_bwd_covars", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, flags, ptr(indptr),
-                 nnz, ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(v_means), ptr(v_cv), stream())
-            v_covars = _covars_grad33(v_cv)
-        v_viewmats = None
-        if ctx.needs_input_grad[3]:  # (always dense [C, 4, 4], with `sparse_grad` as well)
-            blocks = math.ceil(min(nnz, N) / 256)
-            scratch = torch.empty(Cn, blocks, 12, device=dev)
-            v_viewmats = torch.empty(Cn, 4, 4, device=dev)
-            call("eg_project_covars_bwd_viewmats", ptr(means), ptr(cv), ptr(vm), ptr(Kc), N, Cn, width, height, eps2d, flags,
-                 None, ptr(indptr), nnz, ptr(gaussian_ids), ptr(g2d), ptr(vcomp), ptr(vdep), ptr(scratch), blocks,
-                 ptr(v_viewmats), stream())
-        return (v_means, v_covars, None, v_viewmats) + (None,) * 12
+    def backward(ctx, *cotangents):
+        return _packed_backward(_COVAR, ctx, *cotangents)
 
 
 def _dense_projection(means, quats, scales, covars, opacities, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
                       radius_clip, antialiased, tile_size, ortho):
     """The projection node of the general path: `_Projection`, or with ``covars`` `_CovarProjection` (same outputs)."""
-    if covars is None:
-        return _Projection.apply(means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
-                                 float(near_plane), float(far_plane), float(radius_clip), antialiased, tile_size, ortho)
-    return _CovarProjection.apply(means, covars, opacities.detach(), viewmats, Ks, width, height, float(eps2d),
-                                  float(near_plane), float(far_plane), float(radius_clip), antialiased, tile_size, ortho)
+    shape, node = ((quats, scales), _Projection) if covars is None else ((covars,), _CovarProjection)
+    return node.apply(means, *shape, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
+                      float(far_plane), float(radius_clip), antialiased, tile_size, ortho)
 
 
 class _Compositing(torch.autograd.Function):
@@ -1130,6 +1131,19 @@ def bin_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, ranges, counts: Te
 RENDER_MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
 
 
+def _info(radii, means2d, depths, conics, opac, tpg, b: Binning, last_ids, width, height, tile_size, Cn,
+          camera_ids=None, gaussian_ids=None) -> Dict:
+    """gsplat's ``info`` of a general-path call (the ids: None unless packed)."""
+    return {
+        "camera_ids": camera_ids, "gaussian_ids": gaussian_ids,
+        "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
+        "tile_width": math.ceil(width / tile_size), "tile_height": math.ceil(height / tile_size), "tiles_per_gauss": tpg,
+        **b.info,
+        "width": width, "height": height, "tile_size": tile_size, "n_cameras": Cn,
+        "last_ids": last_ids,
+    }
+
+
 def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
                         radius_clip, eps2d, backgrounds, render_mode, absgrad, antialiased, sh_degree=None, chunk=None,
                         tile_size=TILE, ortho=False, covars=None):
@@ -1154,7 +1168,6 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
     opac = opacities[None, :].expand(Cn, N)
     if antialiased:
         opac = opac * comps
-    tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
     with torch.no_grad():
         b = bin_tiles(means2d.contiguous(), radii, depths.contiguous(), [c * N for c in range(Cn + 1)], counts, width,
                       height, tile_size, packed=False)
@@ -1168,15 +1181,7 @@ def _mode_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, w
             bool(absgrad), _splat, depth)
     if render_mode in ("ED", "RGB+ED"):
         render = torch.cat([render[..., :-1], render[..., -1:] / alphas.clamp(min=1e-10)], dim=-1)
-    info = {
-        "camera_ids": None, "gaussian_ids": None,
-        "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
-        "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
-        **b.info,
-        "width": width, "height": height, "tile_size": tile_size, "n_cameras": Cn,
-        "last_ids": last_ids,
-    }
-    return render, alphas, info
+    return render, alphas, _info(radii, means2d, depths, conics, opac, tpg, b, last_ids, width, height, tile_size, Cn)
 
 
 def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane, far_plane,
@@ -1195,14 +1200,10 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
     if render_mode in ("D", "ED"):
         colors, backgrounds = None, None  # (gsplat: the depth is the only channel, its background is 0)
     holder: Dict = {}
-    if covars is None:
-        radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids = _PackedProjection.apply(
-            means, quats, scales, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
-            float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder, tile_size, ortho)
-    else:
-        radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids = _PackedCovarProjection.apply(
-            means, covars, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
-            float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder, tile_size, ortho)
+    shape, node = ((quats, scales), _PackedProjection) if covars is None else ((covars,), _PackedCovarProjection)
+    radii, means2d, depths, conics, comps, tpg, counts, splat, camera_ids, gaussian_ids = node.apply(
+        means, *shape, opacities.detach(), viewmats, Ks, width, height, float(eps2d), float(near_plane),
+        float(far_plane), float(radius_clip), antialiased, bool(sparse_grad), holder, tile_size, ortho)
     indptr = holder["indptr"]
     nnz = indptr[-1]
     if colors is not None:
@@ -1220,7 +1221,6 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
     opac = opacities[gaussian_ids]
     if antialiased:
         opac = opac * comps
-    tw, th = math.ceil(width / tile_size), math.ceil(height / tile_size)
     with torch.no_grad():  # (the second and last read-back of the call)
         b = bin_tiles(means2d, radii, depths, indptr, counts, width, height, tile_size, packed=True)
     if colors is not None and backgrounds is None and not depth and chunk is None:
@@ -1237,15 +1237,8 @@ def _packed_rasterization(means, quats, scales, opacities, colors, viewmats, Ks,
             bool(absgrad), splat, depth, Cn)
     if render_mode in ("ED", "RGB+ED"):
         render = torch.cat([render[..., :-1], render[..., -1:] / alphas.clamp(min=1e-10)], dim=-1)
-    info = {
-        "camera_ids": camera_ids, "gaussian_ids": gaussian_ids,
-        "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
-        "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
-        **b.info,
-        "width": width, "height": height, "tile_size": tile_size, "n_cameras": Cn,
-        "last_ids": last_ids,
-    }
-    return render, alphas, info
+    return render, alphas, _info(radii, means2d, depths, conics, opac, tpg, b, last_ids, width, height, tile_size, Cn,
+                                 camera_ids, gaussian_ids)
 
 
 def rasterization(
@@ -1426,7 +1419,6 @@ def rasterization(
     if antialiased:
         opac = opac * comps
 
-    tw, th = math.ceil(width / TILE), math.ceil(height / TILE)
     # the reference always passes torch.ones(N,3) without grad (edge_gs.py:247, a fresh tensor every step): decide
     # "unit colours" on the device and read the verdict back with M (the one host sync gsplat also has)
     # (never with `covars`: that call takes the general compositing kernels whatever its colours are)
@@ -1440,13 +1432,4 @@ def rasterization(
     render, alphas, last_ids = _Compositing.apply(
         means2d, conics, colors, opac.contiguous(), width, height, tuple(b.offsets), b.camera_lists(), bool(absgrad),
         unit, tuple(b.item_offsets), tuple(b.total), tuple(b.n_items), _splat)
-
-    info = {
-        "camera_ids": None, "gaussian_ids": None,
-        "radii": radii, "means2d": means2d, "depths": depths, "conics": conics, "opacities": opac,
-        "tile_width": tw, "tile_height": th, "tiles_per_gauss": tpg,
-        **b.info,
-        "width": width, "height": height, "tile_size": tile_size, "n_cameras": Cn,
-        "last_ids": last_ids,
-    }
-    return render, alphas, info
+    return render, alphas, _info(radii, means2d, depths, conics, opac, tpg, b, last_ids, width, height, tile_size, Cn)

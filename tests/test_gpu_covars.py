@@ -583,3 +583,78 @@ def test_a_call_without_covars_is_the_call_it_was(env, packed, monkeypatch):
     assert ("eg_packed_count_covars" if packed else "eg_project_covars_fwd_cams_flags") in seen, seen
     assert r_c.shape == (1, 52, 70, 3) and float(a_c.mean()) > 0.05
     assert rel_err(r_c.cpu(), a_c.expand(1, 52, 70, 3).cpu()) <= 1e-5   # (unit colours: the image is the alpha)
+
+
+# ---------------------------------------------------------------------------------------------------
+def _single_cotangent_scene():
+    """200 Gaussians in a unit box, 70 x 52, two cameras looking down +z from 3 and from 5 units: far_plane = 5 culls
+    about half of the rows of the second camera and none of the first."""
+    g = torch.Generator().manual_seed(67)
+    N = 200
+    means = torch.rand(N, 3, generator=g) - 0.5
+    quats = torch.nn.functional.normalize(torch.randn(N, 4, generator=g), dim=-1)
+    scales = 0.03 + 0.05 * torch.rand(N, 3, generator=g)
+    w, x, y, z = quats.unbind(-1)
+    rot = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                       2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                       2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=-1).reshape(N, 3, 3)
+    covars = rot @ torch.diag_embed(scales ** 2) @ rot.transpose(1, 2)
+    covars = 0.5 * (covars + covars.transpose(1, 2))
+    vms = torch.eye(4).repeat(2, 1, 1)
+    vms[0, 2, 3], vms[1, 2, 3] = 3.0, 5.0
+    Ks = torch.tensor([[60.0, 0.0, 35.0], [0.0, 60.0, 26.0], [0.0, 0.0, 1.0]]).repeat(2, 1, 1)
+    opac = 0.1 + 0.8 * torch.rand(N, generator=g)
+    w8 = dict(means2d=torch.randn(2, N, 2, generator=g), depths=torch.randn(2, N, generator=g),
+              conics=torch.randn(2, N, 3, generator=g), comps=torch.randn(2, N, generator=g))
+    return dict(means=means, quats=quats, scales=scales, covars=covars, vms=vms, Ks=Ks, opac=opac, w=w8)
+
+
+SINGLE_NODES = ("_Projection", "_CovarProjection", "_PackedProjection", "_PackedCovarProjection")
+
+
+@pytest.mark.parametrize("aa", [False, True], ids=list(MODES))
+@pytest.mark.parametrize("node", SINGLE_NODES)
+def test_single_cotangent_backwards(env, node, aa):
+    """Each of the four projection nodes, applied directly: the backward of a loss that touches ONE of means2d, conics,
+    depths (and, antialiased, the compensation) against the backward of the same loss plus ``(other * 0).sum()`` for
+    every output it does not touch, i.e. a missing cotangent against an explicit zero one: the gradients of means, of
+    the shape tensors and of viewmats are torch.equal.  (These kernels use no float atomics -- packed.hip,
+    viewmat_grad.hip and functional.hip say so -- and the same call gives the same bits twice.)  Every zero-fill branch of
+    the shared cotangent code, dense and packed, with the pose gradient on."""
+    R = env
+    s = _single_cotangent_scene()
+    packed, covar = "Packed" in node, "Covar" in node
+    touched = ("means2d", "conics", "depths") + (("comps",) if aa else ())
+
+    def run(name, explicit):
+        m = s["means"].cuda().requires_grad_(True)
+        shape = [s["covars"].cuda().requires_grad_(True)] if covar else [s["quats"].cuda().requires_grad_(True),
+                                                                         s["scales"].cuda().requires_grad_(True)]
+        vm = s["vms"].cuda().requires_grad_(True)
+        tail = (False, {}) if packed else ()
+        out = getattr(R, node).apply(m, *shape, s["opac"].cuda(), vm, s["Ks"].cuda(), 70, 52, 0.3, 0.01, 5.0, 0.0, aa, *tail)
+        outs = dict(radii=out[0], means2d=out[1], depths=out[2], conics=out[3], comps=out[4])
+        if packed:
+            cam, gid = out[8], out[9]
+            vis = torch.zeros(2, 200, dtype=torch.bool, device="cuda")
+            vis[cam, gid] = True
+            pick = lambda t: t.cuda()[cam, gid]
+        else:
+            vis = outs["radii"] > 0
+            pick = lambda t: t.cuda()
+        loss = (outs[name] * pick(s["w"][name])).sum()
+        if explicit:
+            loss = loss + sum((outs[k] * 0).sum() for k in touched if k != name)
+        loss.backward()
+        return vis, [m.grad, *[t.grad for t in shape], vm.grad]
+
+    for name in touched:
+        vis, missing = run(name, False)
+        _vis, explicit = run(name, True)
+        n_vis = vis.sum(dim=1).tolist()
+        assert n_vis[0] == 200 and 40 <= n_vis[1] <= 160, n_vis   # (far_plane culls rows of the second camera alone)
+        assert len(missing) == (3 if covar else 4)
+        for a, b in zip(missing, explicit):
+            assert a is not None and a.shape == b.shape and torch.equal(a, b), (node, name)
+        assert missing[0].abs().max() > 0 and missing[-1].abs().max() > 0, (node, name)
+        assert not missing[-1][:, 3].any()

@@ -234,3 +234,43 @@ def test_arguments_through_rasterization(env, mode, eps2d, monkeypatch):
     assert_close(gpu["alpha"][keep], cpu["alpha"][keep], name="alpha")
     for name, a, b in zip(("means", "quats", "scales", "opacities", "colors"), gpu["grads"], cpu["grads"]):
         assert_close(a, b, name=f"grad {name}")
+
+
+# ---------------------------------------------------------------------------------------------------
+def cat_calls_in_backward(rasterization, unit, monkeypatch):
+    """torch.cat calls during the backward of render.sum() + alphas.sum() of a dense three-camera call (300 Gaussians,
+    70 x 52, absgrad=False): D = 3 colours that require grad, or with `unit` torch.ones(N, 3) without grad."""
+    from edgegaussians_amd import synth
+    sc = synth.make_scene(300, 3, 70, 52, seed=5, spread_opacity=True, scale=0.05)
+    p = [t.clone().cuda().requires_grad_(True) for t in (sc.means, sc.quats, sc.log_scales, sc.logit_opacities)]
+    N = p[0].shape[0]
+    if unit:
+        colors = torch.ones(N, 3, device="cuda")
+    else:
+        colors = (0.2 + 0.8 * torch.rand(N, 3, generator=torch.Generator().manual_seed(5))).cuda().requires_grad_(True)
+    render, alphas, _info = rasterization(p[0], p[1], torch.exp(p[2]), torch.sigmoid(p[3]).squeeze(-1), colors,
+                                          sc.viewmats.cuda(), sc.Ks.cuda(), 70, 52, packed=False, absgrad=False)
+    assert float(alphas.detach().mean()) > 0.05
+    calls = []
+    real_cat = torch.cat
+    monkeypatch.setattr(torch, "cat", lambda *a, **k: (calls.append(1), real_cat(*a, **k))[1])
+    (render.sum() + alphas.sum()).backward()
+    monkeypatch.setattr(torch, "cat", real_cat)
+    assert all(t.grad is not None and t.grad.abs().max() > 0 for t in p[:3])
+    return len(calls)
+
+
+# What the commit before the projection nodes were merged gives, measured on it with this very function: one torch.cat
+# behind colours that require grad, none behind unit colours.  The colour backward (eg_composite_bwd_colors) returns
+# contiguous COPIES of its record's words, so `_Projection.backward` re-packs them once (`_g2d_record`); the shortcut
+# -- both cotangents views of one [C, N, 8] record, passed on as it is -- is the unit-colour footprint backward's.
+CAT_CALLS_OF_THE_PARENT = {False: 1, True: 0}
+
+
+@pytest.mark.parametrize("unit", [False, True], ids=["colours", "unit"])
+def test_backward_repacks_the_cotangent_record_as_often_as_before(env, unit, monkeypatch):
+    """The number of torch.cat calls in the backward of a dense `rasterization` call is the parent commit's
+    (CAT_CALLS_OF_THE_PARENT, measured on the parent): the no-re-pack shortcut of `_Projection.backward` is taken where
+    it was taken, and no other assembly of the cotangent record has appeared."""
+    from edgegaussians_amd import rasterization
+    assert cat_calls_in_backward(rasterization, unit, monkeypatch) == CAT_CALLS_OF_THE_PARENT[unit]
