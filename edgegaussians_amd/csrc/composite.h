@@ -85,6 +85,20 @@ __device__ __forceinline__ float finalize_pixel(int p, float T, int last, bool s
   return l;
 }
 
+// The stop rule of every exact walk (gsplat: stop BEFORE compositing the Gaussian that would take T to <= 1e-4), one
+// list entry, branch-free: a lane with `live` is looking for its stop from transmittance T; `alpha`, `counts` are the
+// entry's alpha at the lane's pixel and whether it contributes there, `pos` its list position.  Written once: the
+// chained kernel, the re-walk kernel and the wave-autonomous forward must agree on where a pixel stops.
+__device__ __forceinline__ void stop_step(float alpha, bool counts, int pos, bool &live, float &T, int &lastpos,
+                                          bool &found) {
+  const float nT = T * (1.f - alpha);
+  const bool hit = live & counts, stop = hit & (nT <= kTStop), upd = hit & !stop;
+  T = upd ? nT : T;
+  lastpos = upd ? pos : lastpos;
+  found = found | stop;
+  live = live & !stop;
+}
+
 // per-pixel hand-off from the combine to the re-walk kernel: the slice in which the stop falls and the state
 // before it
 struct StopInfo {

@@ -27,6 +27,11 @@
 // composite_wave.hip, or -- when it keeps its images and pixels do stop -- the chained kernel below: slice, combine
 // and exact stop in one launch.  General colours, and unit colours without item tables, use the classic
 // one-workgroup-per-tile kernel below.
+// The slice, chained and re-walk kernels must place every pixel's stop alike, so what they have in common is written
+// once ("What the workgroup-per-item forward kernels share" below): stage_slice (record -> threshold, extent, quadrant
+// verdicts -> quadrant lists), product_walk, exact_walk, load_slice_records (the read-back of up to eight slice
+// records), list_index and view_pixels (the per-view pointers of a batched step); the stop rule itself is stop_step
+// of composite.h, which composite_wave.hip's exact walks use too.
 //
 // Backward, unit colours without colour gradients (the reference passes colours == 1, edge_gs.py:247): with c == 1
 // and no background, pix = 1 - T_final, hence dpix/dalpha_i = T_final / (1 - alpha_i) for EVERY contributing
@@ -62,6 +67,19 @@ __device__ __forceinline__ int camera_list_base(const int *__restrict__ offsets,
   int base = 0;
   for (int k = 0; k < c; ++k) base += offsets[(size_t)k * (T + 1) + T];
   return base;
+}
+
+// a workgroup's loss terms -> one atomic add (sRed: 4 floats of LDS; one workgroup barrier)
+__device__ __forceinline__ void block_loss_add(float l, float *sRed, float *__restrict__ loss_out) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d, 64);
+  if ((tid & 63) == 0) sRed[tid >> 6] = l;
+  __syncthreads();
+  if (tid == 0) {
+    const float s = sRed[0] + sRed[1] + sRed[2] + sRed[3];
+    if (s != 0.f) unsafeAtomicAdd(loss_out, s);
+  }
 }
 
 template <int CH, bool UNIT, bool DEPTH = false, bool BG = false>
@@ -164,16 +182,7 @@ composite_fwd_kernel(const float4 *__restrict__ splat, const float *__restrict__
       if (vpix) vpix[p] = loss_scale * w * sgn * pass;
     }
   }
-  if (!kModes && wmap && loss_out) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d, 64);
-    if ((tid & 63) == 0) sRed[tid >> 6] = l;
-    __syncthreads();
-    if (tid == 0) {
-      const float s = sRed[0] + sRed[1] + sRed[2] + sRed[3];
-      if (s != 0.f) unsafeAtomicAdd(loss_out, s);
-    }
-  }
+  if (!kModes && wmap && loss_out) block_loss_add(l, sRed, loss_out);
 }
 
 // The tile owning item b -- the largest t with item_offsets[t] <= b (item_offsets[T] = n_items > b) -- looked up by
@@ -252,6 +261,26 @@ __device__ __forceinline__ int build_quad_lists(QuadLists &ql, const bool (&hitq
   return n_mine;
 }
 
+// slice-local index of the Gaussian at position `pos` of wave wv's list
+__device__ __forceinline__ int list_index(const QuadLists &ql, int wv, int pos) {
+  return __float_as_int(((const float *)&ql.E[wv][pos >> 1])[2 + (pos & 1)]);
+}
+
+// view `bv` of a batched step: the per-pixel outputs (each optional) and the view's target and loss weights.
+// CH: channels of a rendered pixel
+template <int CH>
+__device__ __forceinline__ void view_pixels(const Batch &bt, int bv, float *__restrict__ &render,
+                                            float *__restrict__ &alphas, int *__restrict__ &last_ids,
+                                            float *__restrict__ &vpix, StopRec *__restrict__ &gtstop,
+                                            const float *__restrict__ &gt, const float *__restrict__ &wmap) {
+  if (render) render += bv * bt.pixels * CH;
+  if (alphas) alphas += bv * bt.pixels;
+  if (last_ids) last_ids += bv * bt.pixels;
+  if (vpix) vpix += bv * bt.pixels;
+  if (gtstop) gtstop += bv * bt.pixels;
+  if (bt.gt[0]) { gt = bt.gt[bv]; wmap = bt.wmap[bv]; }
+}
+
 // alpha of a pair of listed Gaussians at pixel (px, py) with packed fp32, and whether each one counts
 typedef float v2f __attribute__((ext_vector_type(2)));
 struct PairEval {
@@ -276,15 +305,122 @@ __device__ __forceinline__ PairEval eval_pair(const float4 X, const float4 Cq, c
   return r;
 }
 
-__device__ __forceinline__ void block_loss_add(float l, float *sRed, float *__restrict__ loss_out) {
-  const int tid = threadIdx.x;
+// ---------------------------------------------------------------------------------------------
+// What the workgroup-per-item forward kernels share.  The chained kernel and the slice -> combine -> re-walk sequence
+// must place every pixel's transmittance stop alike -- the same arithmetic, in the same order -- so the staging, the
+// product walk, the exact walk and the read-back of the slice records are written ONCE, here; the stop rule itself is
+// stop_step of composite.h, shared with the wave-autonomous forward (composite_wave.hip).
+// Deliberately NOT shared:
+//   - the extent arithmetic of the quadrant test: quad_hit / stage_derive of composite_wave.hip are compiled under
+//     `fp contract(off)`, stage_slice below is not -- one copy for both would change bits in one of them;
+//   - eval_pair (here) and eval_entry (composite_wave.hip): the lists have different formats (half conics and a sigma
+//     threshold here, the conic premultiplied by -log2(e) and log2(opacity) there);
+//   - the three ways of combining a tile's slices: the ticket (slice kernel / combine_tail), the look-back (chained
+//     kernel), the granules (composite_wave.hip).  Their folds over the records differ: one records the stop slice,
+//     one a flag.
+
+// Staging: thread tid fetches Gaussian start + tid of the slice [start, end), computes its conservative alpha >= 1/255
+// extent (ex, ey) and tests it against the four quadrants of tile (tx, ty); the verdicts (bit q = quadrant q) come
+// back in `qmask`, the quadrant lists in `ql`.  Returns the length of the calling wave's list.  Two barriers.
+__device__ __forceinline__ int stage_slice(QuadLists &ql, const float4 *__restrict__ splat,
+                                           const int *__restrict__ flat, int start, int end, int tx, int ty, int tid,
+                                           int &qmask) {
+  float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), rB = s0;
+  bool hitq[4] = {false, false, false, false};
+  if (start + tid < end) {
+    const int g = flat[start + tid];
+    s0 = splat[2 * g];
+    const float4 s1 = splat[2 * g + 1];
+    const float thr = __logf(255.f * s1.y) + kThrMargin;
+    rB = make_float4(s1.x, s1.y, thr, __int_as_float(tid));
+    const float det = s0.z * s1.x - s0.w * s0.w;
+    if (thr > 0.f && det > 0.f) {
+      const float k2 = 2.f * thr * __builtin_amdgcn_rcpf(det);  // hardware rcp / sqrt: the inflation covers 1 ulp
+      const float ex = __builtin_amdgcn_sqrtf(k2 * s1.x) * 1.001f + 0.01f;
+      const float ey = __builtin_amdgcn_sqrtf(k2 * s0.z) * 1.001f + 0.01f;
+      const float X0 = (float)(tx * kTile), Y0 = (float)(ty * kTile);
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) l += __shfl_xor(l, d, 64);
-  if ((tid & 63) == 0) sRed[tid >> 6] = l;
-  __syncthreads();
-  if (tid == 0) {
-    const float s = sRed[0] + sRed[1] + sRed[2] + sRed[3];
-    if (s != 0.f) unsafeAtomicAdd(loss_out, s);
+      for (int q = 0; q < 4; ++q) {
+        const float qx = X0 + (float)((q & 1) << 3), qy = Y0 + (float)((q >> 1) << 3);
+        // pixel centres of the quadrant span [q + 0.5, q + 7.5]: AABB reject, then the exact
+        // ellipse-vs-rectangle test (thin diagonal ellipses miss most of their AABB)
+        hitq[q] = (s0.x - ex <= qx + 7.5f) && (s0.x + ex >= qx + 0.5f) && (s0.y - ey <= qy + 7.5f) &&
+                  (s0.y + ey >= qy + 0.5f) &&
+                  ellipse_hits_rect(s0.x, s0.y, s0.z, s0.w, s1.x, thr, qx + 0.5f, qy + 0.5f, qx + 7.5f, qy + 7.5f);
+      }
+    }
+  }
+  qmask = (int)hitq[0] | ((int)hitq[1] << 1) | ((int)hitq[2] << 2) | ((int)hitq[3] << 3);
+  return build_quad_lists(ql, hitq, s0, rB, tid);
+}
+
+// Product walk of wave wv's list: P *= (1 - alpha) over the listed Gaussians that count at the pixel, in depth order;
+// Lpos = list position of the last one (a wave-uniform value per Gaussian; translate with list_index after the walk).
+// Two pairs (four Gaussians) per iteration: all LDS reads of a group are issued before the first use.  No branches:
+// every listed Gaussian reaches some pixel of the quadrant (exact test in the staging), so a wave-level skip never
+// fires and exec-mask bookkeeping is pure overhead; a rejected pair multiplies by 1.
+__device__ __forceinline__ void product_walk(const QuadLists &ql, int wv, int n_mine, const v2f px2, const v2f py2,
+                                             float &P, int &Lpos) {
+  const float4 *lX = ql.X[wv], *lC = ql.C[wv], *lD = ql.D[wv], *lE = ql.E[wv];
+  for (int t = 0; t < n_mine; t += 4) {
+    float4 X[2], Cq[2], D[2], E[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      X[u] = lX[(t >> 1) + u]; Cq[u] = lC[(t >> 1) + u]; D[u] = lD[(t >> 1) + u]; E[u] = lE[(t >> 1) + u];
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const PairEval ev = eval_pair(X[u], Cq[u], D[u], E[u], px2, py2);
+      P *= ev.k0 ? 1.f - ev.a0 : 1.f;  // depth order kept: (P * m0) * m1
+      P *= ev.k1 ? 1.f - ev.a1 : 1.f;
+      Lpos = ev.k0 ? t + 2 * u : Lpos;
+      Lpos = ev.k1 ? t + 2 * u + 1 : Lpos;
+    }
+  }
+}
+
+// Sequential walk of wave wv's list with the stop rule, branch-free inside: lanes with `live` look for their stop
+// from transmittance T; a wave leaves as soon as none of its lanes is looking.  Returns the list position of the last
+// contributor composited here (-1: none).
+__device__ __forceinline__ int exact_walk(const QuadLists &ql, int wv, int n_mine, const v2f px2, const v2f py2,
+                                          bool &live, float &T, bool &found) {
+  const float4 *lX = ql.X[wv], *lC = ql.C[wv], *lD = ql.D[wv], *lE = ql.E[wv];
+  int lastpos = -1;
+  for (int t = 0; t < n_mine && __ballot(live) != 0ull; t += 4) {
+    float4 X[2], Cq[2], D[2], E[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      X[u] = lX[(t >> 1) + u]; Cq[u] = lC[(t >> 1) + u]; D[u] = lD[(t >> 1) + u]; E[u] = lE[(t >> 1) + u];
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const PairEval ev = eval_pair(X[u], Cq[u], D[u], E[u], px2, py2);
+      stop_step(ev.a0, ev.k0, t + 2 * u, live, T, lastpos, found);
+      stop_step(ev.a1, ev.k1, t + 2 * u + 1, live, T, lastpos, found);
+    }
+  }
+  return lastpos;
+}
+
+// The records (product, last contributor) of up to eight slices, items item0 .. item0 + n - 1, all in flight before
+// the first is used (a walk over a tile's slices is a chain of round trips); slots beyond n hold the neutral record
+// (1, -1).  DEVICE_SCOPE: the records were published inside the same launch (another XCD's L2 may hold the line);
+// plain loads after a kernel boundary.
+template <bool DEVICE_SCOPE>
+__device__ __forceinline__ void load_slice_records(const SliceWs &ws, int item0, int n, int tid, float (&Ps)[8],
+                                                   int (&Ls)[8]) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const bool ok = u < n;
+    const size_t o = (size_t)(item0 + (ok ? u : 0)) * kTilePix + tid;
+    if (DEVICE_SCOPE) {
+      Ps[u] = __hip_atomic_load(&ws.sliceP[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      Ls[u] = __hip_atomic_load(&ws.sliceL[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      Ps[u] = ws.sliceP[o];
+      Ls[u] = ws.sliceL[o];
+    }
+    if (!ok) { Ps[u] = 1.f; Ls[u] = -1; }
   }
 }
 
@@ -301,22 +437,9 @@ __device__ __forceinline__ void combine_tail(int tile, int tid, int i0, int ns, 
                                              StopRec *__restrict__ gtstop, float *sRed, bool rewalk_skipped) {
   if (ns > 1) {
     for (int s8 = 0; s8 < ns && stop_slice < 0; s8 += 8) {
-      // eight slices' records in flight per wait (the walk over a tile's slices is a chain of round trips)
       float Ps[8];
       int Ls[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const bool ok = s8 + u < ns;
-        const size_t o = (size_t)(i0 + (ok ? s8 + u : 0)) * kTilePix + tid;
-        if (DEVICE_SCOPE) {
-          Ps[u] = __hip_atomic_load(&ws.sliceP[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          Ls[u] = __hip_atomic_load(&ws.sliceL[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-          Ps[u] = ws.sliceP[o];
-          Ls[u] = ws.sliceL[o];
-        }
-        if (!ok) { Ps[u] = 1.f; Ls[u] = -1; }
-      }
+      load_slice_records<DEVICE_SCOPE>(ws, i0 + s8, ns - s8, tid, Ps, Ls);
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         if (Ls[u] < 0 || stop_slice >= 0) continue;
@@ -380,12 +503,7 @@ composite_slice_fwd_kernel(const float4 *__restrict__ splat, const TileTable tt_
   const TileTable tt = view_of(tt_, bt, bv);
   const SliceWs ws = view_of(ws_, bt, bv);
   total += 4 * bv; flat += bv * bt.keys; splat += bv * bt.splat4;
-  if (render) render += bv * bt.pixels * CH;
-  if (alphas) alphas += bv * bt.pixels;
-  if (last_ids) last_ids += bv * bt.pixels;
-  if (vpix) vpix += bv * bt.pixels;
-  if (gtstop) gtstop += bv * bt.pixels;
-  if (bt.gt[0]) { gt = bt.gt[bv]; wmap = bt.wmap[bv]; }
+  view_pixels<CH>(bt, bv, render, alphas, last_ids, vpix, gtstop, gt, wmap);
   const int b = blockIdx.x;
   if (b >= total[2]) return;
   const int tile = tt.item_tile ? tt.item_tile[b] : item_tile_coop(tt.item_first, tw * th, b, sTile);
@@ -399,64 +517,18 @@ composite_slice_fwd_kernel(const float4 *__restrict__ splat, const TileTable tt_
   const int i0 = tt.item_first[tile], ns = tt.item_end[tile] - i0;
   const int start = tt.start[tile] + (b - i0) * kSlice;
   const int end = min(tt.end[tile], start + kSlice);
-  const int idx = start + tid;
   if (tt.cursor_reset && b == i0 && tid == 0) tt.cursor_reset[tile] = 0;
 
   float P = 1.f;
   int L = -1;
   if (end > start) {  // (an empty tile's single item has nothing to walk)
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), rB = s0;
-    bool hitq[4] = {false, false, false, false};
-    if (idx < end) {
-      const int g = flat[idx];
-      s0 = splat[2 * g];
-      const float4 s1 = splat[2 * g + 1];
-      const float thr = __logf(255.f * s1.y) + kThrMargin;
-      rB = make_float4(s1.x, s1.y, thr, __int_as_float(tid));
-      const float det = s0.z * s1.x - s0.w * s0.w;
-      if (thr > 0.f && det > 0.f) {
-        const float k2 = 2.f * thr * __builtin_amdgcn_rcpf(det);  // hardware rcp / sqrt: the inflation covers 1 ulp
-        const float ex = __builtin_amdgcn_sqrtf(k2 * s1.x) * 1.001f + 0.01f;
-        const float ey = __builtin_amdgcn_sqrtf(k2 * s0.z) * 1.001f + 0.01f;
-        const float X0 = (float)(tx * kTile), Y0 = (float)(ty * kTile);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float qx = X0 + (float)((q & 1) << 3), qy = Y0 + (float)((q >> 1) << 3);
-          // pixel centres of the quadrant span [q + 0.5, q + 7.5]: AABB reject, then the exact
-          // ellipse-vs-rectangle test (thin diagonal ellipses miss most of their AABB)
-          hitq[q] = (s0.x - ex <= qx + 7.5f) && (s0.x + ex >= qx + 0.5f) && (s0.y - ey <= qy + 7.5f) &&
-                    (s0.y + ey >= qy + 0.5f) &&
-                    ellipse_hits_rect(s0.x, s0.y, s0.z, s0.w, s1.x, thr, qx + 0.5f, qy + 0.5f, qx + 7.5f, qy + 7.5f);
-        }
-      }
-    }
+    int qmask;
+    const int n_mine = stage_slice(ql, splat, flat, start, end, tx, ty, tid, qmask);
     if (tid < kSlice)  // which quadrants each Gaussian of the slice reaches: reused by the exact-stop re-walk
-      ws.sliceQ[(size_t)b * kSlice + tid] = (unsigned char)((int)hitq[0] | ((int)hitq[1] << 1) | ((int)hitq[2] << 2) |
-                                                            ((int)hitq[3] << 3));
-    const int n_mine = build_quad_lists(ql, hitq, s0, rB, tid);
-
-    const float4 *lX = ql.X[wv], *lC = ql.C[wv], *lD = ql.D[wv], *lE = ql.E[wv];
+      ws.sliceQ[(size_t)b * kSlice + tid] = (unsigned char)qmask;
     const v2f px2 = {px, px}, py2 = {py, py};
-    // Walk, two pairs (four Gaussians) per iteration: all LDS reads of a group are issued before the
-    // first use.  No branches: every listed Gaussian reaches some pixel of the quadrant (exact test
-    // above), so a wave-level skip never fires and exec-mask bookkeeping is pure overhead; a rejected
-    // pair multiplies by 1.
-    for (int t = 0; t < n_mine; t += 4) {
-      float4 X[2], Cq[2], D[2], E[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        X[u] = lX[(t >> 1) + u]; Cq[u] = lC[(t >> 1) + u]; D[u] = lD[(t >> 1) + u]; E[u] = lE[(t >> 1) + u];
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const PairEval ev = eval_pair(X[u], Cq[u], D[u], E[u], px2, py2);
-        P *= ev.k0 ? 1.f - ev.a0 : 1.f;  // depth order kept: (P * m0) * m1
-        P *= ev.k1 ? 1.f - ev.a1 : 1.f;
-        L = ev.k0 ? t + 2 * u : L;       // list position (wave-uniform value); translated once after the walk
-        L = ev.k1 ? t + 2 * u + 1 : L;
-      }
-    }
-    if (L >= 0) L = start + __float_as_int(((const float *)&lE[L >> 1])[2 + (L & 1)]);
+    product_walk(ql, wv, n_mine, px2, py2, P, L);
+    if (L >= 0) L = start + list_index(ql, wv, L);
   }
 
   // the pixel's target and loss weight do not depend on the slices: in flight under the ticket round trip
@@ -504,70 +576,6 @@ composite_slice_fwd_kernel(const float4 *__restrict__ splat, const TileTable tt_
 // by a sequential walk of the quadrant lists that are still in LDS -- no re-staging, no second kernel, no lists)
 // or lies further back.  The workgroup in whose slice a pixel stops finalises that pixel; the last slice
 // finalises the pixels that never stop.  Same arithmetic, in the same order, as slice -> combine -> re-walk.
-__device__ __forceinline__ int stage_slice(QuadLists &ql, const float4 *__restrict__ splat,
-                                           const int *__restrict__ flat, int start, int end, int tx, int ty, int tid) {
-  float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), rB = s0;
-  bool hitq[4] = {false, false, false, false};
-  if (start + tid < end) {
-    const int g = flat[start + tid];
-    s0 = splat[2 * g];
-    const float4 s1 = splat[2 * g + 1];
-    const float thr = __logf(255.f * s1.y) + kThrMargin;
-    rB = make_float4(s1.x, s1.y, thr, __int_as_float(tid));
-    const float det = s0.z * s1.x - s0.w * s0.w;
-    if (thr > 0.f && det > 0.f) {
-      const float k2 = 2.f * thr * __builtin_amdgcn_rcpf(det);
-      const float ex = __builtin_amdgcn_sqrtf(k2 * s1.x) * 1.001f + 0.01f;
-      const float ey = __builtin_amdgcn_sqrtf(k2 * s0.z) * 1.001f + 0.01f;
-      const float X0 = (float)(tx * kTile), Y0 = (float)(ty * kTile);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float qx = X0 + (float)((q & 1) << 3), qy = Y0 + (float)((q >> 1) << 3);
-        hitq[q] = (s0.x - ex <= qx + 7.5f) && (s0.x + ex >= qx + 0.5f) && (s0.y - ey <= qy + 7.5f) &&
-                  (s0.y + ey >= qy + 0.5f) &&
-                  ellipse_hits_rect(s0.x, s0.y, s0.z, s0.w, s1.x, thr, qx + 0.5f, qy + 0.5f, qx + 7.5f, qy + 7.5f);
-      }
-    }
-  }
-  return build_quad_lists(ql, hitq, s0, rB, tid);
-}
-
-// sequential walk of this wave's quadrant list with the stop rule (the re-walk kernel's inner loop): lanes with
-// `live` look for their stop from transmittance T; returns the list position of the last contributor (-1: none)
-__device__ __forceinline__ int exact_walk(const QuadLists &ql, int wv, int n_mine, const v2f px2, const v2f py2,
-                                          bool &live, float &T, bool &found) {
-  const float4 *lX = ql.X[wv], *lC = ql.C[wv], *lD = ql.D[wv], *lE = ql.E[wv];
-  int lastpos = -1;
-  for (int t = 0; t < n_mine && __ballot(live) != 0ull; t += 4) {
-    float4 X[2], Cq[2], D[2], E[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      X[u] = lX[(t >> 1) + u]; Cq[u] = lC[(t >> 1) + u]; D[u] = lD[(t >> 1) + u]; E[u] = lE[(t >> 1) + u];
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const PairEval ev = eval_pair(X[u], Cq[u], D[u], E[u], px2, py2);
-      {
-        const float nT = T * (1.f - ev.a0);
-        const bool hit = live & ev.k0, stop = hit & (nT <= kTStop), upd = hit & !stop;
-        T = upd ? nT : T;
-        lastpos = upd ? t + 2 * u : lastpos;
-        found = found | stop;
-        live = live & !stop;
-      }
-      {
-        const float nT = T * (1.f - ev.a1);
-        const bool hit = live & ev.k1, stop = hit & (nT <= kTStop), upd = hit & !stop;
-        T = upd ? nT : T;
-        lastpos = upd ? t + 2 * u + 1 : lastpos;
-        found = found | stop;
-        live = live & !stop;
-      }
-    }
-  }
-  return lastpos;
-}
-
 __global__ void __launch_bounds__(256)
 composite_chained_fwd_kernel(const float4 *__restrict__ splat, const TileTable tt_, const int *__restrict__ total,
                              const int *__restrict__ flat, int width, int height, int tw, int th, const SliceWs ws_,
@@ -582,6 +590,7 @@ composite_chained_fwd_kernel(const float4 *__restrict__ splat, const TileTable t
   const TileTable tt = view_of(tt_, bt, bv);
   const SliceWs ws = view_of(ws_, bt, bv);
   total += 4 * bv; flat += bv * bt.keys; splat += bv * bt.splat4;
+  // (view_pixels<1>, written out: through the helper this kernel's instructions come out in another order)
   if (render) render += bv * bt.pixels;
   if (alphas) alphas += bv * bt.pixels;
   if (last_ids) last_ids += bv * bt.pixels;
@@ -609,27 +618,12 @@ composite_chained_fwd_kernel(const float4 *__restrict__ splat, const TileTable t
 
   // ---- phase A: this slice's product and last contributor (lists stay in LDS)
   float P = 1.f;
-  int Lpos = -1, n_mine = 0;
+  int Lpos = -1, n_mine = 0, qmask;  // (qmask: the quadrant verdicts, which only the split path keeps)
   if (end > start) {
-    n_mine = stage_slice(ql, splat, flat, start, end, tx, ty, tid);
-    const float4 *lX = ql.X[wv], *lC = ql.C[wv], *lD = ql.D[wv], *lE = ql.E[wv];
-    for (int t = 0; t < n_mine; t += 4) {
-      float4 X[2], Cq[2], D[2], E[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        X[u] = lX[(t >> 1) + u]; Cq[u] = lC[(t >> 1) + u]; D[u] = lD[(t >> 1) + u]; E[u] = lE[(t >> 1) + u];
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const PairEval ev = eval_pair(X[u], Cq[u], D[u], E[u], px2, py2);
-        P *= ev.k0 ? 1.f - ev.a0 : 1.f;
-        P *= ev.k1 ? 1.f - ev.a1 : 1.f;
-        Lpos = ev.k0 ? t + 2 * u : Lpos;
-        Lpos = ev.k1 ? t + 2 * u + 1 : Lpos;
-      }
-    }
+    n_mine = stage_slice(ql, splat, flat, start, end, tx, ty, tid, qmask);
+    product_walk(ql, wv, n_mine, px2, py2, P, Lpos);
   }
-  const int L = (Lpos >= 0) ? start + __float_as_int(((const float *)&ql.E[wv][Lpos >> 1])[2 + (Lpos & 1)]) : -1;
+  const int L = (Lpos >= 0) ? start + list_index(ql, wv, Lpos) : -1;
 
   // ---- publish for the slices behind this one (the last slice has nobody behind it)
   if (s_me < ns - 1) {
@@ -652,14 +646,7 @@ composite_chained_fwd_kernel(const float4 *__restrict__ splat, const TileTable t
     __syncthreads();
     float Ps[8];
     int Ls[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const bool ok = u < nb;
-      const size_t o = (size_t)(i0 + j8 + (ok ? u : 0)) * kTilePix + tid;
-      Ps[u] = __hip_atomic_load(&ws.sliceP[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      Ls[u] = __hip_atomic_load(&ws.sliceL[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (!ok) { Ps[u] = 1.f; Ls[u] = -1; }
-    }
+    load_slice_records<true>(ws, i0 + j8, nb, tid, Ps, Ls);
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       if (Ls[u] < 0 || before) continue;
@@ -683,14 +670,14 @@ composite_chained_fwd_kernel(const float4 *__restrict__ splat, const TileTable t
     // crossing past the slice end, the same lanes carry on through the following slices (staged afresh)
     bool live = cross;
     const int lp = exact_walk(ql, wv, n_mine, px2, py2, live, T, found);
-    if (lp >= 0) last = start + __float_as_int(((const float *)&ql.E[wv][lp >> 1])[2 + (lp & 1)]);
+    if (lp >= 0) last = start + list_index(ql, wv, lp);
     for (int s2 = s_me + 1; s2 < ns; ++s2) {
       if (!__syncthreads_or(cross && !found)) break;
       const int st2 = t_start + s2 * kSlice, en2 = min(t_end, st2 + kSlice);
-      const int n2 = stage_slice(ql, splat, flat, st2, en2, tx, ty, tid);
+      const int n2 = stage_slice(ql, splat, flat, st2, en2, tx, ty, tid, qmask);
       live = cross && !found;
       const int lp2 = exact_walk(ql, wv, n2, px2, py2, live, T, found);
-      if (lp2 >= 0) last = st2 + __float_as_int(((const float *)&ql.E[wv][lp2 >> 1])[2 + (lp2 & 1)]);
+      if (lp2 >= 0) last = st2 + list_index(ql, wv, lp2);
     }
   }
   // ---- finalise: the pixels that stop here (whichever way the exact walk ended), and -- in the last slice -- the
@@ -715,12 +702,7 @@ composite_combine_fwd_kernel(const TileTable tt_, const int *__restrict__ flat, 
   const TileTable tt = view_of(tt_, bt, bv);
   const SliceWs ws = view_of(ws_, bt, bv);
   flat += bv * bt.keys;
-  if (render) render += bv * bt.pixels * CH;
-  if (alphas) alphas += bv * bt.pixels;
-  if (last_ids) last_ids += bv * bt.pixels;
-  if (vpix) vpix += bv * bt.pixels;
-  if (gtstop) gtstop += bv * bt.pixels;
-  if (bt.gt[0]) { gt = bt.gt[bv]; wmap = bt.wmap[bv]; }
+  view_pixels<CH>(bt, bv, render, alphas, last_ids, vpix, gtstop, gt, wmap);
   const int tile = blockIdx.x, tid = threadIdx.x;
   const int i0 = tt.item_first[tile], ns = tt.item_end[tile] - i0;
   if (ns <= 1) return;  // finalised by its slice workgroup
@@ -754,12 +736,7 @@ composite_rewalk_fwd_kernel(const float4 *__restrict__ splat, const TileTable tt
   const TileTable tt = view_of(tt_, bt, bv);
   const SliceWs ws = view_of(ws_, bt, bv);
   flat += bv * bt.keys; splat += bv * bt.splat4;
-  if (render) render += bv * bt.pixels * CH;
-  if (alphas) alphas += bv * bt.pixels;
-  if (last_ids) last_ids += bv * bt.pixels;
-  if (vpix) vpix += bv * bt.pixels;
-  if (gtstop) gtstop += bv * bt.pixels;
-  if (bt.gt[0]) { gt = bt.gt[bv]; wmap = bt.wmap[bv]; }
+  view_pixels<CH>(bt, bv, render, alphas, last_ids, vpix, gtstop, gt, wmap);
   const int tid = threadIdx.x, wv = tid >> 6;
   int di, dj;
   quad_pixel(tid, di, dj);
@@ -797,39 +774,9 @@ composite_rewalk_fwd_kernel(const float4 *__restrict__ splat, const TileTable tt
       for (int q = 0; q < 4; ++q) hitq[q] = (m >> q) & 1;
     }
     const int n_mine = build_quad_lists(ql, hitq, g0, rB, tid);
-    const float4 *lX = ql.X[wv], *lC = ql.C[wv], *lD = ql.D[wv], *lE = ql.E[wv];
-    // sequential walk with the stop rule, branch-free inside: `live` lanes are still looking for
-    // their stop; a wave leaves as soon as none of its lanes is
     bool live = mine && !found;
-    int lastpos = -1;
-    for (int t = 0; t < n_mine && __ballot(live) != 0ull; t += 4) {
-      float4 X[2], Cq[2], D[2], E[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        X[u] = lX[(t >> 1) + u]; Cq[u] = lC[(t >> 1) + u]; D[u] = lD[(t >> 1) + u]; E[u] = lE[(t >> 1) + u];
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const PairEval ev = eval_pair(X[u], Cq[u], D[u], E[u], px2, py2);
-        {
-          const float nT = T * (1.f - ev.a0);
-          const bool hit = live & ev.k0, stop = hit & (nT <= kTStop), upd = hit & !stop;
-          T = upd ? nT : T;
-          lastpos = upd ? t + 2 * u : lastpos;
-          found = found | stop;
-          live = live & !stop;
-        }
-        {
-          const float nT = T * (1.f - ev.a1);
-          const bool hit = live & ev.k1, stop = hit & (nT <= kTStop), upd = hit & !stop;
-          T = upd ? nT : T;
-          lastpos = upd ? t + 2 * u + 1 : lastpos;
-          found = found | stop;
-          live = live & !stop;
-        }
-      }
-    }
-    if (lastpos >= 0) last = start + __float_as_int(((const float *)&lE[lastpos >> 1])[2 + (lastpos & 1)]);
+    const int lastpos = exact_walk(ql, wv, n_mine, px2, py2, live, T, found);
+    if (lastpos >= 0) last = start + list_index(ql, wv, lastpos);
   }
   float l = 0.f;
   if (mine)

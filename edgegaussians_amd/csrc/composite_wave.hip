@@ -155,6 +155,18 @@ __device__ __forceinline__ void put_entry_staged(WaveList &wl, int pos, const fl
   wl.idx[pos] = (unsigned char)slice_idx;
 }
 
+// the three rejecting entries behind a list of n_mine (the walks read four entries at a time): log2(opacity) = -1e30
+// => alpha = 0
+template <class WaveList>
+__device__ __forceinline__ void put_sentinels(WaveList &wl, int n_mine, int lane) {
+  if (lane < 3) {
+    const int e = n_mine + lane, pr = e >> 1, sl = e & 1;
+    ((float *)&wl.X[pr])[sl] = 0.f; ((float *)&wl.X[pr])[2 + sl] = 0.f;
+    ((float *)&wl.C[pr])[sl] = 0.f; ((float *)&wl.C[pr])[2 + sl] = 0.f;
+    ((float *)&wl.D[pr])[sl] = 0.f; ((float *)&wl.D[pr])[2 + sl] = -1e30f;
+  }
+}
+
 __device__ __forceinline__ void wave_lds_fence() {
   // LDS operations of one wave complete in order; this only keeps the compiler from moving them across
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -192,12 +204,7 @@ __device__ __forceinline__ int stage_rounds(WaveList &wl, const float4 *__restri
 #pragma unroll
   for (int r = 0; r < R; ++r)
     if (hit[r]) put_entry(wl, base[r] + __popcll(bal[r] & lt), r0[r], r1[r], lane + 64 * r);
-  if (lane < 3) {  // sentinels: log2(opacity) = -1e30 => alpha = 0
-    const int e = n_mine + lane, pr = e >> 1, sl = e & 1;
-    ((float *)&wl.X[pr])[sl] = 0.f; ((float *)&wl.X[pr])[2 + sl] = 0.f;
-    ((float *)&wl.C[pr])[sl] = 0.f; ((float *)&wl.C[pr])[2 + sl] = 0.f;
-    ((float *)&wl.D[pr])[sl] = 0.f; ((float *)&wl.D[pr])[2 + sl] = -1e30f;
-  }
+  put_sentinels(wl, n_mine, lane);
   wave_lds_fence();
   return n_mine;
 }
@@ -228,12 +235,7 @@ __device__ __forceinline__ int stage_from_lds(WaveList &wl, const Stage &st, int
 #pragma unroll
   for (int r = 0; r < R; ++r)
     if (hit[r]) put_entry_staged(wl, base[r] + __popcll(bal[r] & lt), r0[r], r1[r], lane + 64 * r);
-  if (lane < 3) {  // sentinels: log2(opacity) = -1e30 => alpha = 0
-    const int e = n_mine + lane, pr = e >> 1, sl = e & 1;
-    ((float *)&wl.X[pr])[sl] = 0.f; ((float *)&wl.X[pr])[2 + sl] = 0.f;
-    ((float *)&wl.C[pr])[sl] = 0.f; ((float *)&wl.C[pr])[2 + sl] = 0.f;
-    ((float *)&wl.D[pr])[sl] = 0.f; ((float *)&wl.D[pr])[2 + sl] = -1e30f;
-  }
+  put_sentinels(wl, n_mine, lane);
   wave_lds_fence();
   return n_mine;
 }
@@ -265,27 +267,32 @@ __device__ __forceinline__ EntryEval eval_entry(float x, float y, float A, float
   return r;
 }
 
+// phase A, list entries t .. t + 3: their factors (1 - alpha) onto P in depth order, and (TRACK) the list position of the
+// last contributor
+template <bool TRACK, class WaveList>
+__device__ __forceinline__ void walk4(const WaveList &wl, int t, float px, float py, float &P, int &Lpos) {
+  const int p = t >> 1;
+  const float4 X0 = wl.X[p], X1 = wl.X[p + 1], C0 = wl.C[p], C1 = wl.C[p + 1], D0 = wl.D[p], D1 = wl.D[p + 1];
+  const EntryEval e0 = eval_entry(X0.x, X0.z, C0.x, C0.z, D0.x, D0.z, px, py);
+  const EntryEval e1 = eval_entry(X0.y, X0.w, C0.y, C0.w, D0.y, D0.w, px, py);
+  const EntryEval e2 = eval_entry(X1.x, X1.z, C1.x, C1.z, D1.x, D1.z, px, py);
+  const EntryEval e3 = eval_entry(X1.y, X1.w, C1.y, C1.w, D1.y, D1.w, px, py);
+  P *= e0.k ? 1.f - e0.a : 1.f;  // depth order kept: ((P m0) m1) m2 ...
+  P *= e1.k ? 1.f - e1.a : 1.f;
+  P *= e2.k ? 1.f - e2.a : 1.f;
+  P *= e3.k ? 1.f - e3.a : 1.f;
+  if (TRACK) {
+    Lpos = e0.k ? t : Lpos;
+    Lpos = e1.k ? t + 1 : Lpos;
+    Lpos = e2.k ? t + 2 : Lpos;
+    Lpos = e3.k ? t + 3 : Lpos;
+  }
+}
+
 // phase A: product of (1 - alpha) over the list in depth order, and (TRACK) the list position of the last contributor
 template <bool TRACK, class WaveList>
 __device__ __forceinline__ void walk_list(const WaveList &wl, int n_mine, float px, float py, float &P, int &Lpos) {
-  for (int t = 0; t < n_mine; t += 4) {
-    const int p = t >> 1;
-    const float4 X0 = wl.X[p], X1 = wl.X[p + 1], C0 = wl.C[p], C1 = wl.C[p + 1], D0 = wl.D[p], D1 = wl.D[p + 1];
-    const EntryEval e0 = eval_entry(X0.x, X0.z, C0.x, C0.z, D0.x, D0.z, px, py);
-    const EntryEval e1 = eval_entry(X0.y, X0.w, C0.y, C0.w, D0.y, D0.w, px, py);
-    const EntryEval e2 = eval_entry(X1.x, X1.z, C1.x, C1.z, D1.x, D1.z, px, py);
-    const EntryEval e3 = eval_entry(X1.y, X1.w, C1.y, C1.w, D1.y, D1.w, px, py);
-    P *= e0.k ? 1.f - e0.a : 1.f;  // depth order kept: ((P m0) m1) m2 ...
-    P *= e1.k ? 1.f - e1.a : 1.f;
-    P *= e2.k ? 1.f - e2.a : 1.f;
-    P *= e3.k ? 1.f - e3.a : 1.f;
-    if (TRACK) {
-      Lpos = e0.k ? t : Lpos;
-      Lpos = e1.k ? t + 1 : Lpos;
-      Lpos = e2.k ? t + 2 : Lpos;
-      Lpos = e3.k ? t + 3 : Lpos;
-    }
-  }
+  for (int t = 0; t < n_mine; t += 4) walk4<TRACK>(wl, t, px, py, P, Lpos);
 }
 
 // Phase A with CHECKPOINTS (chained mode): the product and the last contributor after every quarter of the list
@@ -300,22 +307,7 @@ __device__ __forceinline__ void walk_list_ck(const WaveList &wl, int n_mine, flo
 #pragma unroll
   for (int seg = 0; seg < 4; ++seg) {
     const int t1 = min(n_mine, kSeg * (seg + 1));
-    for (int t = kSeg * seg; t < t1; t += 4) {
-      const int p = t >> 1;
-      const float4 X0 = wl.X[p], X1 = wl.X[p + 1], C0 = wl.C[p], C1 = wl.C[p + 1], D0 = wl.D[p], D1 = wl.D[p + 1];
-      const EntryEval e0 = eval_entry(X0.x, X0.z, C0.x, C0.z, D0.x, D0.z, px, py);
-      const EntryEval e1 = eval_entry(X0.y, X0.w, C0.y, C0.w, D0.y, D0.w, px, py);
-      const EntryEval e2 = eval_entry(X1.x, X1.z, C1.x, C1.z, D1.x, D1.z, px, py);
-      const EntryEval e3 = eval_entry(X1.y, X1.w, C1.y, C1.w, D1.y, D1.w, px, py);
-      P *= e0.k ? 1.f - e0.a : 1.f;
-      P *= e1.k ? 1.f - e1.a : 1.f;
-      P *= e2.k ? 1.f - e2.a : 1.f;
-      P *= e3.k ? 1.f - e3.a : 1.f;
-      Lpos = e0.k ? t : Lpos;
-      Lpos = e1.k ? t + 1 : Lpos;
-      Lpos = e2.k ? t + 2 : Lpos;
-      Lpos = e3.k ? t + 3 : Lpos;
-    }
+    for (int t = kSeg * seg; t < t1; t += 4) walk4<true>(wl, t, px, py, P, Lpos);
     ck[seg] = P;
     ckL = (ckL & ~(0xffu << (8 * seg))) | (((unsigned)Lpos & 0xffu) << (8 * seg));  // (-1 -> 0xff: none yet)
   }
@@ -334,22 +326,8 @@ __device__ __forceinline__ int exact_walk_lane(const WaveList &wl, int n_mine, i
     const float4 X0 = wl.X[p], C0 = wl.C[p], D0 = wl.D[p];
     const EntryEval e0 = eval_entry(X0.x, X0.z, C0.x, C0.z, D0.x, D0.z, px, py);
     const EntryEval e1 = eval_entry(X0.y, X0.w, C0.y, C0.w, D0.y, D0.w, px, py);
-    {
-      const float nT = T * (1.f - e0.a);
-      const bool hit = live & e0.k, stop = hit & (nT <= kTStop), upd = hit & !stop;
-      T = upd ? nT : T;
-      lastpos = upd ? pos : lastpos;
-      found = found | stop;
-      live = live & !stop;
-    }
-    {
-      const float nT = T * (1.f - e1.a);
-      const bool hit = live & e1.k, stop = hit & (nT <= kTStop), upd = hit & !stop;
-      T = upd ? nT : T;
-      lastpos = upd ? pos + 1 : lastpos;
-      found = found | stop;
-      live = live & !stop;
-    }
+    stop_step(e0.a, e0.k, pos, live, T, lastpos, found);
+    stop_step(e1.a, e1.k, pos + 1, live, T, lastpos, found);
     pos += 2;
     live = live & (pos < n_mine);
   }
@@ -368,22 +346,8 @@ __device__ __forceinline__ int exact_walk_wave(const WaveList &wl, int n_mine, f
     const float4 X0 = wl.X[p], C0 = wl.C[p], D0 = wl.D[p];
     const EntryEval e0 = eval_entry(X0.x, X0.z, C0.x, C0.z, D0.x, D0.z, px, py);
     const EntryEval e1 = eval_entry(X0.y, X0.w, C0.y, C0.w, D0.y, D0.w, px, py);
-    {
-      const float nT = T * (1.f - e0.a);
-      const bool hit = live & e0.k, stop = hit & (nT <= kTStop), upd = hit & !stop;
-      T = upd ? nT : T;
-      lastpos = upd ? t : lastpos;
-      found = found | stop;
-      live = live & !stop;
-    }
-    {
-      const float nT = T * (1.f - e1.a);
-      const bool hit = live & e1.k, stop = hit & (nT <= kTStop), upd = hit & !stop;
-      T = upd ? nT : T;
-      lastpos = upd ? t + 1 : lastpos;
-      found = found | stop;
-      live = live & !stop;
-    }
+    stop_step(e0.a, e0.k, t, live, T, lastpos, found);
+    stop_step(e1.a, e1.k, t + 1, live, T, lastpos, found);
   }
   return lastpos;
 }
