@@ -949,6 +949,25 @@ int eg_sh_bwd(int32_t degree, int32_t K, int32_t C, int32_t N, const float *dirs
               const float *v_colors /*[C,N,3]*/, float *v_coeffs, float *v_dirs /*[C,N,3] or NULL*/,
               float *v_means /*[N,3] or NULL*/, eg_stream_t stream);
 
+/* ---- fused SSIM (the `fused_ssim` operation of 3DGS trainers), csrc/ssim.hip; edgegaussians_amd/ssim.py.
+ * S[b, c] = A1 A2 / (B1 B2) of the five moments m1 = G*img1, m2 = G*img2, e11 = G*img1^2, e22 = G*img2^2,
+ * e12 = G*(img1 img2), G* = the 11-tap Gaussian (sigma 1.5, normalised, fp32) along W then along H with zero padding of 5,
+ * per (b, c) plane; s1 = e11 - m1^2, s2 = e22 - m2^2, s12 = e12 - m1 m2, A1 = 2 m1 m2 + C1, A2 = 2 s12 + C2,
+ * B1 = m1^2 + m2^2 + C1, B2 = s1 + s2 + C2, C1 = 0.01^2, C2 = 0.03^2.  img1 / img2 are [B, C, H, W] fp32 read through
+ * their own element strides (host arrays of four: b, c, h, w; >= 0; the caller guarantees that they address the tensor);
+ * S and the derivative maps d_m1 (dS/dm1 at fixed e11, e22, e12), d_s1 = dS/ds1 and d_s12 = dS/ds12 are contiguous
+ * [B, C, H, W]; the three maps are written when given and must be all given or all NULL (evaluation).
+ * eg_ssim_bwd: v [B, C, H, W] contiguous, the cotangent of S;
+ *   v_img1 = G*(v d_m1) + 2 img1 G*(v d_s1) + img2 G*(v d_s12), stored through img1's strides, every element once by
+ *   one lane: no atomics, the same bits every run.  One launch each.  Null pointers, sizes < 1, B * C > 65535 planes,
+ *   H > 65535 * 32 or W > 2^24 are refused with EG_ERR_ARG before any HIP call. */
+int eg_ssim_fwd(const float *img1, const float *img2, int32_t B, int32_t C, int32_t H, int32_t W,
+                const int64_t *strides1_host /*[4]*/, const int64_t *strides2_host /*[4]*/, float *S,
+                float *d_m1 /*NULL ok*/, float *d_s1 /*NULL ok*/, float *d_s12 /*NULL ok*/, eg_stream_t stream);
+int eg_ssim_bwd(const float *img1, const float *img2, int32_t B, int32_t C, int32_t H, int32_t W,
+                const int64_t *strides1_host /*[4]*/, const int64_t *strides2_host /*[4]*/, const float *v,
+                const float *d_m1, const float *d_s1, const float *d_s12, float *v_img1, eg_stream_t stream);
+
 /* ---- native data-parallel run (edgegaussians_amd/dist.py drives it).  RCCL is dlopen'ed from
  * `librccl_path` (NULL / "": "librccl.so" by the loader's search path) -- the library PyTorch ships, so that the process
  * holds ONE RCCL -- and the communicator is created from a 128-byte ncclUniqueId: rank 0 calls eg_dp_unique_id, the

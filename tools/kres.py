@@ -15,7 +15,7 @@ for line in err.splitlines():
     m = re.search(r"Function Name: (\S+)", line)
     if m:
         cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-        cur = re.sub(r"\(.*", "", cur)
+        cur = re.sub(r"\(.*", "", cur.replace("(anonymous namespace)::", ""))
         rows[cur] = {}
         continue
     m = re.search(r"remark:\s+(\w[\w ]*\w)\s*(?:\[bytes/lane\]|\[waves/SIMD\]|\[bytes/block\])?: (\d+)", line)
