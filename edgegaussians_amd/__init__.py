@@ -6,6 +6,7 @@ kunalchelani/EdgeGaussians) behind the reference's own operator surface.
     from edgegaussians_amd import functional         # gsplat's stage-by-stage API (fully_fused_projection, isect_tiles, ...)
     from edgegaussians_amd import strategy           # gsplat.strategy: DefaultStrategy, MCMCStrategy and their ops
     from edgegaussians_amd.ssim import fused_ssim    # == fused_ssim.fused_ssim (the SSIM term of the 3DGS loss)
+    from edgegaussians_amd import losses             # scalar image losses: projection_loss, photometric_loss, ...
     from edgegaussians_amd import EdgeTrainer        # fused per-view training step (train_gaussians.py:71-106)
 """
 from .rasterizer import rasterization  # noqa: F401
@@ -16,5 +17,6 @@ from . import edges  # noqa: F401  (parametric edges -> points -> metrics)
 from . import functional  # noqa: F401  (gsplat's functional API over the same kernels)
 from . import strategy  # noqa: F401  (gsplat's densification strategies: DefaultStrategy, MCMCStrategy, ops)
 from . import ssim  # noqa: F401  (fused SSIM: ssim_map, fused_ssim -- the `fused_ssim` package's operation)
+from . import losses  # noqa: F401  (scalar image losses on the device: weighted / masked L1, L1 + D-SSIM)
 
-__all__ = ["rasterization", "spherical_harmonics", "EdgeTrainer", "LRSchedule", "train", "train_epoch", "train_steps_multi", "edges", "functional", "strategy", "ssim"]
+__all__ = ["rasterization", "spherical_harmonics", "EdgeTrainer", "LRSchedule", "train", "train_epoch", "train_steps_multi", "edges", "functional", "strategy", "ssim", "losses"]

@@ -170,6 +170,14 @@ _SIGS = {
     "eg_sh_bwd": [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "eg_ssim_fwd": [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp],
     "eg_ssim_bwd": [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp],
+    "eg_photometric_fwd": [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), _i32, _f, _vp, _vp, _vp, _vp,
+                           _i64, _vp, _vp],
+    "eg_photometric_bwd": [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), _i32, _f, _vp, _vp, _vp, _vp,
+                           _vp, _vp],
+    "eg_loss_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _i32,
+                    _i32, _i32, _vp, _i64, _vp, _vp],
+    "eg_loss_bwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _i32,
+                    _i32, _vp, _vp, _vp, C.POINTER(_i64), _vp],
     "eg_quat_scale_to_covar_preci_fwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp],
     "eg_quat_scale_to_covar_preci_bwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "eg_project_covars_fwd_cams": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _f, _f, _f] + [_vp] * 5 + [_vp],

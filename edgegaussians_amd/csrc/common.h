@@ -163,6 +163,26 @@ __device__ __forceinline__ float wave_sum_dpp_f(float x) {
 #undef EG_DPP_STEPF
   return x;
 }
+// Sum of one float per lane over a workgroup of THREADS lanes (all of them active), valid in every lane: the DPP tree of
+// each wave, then the waves' sums added in wave order through wave_tmp [THREADS / 64] (LDS; one array per call site).
+template <int THREADS>
+__device__ __forceinline__ float block_sum_f(float x, float *wave_tmp) {
+  x = wave_sum_dpp_f(x);
+  if ((threadIdx.x & 63) == 63) wave_tmp[threadIdx.x >> 6] = x;
+  __syncthreads();
+  float s = wave_tmp[0];
+#pragma unroll
+  for (int w = 1; w < THREADS / 64; ++w) s += wave_tmp[w];
+  return s;
+}
+// The n partial sums slab[0], slab[stride], slab[2 stride], .. added by ONE full wave in a fixed order: lane l adds
+// the partials l, l + 64, .. in index order, then the DPP tree.  Valid in lane 63.  (losses.hip, ssim.hip: the finalize
+// kernels of the scalar losses -- the same bits on every run, no atomics.)
+__device__ __forceinline__ float slab_sum_f(const float *__restrict__ slab, int n, int stride) {
+  float acc = 0.f;
+  for (int i = threadIdx.x & 63; i < n; i += 64) acc += slab[(size_t)i * stride];
+  return wave_sum_dpp_f(acc);
+}
 // the value of the neighbouring lane (lane ^ 1): quad_perm [1, 0, 3, 2]
 __device__ __forceinline__ float lane_xor1_f(float x) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, false));
@@ -171,6 +191,17 @@ struct OpAdd { __device__ __forceinline__ int operator()(int a, int b) const { r
 struct OpMaxI { __device__ __forceinline__ int operator()(int a, int b) const { return a > b ? a : b; } };
 struct OpMinU { __device__ __forceinline__ int operator()(int a, int b) const { return (unsigned)a < (unsigned)b ? a : b; } };
 struct OpMaxU { __device__ __forceinline__ int operator()(int a, int b) const { return (unsigned)a > (unsigned)b ? a : b; } };
+// block_sum_f for one int per lane (exact)
+template <int THREADS>
+__device__ __forceinline__ int block_sum_i(int x, int *wave_tmp) {
+  x = wave_scan_dpp(x, 0, OpAdd());
+  if ((threadIdx.x & 63) == 63) wave_tmp[threadIdx.x >> 6] = x;
+  __syncthreads();
+  int s = wave_tmp[0];
+#pragma unroll
+  for (int w = 1; w < THREADS / 64; ++w) s += wave_tmp[w];
+  return s;
+}
 #endif
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -968,6 +968,48 @@ int eg_ssim_bwd(const float *img1, const float *img2, int32_t B, int32_t C, int3
                 const int64_t *strides1_host /*[4]*/, const int64_t *strides2_host /*[4]*/, const float *v,
                 const float *d_m1, const float *d_s1, const float *d_s12, float *v_img1, eg_stream_t stream);
 
+/* ---- the photometric loss as a scalar, csrc/ssim.hip; edgegaussians_amd/losses.py: photometric_loss.
+ * out[0] = (1 - lambda) out[1] + lambda (1 - out[2]), out[1] = mean |img1 - img2| over B C H W, out[2] = the mean of
+ * the map S of eg_ssim_fwd -- over all of it, or with valid != 0 over its crop by 5 on every side (H, W >= 11).  No map
+ * is written: every workgroup (one per 32 x 32 tile of a plane) leaves its two partial sums in slab [slab_len >= 2 G],
+ * G = ceil(W / 32) ceil(H / 32) B C, and a second launch adds them in index order: no atomics, the same bits every run.
+ * d_m1, d_s1, d_s12 (all three or none) receive the derivative maps, zero outside the crop.  img1 / img2, their strides
+ * and the limits on the sizes are those of eg_ssim_fwd.
+ * eg_photometric_bwd, one launch: v_img1 = v [ (1 - lambda) / n sign(img1 - img2) - lambda / n_S (G*d_m1 + 2 img1
+ *   G*d_s1 + img2 G*d_s12) ] through img1's strides, n = B C H W, n_S the number of map elements the mean ran over,
+ *   v ONE float on the device (the cotangent of out[0]), sign(0) = 0. */
+int eg_photometric_fwd(const float *img1, const float *img2, int32_t B, int32_t C, int32_t H, int32_t W,
+                       const int64_t *strides1_host /*[4]*/, const int64_t *strides2_host /*[4]*/, int32_t valid,
+                       float lambda, float *d_m1 /*NULL ok*/, float *d_s1 /*NULL ok*/, float *d_s12 /*NULL ok*/,
+                       float *slab, int64_t slab_len, float *out /*[3]*/, eg_stream_t stream);
+int eg_photometric_bwd(const float *img1, const float *img2, int32_t B, int32_t C, int32_t H, int32_t W,
+                       const int64_t *strides1_host /*[4]*/, const int64_t *strides2_host /*[4]*/, int32_t valid,
+                       float lambda, const float *v /*[1]*/, const float *d_m1, const float *d_s1, const float *d_s12,
+                       float *v_img1, eg_stream_t stream);
+
+/* ---- scalar pointwise image losses, csrc/losses.hip; edgegaussians_amd/losses.py.
+ * t_p = w_p |c(x_p) - y_p|^q over a logical [B, C, H, W] problem (B C H W < 2^31): q = 1 or 2; c = clamp(., 0, 1) when
+ * clamp != 0; w_kind 0: w_p = 1 (w NULL), 1: w fp32, 2: w a bool mask read as bytes.  x, y, w are each read through
+ * their own four element strides (host arrays; >= 0, 0 = a broadcast dimension; the caller guarantees that they address
+ * the tensors); work is assigned by the logical index, so the bits of the result do not depend on the strides.
+ * eg_loss_fwd, two launches: every workgroup (1024 consecutive logical indices) leaves its partial sum -- and with a
+ *   mask its count of selected elements, an integer -- in slab [slab_words >= G 4-byte words, 2 G with a mask],
+ *   G = ceil(B C H W / 1024); the second launch adds them in index order.  out[0] = sum / D, out[1] = sum, out[2] = D;
+ *   reduction 0: D = 1, 1: D = B C H W, 2 (w_kind 2 only): D = the count (0 selected elements: out[0] is nan).
+ * eg_loss_bwd, one launch: g_p = (v / D) w_p q |c(x_p) - y_p|^(q - 1) sign(c(x_p) - y_p) [0 <= x_p <= 1 when clamped]
+ *   through strides_g (>= 1 wherever the size is above 1); v ONE float on the device, D = fwd_out[2] of the forward;
+ *   sign(0) = 0; exactly 0.0 where the mask is false, the weight is 0 or the gate is shut, whatever v / D is.
+ * No atomics; nothing is read back to the host.  Bad arguments are refused with EG_ERR_ARG before any launch. */
+int eg_loss_fwd(const float *x, const float *y, const void *w /*NULL iff w_kind 0*/, int32_t w_kind, int32_t B, int32_t C,
+                int32_t H, int32_t W, const int64_t *strides_x_host /*[4]*/, const int64_t *strides_y_host /*[4]*/,
+                const int64_t *strides_w_host /*[4], NULL ok with w_kind 0*/, int32_t q, int32_t clamp, int32_t reduction,
+                void *slab, int64_t slab_words, float *out /*[3]*/, eg_stream_t stream);
+int eg_loss_bwd(const float *x, const float *y, const void *w /*NULL iff w_kind 0*/, int32_t w_kind, int32_t B, int32_t C,
+                int32_t H, int32_t W, const int64_t *strides_x_host /*[4]*/, const int64_t *strides_y_host /*[4]*/,
+                const int64_t *strides_w_host /*[4], NULL ok with w_kind 0*/, int32_t q, int32_t clamp,
+                const float *v /*[1]*/, const float *fwd_out /*[3]*/, float *g, const int64_t *strides_g_host /*[4]*/,
+                eg_stream_t stream);
+
 /* ---- native data-parallel run (edgegaussians_amd/dist.py drives it).  RCCL is dlopen'ed from
  * `librccl_path` (NULL / "": "librccl.so" by the loader's search path) -- the library PyTorch ships, so that the process
  * holds ONE RCCL -- and the communicator is created from a 128-byte ncclUniqueId: rank 0 calls eg_dp_unique_id, the
