@@ -178,6 +178,12 @@ _SIGS = {
                     _i32, _i32, _vp, _i64, _vp, _vp],
     "eg_loss_bwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _i32,
                     _i32, _vp, _vp, _vp, C.POINTER(_i64), _vp],
+    "eg_bilagrid_slice_fwd": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i64),
+                              C.POINTER(_i64), _i32, _vp, _vp],
+    "eg_bilagrid_slice_bwd": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i64),
+                              C.POINTER(_i64), _i32, _vp, _vp, _vp, _vp],
+    "eg_bilagrid_tv_fwd": [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
+    "eg_bilagrid_tv_bwd": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     "eg_quat_scale_to_covar_preci_fwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp],
     "eg_quat_scale_to_covar_preci_bwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "eg_project_covars_fwd_cams": [_vp] * 4 + [_i32, _i32, _i32, _i32, _f, _f, _f, _f] + [_vp] * 5 + [_vp],

@@ -1010,6 +1010,47 @@ int eg_loss_bwd(const float *x, const float *y, const void *w /*NULL iff w_kind 
                 const float *v /*[1]*/, const float *fwd_out /*[3]*/, float *g, const int64_t *strides_g_host /*[4]*/,
                 eg_stream_t stream);
 
+/* ---- bilateral grid: slice + apply, and the total-variation regulariser, csrc/bilagrid.hip;
+ * edgegaussians_amd/bilagrid.py (the module docstring states the semantics, tests/bilagrid_util.py in float64).
+ * grids [N, 12, L, Hg, Wg] fp32 contiguous (N 12 L Hg Wg < 2^31).  The samples are a logical [B, H, W] problem
+ * (B H W < 2^31): rgb [B, H, W, 3] and xy [B, H, W, 2] are each read through their own four element strides (host
+ * arrays: b, h, w, last; >= 0, 0 = a broadcast dimension; the caller guarantees that they address the tensors).
+ * grid_idx: [B] int32 (idx_is_int64 0) or int64 (1) on the device, or NULL with B == N (image b uses grid b); the
+ * caller checks its range, the kernels clamp it so that no access leaves the grids.
+ * eg_bilagrid_slice_fwd, one launch: out [B, H, W, 3] contiguous.  While one grid, 48 L Hg Wg bytes, fits
+ *   EG_BILAGRID_LDS_BUDGET the forward and the v_rgb kernel read it from a copy in LDS (persistent workgroups), above it
+ *   from global memory: the same arithmetic and the same bits either way.  max_workgroups (>= 0; 0 = 256, one per
+ *   CU) caps the persistent workgroups of the LDS kernels over all images -- each image gets at least one, and no
+ *   workgroup fewer than 1024 samples -- so a caller can make one workgroup walk many blocks of samples; it changes
+ *   no bit of out or v_rgb.  It is ignored above the budget.  B is not limited beyond B H W < 2^31.
+ * eg_bilagrid_slice_bwd: v [B, H, W, 3] contiguous, the cotangent of out.  v_rgb [B, H, W, 3] contiguous (NULL: not
+ *   wanted) is WRITTEN by one launch, a pure map: the same bits every run.  v_grids, in the shape of grids (NULL: not
+ *   wanted), is ADDED TO with float atomics by one more launch: the caller zeroes it, and its bits depend on the order
+ *   in which the adds arrive.  While one grid's gradient, 48 L Hg Wg bytes, fits EG_BILAGRID_LDS_BUDGET every
+ *   workgroup sums its block of samples in LDS and flushes the non-zero words once; above it the samples add to
+ *   global memory directly, combined per wave where a wave's samples share their cell.
+ * eg_bilagrid_tv_fwd, two launches: out[0] = sum over the axes a of (L, Hg, Wg) with n_a > 1 of
+ *   mean((x[.. i + 1 ..] - x[.. i ..])^2), the mean over all N 12 (n_a - 1) (the other two sizes) differences; slab
+ *   [slab_len >= ceil(N 12 L Hg Wg / 1024)] holds one partial per workgroup, added in index order by the second launch.
+ * eg_bilagrid_tv_bwd, one launch: v_grids = v[0] times the gradient of that value, every cell from its <= 6 neighbours;
+ *   v ONE float on the device.  No atomics in either: the same bits every run.
+ * Bad arguments are refused with EG_ERR_ARG before any launch; nothing is read back to the host. */
+#define EG_BILAGRID_LDS_BUDGET (96 * 1024) /* bytes of LDS the scatter may take: the 8 x 16 x 16 grid exactly */
+int eg_bilagrid_slice_fwd(const float *grids, int32_t N, int32_t L, int32_t Hg, int32_t Wg, const float *rgb,
+                          const float *xy, const void *grid_idx /*NULL ok with B == N*/, int32_t idx_is_int64, int32_t B,
+                          int32_t H, int32_t W, const int64_t *strides_rgb_host /*[4]*/,
+                          const int64_t *strides_xy_host /*[4]*/, int32_t max_workgroups /*0: one per CU*/, float *out,
+                          eg_stream_t stream);
+int eg_bilagrid_slice_bwd(const float *grids, int32_t N, int32_t L, int32_t Hg, int32_t Wg, const float *rgb,
+                          const float *xy, const void *grid_idx /*NULL ok with B == N*/, int32_t idx_is_int64, int32_t B,
+                          int32_t H, int32_t W, const int64_t *strides_rgb_host /*[4]*/,
+                          const int64_t *strides_xy_host /*[4]*/, int32_t max_workgroups /*0: one per CU*/,
+                          const float *v, float *v_rgb /*NULL ok*/, float *v_grids /*NULL ok*/, eg_stream_t stream);
+int eg_bilagrid_tv_fwd(const float *grids, int32_t N, int32_t L, int32_t Hg, int32_t Wg, float *slab, int64_t slab_len,
+                       float *out /*[1]*/, eg_stream_t stream);
+int eg_bilagrid_tv_bwd(const float *grids, int32_t N, int32_t L, int32_t Hg, int32_t Wg, const float *v /*[1]*/,
+                       float *v_grids, eg_stream_t stream);
+
 /* ---- native data-parallel run (edgegaussians_amd/dist.py drives it).  RCCL is dlopen'ed from
  * `librccl_path` (NULL / "": "librccl.so" by the loader's search path) -- the library PyTorch ships, so that the process
  * holds ONE RCCL -- and the communicator is created from a 128-byte ncclUniqueId: rank 0 calls eg_dp_unique_id, the
